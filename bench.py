@@ -9,8 +9,13 @@ floor x residue, IMDCT, window/overlap-add, i16 conversion), inputs (entropy-dec
 in HBM.  Weak scaling: every rank runs the same per-GPU workload on its own streams, no collectives in the data
 path (streams are independent).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line; `cpu_baseline`, `end_to_end`, `other_configs` and
+the oracle check of the timed batch (`config.parity`) are measured with --full only.  --dump-outputs DIR writes the PCM
+the last timed step computed to DIR/pcm.npy (float32, one row per packet; the inputs are seeded, so two builds can be
+compared output for output).
 
 Prints ONE JSON line on rank 0.
 """
@@ -75,6 +80,11 @@ def main():
                          "with LW_BENCH_BACKEND=gloo -- RCCL cannot form a group of two ranks on one device); default: device = LOCAL_RANK")
     ap.add_argument("--streams", type=int, default=256,
                     help="logical streams per 4096-packet batch (each contributes 4096/streams consecutive packets)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: the oracle check of the timed batch, "
+                         "cpu_baseline, end_to_end and other_configs (each of the last three can still be left out by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the PCM of the last timed step to DIR/pcm.npy (float32, packets x samples per packet)")
     args = ap.parse_args()
 
     if not args.no_active_wait:
@@ -266,12 +276,20 @@ def main():
     # device time of the K steps on the launch stream (HIP events), per step
     launch_ms = ev0.elapsed_time(ev1) / args.steps
 
-    # ---- parity of the bytes that were just timed: outs[0] as the last timed replay of batch 0 left it, against the
+    if args.dump_outputs and rank == 0:
+        # the last timed step synthesised batch (W + K - 1) mod N_BATCHES into its output buffer: that buffer as a caller of
+        # lw_batch_synth receives it, one row per packet (every timed packet yields the same number of samples); float32 is exact
+        # for i16.  4096 x 2048 values = 32 MiB
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        last = outs[(args.warmup + args.steps - 1) % N_BATCHES].cpu().numpy()
+        np.save(os.path.join(args.dump_outputs, "pcm.npy"), last.astype(np.float32).reshape(PACKETS_PER_BATCH, -1))
+
+    # ---- parity of the bytes that were just timed (--full): outs[0] as the last timed replay of batch 0 left it, against the
     #      oracle (rank 0): streams 0, S/2 - 1 and S - 1 of that batch, every packet of each, starting from the
     #      primed state (the oracle decodes the priming packet first, exactly as the GPU stream did)
-    parity = None
+    parity = "unchecked (bench.py --full checks the timed batch against the oracle)"
     kernels = batches[0].last_kernels
-    if rank == 0 or world > 1:   # (N > 1: every rank checks the bytes it timed; rank 0 reports all of them, `ranks` below)
+    if args.full and (rank == 0 or world > 1):   # (N > 1: every rank checks the bytes it timed; rank 0 reports all of them, `ranks` below)
         try:
             from oracle import pyoracle as po
             o_id = po.Ident(idp)
@@ -300,7 +318,7 @@ def main():
         per_rank = [None] * world
         dist.all_gather_object(per_rank, mine)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:  # (the contract: rank 0 at N=1 only; null in the N>1 lines)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:  # (the contract: rank 0 at N=1 only; null in the N>1 lines)
         from oracle import pyoracle as po
         o_id = po.Ident(idp)
         o_st = po.Setup(stp, o_id)
@@ -347,7 +365,7 @@ def main():
     # ---- end-to-end rate through the library's staging ring (informational; never `value`): host entropy stage on this
     #      box's cores -> pinned staging -> H2D -> kernels -> D2H, entropy decode of batch N+1 overlapping the GPU work of N
     e2e_obj = None
-    if rank == 0 and world == 1 and not args.no_end_to_end:
+    if args.full and rank == 0 and world == 1 and not args.no_end_to_end:
         try:
             from lewton_amd import e2e as e2e_mod
             best = None
@@ -391,7 +409,7 @@ def main():
     #      timed like the headline (records resident in HBM, rotated batches, hipGraph replay, HIP events) and carries the
     #      oracle check of the PCM its timed launches left for batch 0
     other = None
-    if rank == 0 and world == 1 and not args.no_other_configs:
+    if args.full and rank == 0 and world == 1 and not args.no_other_configs:
         other = {}
         try:
             sys.path.insert(0, os.path.join(ROOT, "tools"))

@@ -26,7 +26,7 @@ def _bench(*flags, env=None):
 
 
 def test_bench_line_through_the_distributed_path_on_one_gpu():
-    d = _bench("--gpus", "1", "--force-dist", "--steps", "20", "--warmup", "8", "--no-end-to-end", "--no-other-configs",
+    d = _bench("--gpus", "1", "--force-dist", "--steps", "20", "--warmup", "8", "--full", "--no-end-to-end", "--no-other-configs",
                "--no-cpu-baseline")
     assert d["n_gpus"] == 1 and d["steps"] == 20 and d["unit"] == "packets/s" and d["scaling"] == "weak"
     assert d["cpu_baseline"] is None and d["end_to_end"] is None and d["other_configs"] is None
@@ -46,7 +46,7 @@ def test_two_ranks_on_one_gpu_run_the_n_gt_1_path():
     e = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", LW_BENCH_BACKEND="gloo")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                           "--master-port", "29547", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "8",
-                          "--device-of-rank", "0,0"], cwd=ROOT, env=e, capture_output=True, text=True, timeout=900)
+                          "--full", "--device-of-rank", "0,0"], cwd=ROOT, env=e, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]   # ONE JSON line, rank 0's
@@ -59,3 +59,21 @@ def test_two_ranks_on_one_gpu_run_the_n_gt_1_path():
     slowest = max(r["elapsed_s"] for r in ranks)
     assert abs(d["ms_per_step"] - slowest / 20 * 1e3) < 1e-9 * max(1.0, d["ms_per_step"])
     assert abs(d["value"] - 2 * 4096 * 20 / slowest) < 1e-6 * d["value"]
+
+
+def test_plain_run_is_the_headline_and_dumps_the_checked_pcm(tmp_path):
+    """A plain run leaves out everything but the headline (cpu_baseline / end_to_end / other_configs null, the timed batch not
+    checked), and --dump-outputs writes the PCM of the last timed step.  W + K - 1 = 16 makes that step batch 0, the batch --full
+    checks against the oracle: the same command with --full dumps the same array and reports it bit-exact."""
+    flags = ("--gpus", "1", "--steps", "13", "--warmup", "4")
+    d = _bench(*flags, "--dump-outputs", str(tmp_path / "plain"))
+    f = _bench(*flags, "--full", "--no-end-to-end", "--no-other-configs", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "full"))
+    assert d["steps"] == 13 and d["warmup"] == 4 and d["cpu_baseline"] is None and d["end_to_end"] is None and d["other_configs"] is None
+    assert "bit-exact" not in d["config"]["parity"] and "bit-exact" in f["config"]["parity"]
+    for k in ("metric", "unit", "higher_is_better", "dtype"):
+        assert d[k] == f[k], k
+    assert abs(d["value"] - 4096 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    import numpy as np
+    a, b = np.load(tmp_path / "plain" / "pcm.npy"), np.load(tmp_path / "full" / "pcm.npy")
+    assert a.dtype == np.float32 and a.shape == (4096, 2048) and a.nbytes <= 64 << 20
+    assert np.array_equal(a, b) and np.array_equal(a, np.round(a)) and np.abs(a).max() > 0

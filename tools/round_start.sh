@@ -8,7 +8,7 @@ D=gpurun_out/$TAG
 mkdir -p $D
 timeout 900 python -m pytest tests -m gpu -x -q > $D/pytest.log 2>&1; echo "pytest rc=$?" >> $D/pytest.log
 timeout 120 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $D/smoke.log 2>&1
-timeout 300 python bench.py > $D/bench.json 2> $D/bench.err
+timeout 300 python bench.py --full > $D/bench.json 2> $D/bench.err
 for t in 16 32 64 128 0; do
   timeout 120 python tools/e2e.py --batches 48 --threads $t > $D/e2e_t$t.txt 2>&1
 done
