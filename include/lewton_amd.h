@@ -55,7 +55,8 @@ enum {
 enum {
 	LW_FMT_I16_PLANAR = 0,      /* Vec<Vec<i16>>: per packet [ch][m]          (samples.rs:20-40, :92-103) */
 	LW_FMT_I16_INTERLEAVED = 1, /* InterleavedSamples<i16>: per packet [m][ch] (samples.rs:48-78) */
-	LW_FMT_F32_PLANAR = 2       /* Vec<Vec<f32>>: per packet [ch][m]          (samples.rs:86-90; capi.rs:110) */
+	LW_FMT_F32_PLANAR = 2,      /* Vec<Vec<f32>>: per packet [ch][m]          (samples.rs:86-90; capi.rs:110) */
+	LW_FMT_F32_INTERLEAVED = 3  /* InterleavedSamples<f32>: per packet [m][ch] (samples.rs:48-78, :86-90) */
 };
 
 typedef struct lw_ident lw_ident;     /* IdentHeader incl. cached_bs_derived, src/header.rs:188-211 */

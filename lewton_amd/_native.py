@@ -205,7 +205,18 @@ HDR_BAD_TYPE, HDR_IS_AUDIO, HDR_UTF8, HDR_BUFFER_NOT_ADDRESSABLE = 20, 21, 22, 2
 ERR_NULL_ARG, ERR_DEVICE, ERR_CAPACITY, ERR_STATE_MISMATCH, ERR_UNSUPPORTED = 32, 33, 34, 35, 36
 OGG_EOF, OGG_NO_CAPTURE_PATTERN, OGG_INVALID_STREAM_STRUCT_VER, OGG_HASH_MISMATCH = 48, 49, 50, 51
 OGG_READ_ERROR, OGG_INVALID_DATA = 52, 53
-FMT_I16_PLANAR, FMT_I16_INTERLEAVED, FMT_F32_PLANAR = 0, 1, 2
+FMT_I16_PLANAR, FMT_I16_INTERLEAVED, FMT_F32_PLANAR, FMT_F32_INTERLEAVED = 0, 1, 2, 3
+
+
+def fmt_dtype(fmt):
+    """numpy element type of a sample format."""
+    import numpy as np
+    return np.float32 if fmt in (FMT_F32_PLANAR, FMT_F32_INTERLEAVED) else np.int16
+
+
+def fmt_interleaved(fmt):
+    """True for the formats laid out per packet as [m][ch] (InterleavedSamples<S>), False for [ch][m]."""
+    return fmt in (FMT_I16_INTERLEAVED, FMT_F32_INTERLEAVED)
 TAP_RESIDUE_PRE_INVERSE, TAP_RESIDUE_POST_INVERSE, TAP_PRE_MDCT, TAP_POST_MDCT = 0, 1, 2, 3
 
 

@@ -125,11 +125,13 @@ def get_decoded_sample_count(ident, setup, packet):
     return n.value
 
 
-_FMT = {"i16": N.FMT_I16_PLANAR, "i16_interleaved": N.FMT_I16_INTERLEAVED, "f32": N.FMT_F32_PLANAR}
+_FMT = {"i16": N.FMT_I16_PLANAR, "i16_interleaved": N.FMT_I16_INTERLEAVED, "f32": N.FMT_F32_PLANAR,
+        "f32_interleaved": N.FMT_F32_INTERLEAVED}
 
 
 def read_audio_packet_generic(ident, setup, packet, pwr, samples="i16", device=0):
-    """`samples`: 'i16' (Vec<Vec<i16>>), 'i16_interleaved' (InterleavedSamples<i16>), 'f32' (Vec<Vec<f32>>)."""
+    """`samples`: 'i16' (Vec<Vec<i16>>), 'i16_interleaved' (InterleavedSamples<i16>), 'f32' (Vec<Vec<f32>>),
+    'f32_interleaved' (InterleavedSamples<f32>).  Interleaved formats come back flat ([m * ch]), planar ones as [ch][m]."""
     return read_audio_packet_on(decoder_for(ident, setup, device), packet, pwr, samples)
 
 
@@ -140,13 +142,13 @@ def read_audio_packet_on(dec, packet, pwr, samples="i16"):
     ch = ident.audio_channels
     cap = (1 << ident.blocksize_1)
     fmt = _FMT[samples]
-    out = np.zeros(ch * cap, np.float32 if fmt == N.FMT_F32_PLANAR else np.int16)
+    out = np.zeros(ch * cap, N.fmt_dtype(fmt))
     m = C.c_size_t(0)
     pkt = bytes(packet)
     rc = N.lw_read_audio_packet(dec._h, pkt, len(pkt), h, fmt, out.ctypes.data_as(C.c_void_p), cap, C.byref(m))
     if rc:
         raise AudioReadError(rc)
-    if fmt == N.FMT_I16_INTERLEAVED:
+    if N.fmt_interleaved(fmt):
         return out[: ch * m.value].copy()
     return out[: ch * m.value].reshape(ch, m.value).copy()
 

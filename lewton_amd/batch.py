@@ -122,7 +122,7 @@ class Batch:
 
     def synth_to_host(self, stream=None):
         n = self.out_elems
-        out = np.zeros(max(n, 1), np.float32 if self.fmt == N.FMT_F32_PLANAR else np.int16)
+        out = np.zeros(max(n, 1), N.fmt_dtype(self.fmt))
         rc = N.lw_batch_synth_to_host(self._h, out.ctypes.data_as(C.c_void_p), n, stream)
         if rc:
             raise RuntimeError("lw_batch_synth_to_host: %d %s" % (rc, N.device_error()))
@@ -152,7 +152,7 @@ class Batch:
         for status, m, off in self.results():
             if status != 0:
                 out.append(None)
-            elif self.fmt == N.FMT_I16_INTERLEAVED:
+            elif N.fmt_interleaved(self.fmt):
                 out.append(flat[off: off + m * channels])
             else:
                 out.append(flat[off: off + m * channels].reshape(channels, m))

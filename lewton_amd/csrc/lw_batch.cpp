@@ -28,7 +28,7 @@ lw_batch *lw_batch_create(lw_decoder *d, size_t max_packets, int fmt, int *err)
 	if (!err)
 		err = &dummy;
 	*err = LW_OK;
-	if (!d || max_packets == 0 || fmt < 0 || fmt > 2) {
+	if (!d || max_packets == 0 || !lw_fmt_valid(fmt)) {
 		*err = LW_ERR_NULL_ARG;
 		return nullptr;
 	}
@@ -1145,6 +1145,7 @@ static int batch_launch(lw_batch *b, void *d_out, hipStream_t st, bool all_gener
 				L.pre[i] = d->fast.pre[i];
 		}
 	}
+	const int kfmt = lw_kernel_fmt(b->fmt, d->T.ch); // (the launchers' own format tags)
 	auto short_launch = [&](int cls) {
 		const LwShortPlan &bp = d->blkp[cls];
 		LwShortLaunch S{};
@@ -1168,7 +1169,7 @@ static int batch_launch(lw_batch *b, void *d_out, hipStream_t st, bool all_gener
 		const LwShortLaunch S = short_launch(0);
 		if (lw_mix_applicable(L, S, d->n_cus)) {
 			uint32_t *flags = (uint32_t *)(b->d_edge + b->max_packets * 2 * d->T.ch * lw_edge_values(d));
-			HIP_TRY(lw_launch_mix(d->T, Bc[1], L, S, flags, b->d_err, break_spin, break_spin != 0, d_out, b->fmt, st));
+			HIP_TRY(lw_launch_mix(d->T, Bc[1], L, S, flags, b->d_err, break_spin, break_spin != 0, d_out, kfmt, st));
 			b->last_kernels += b->n_halo_items ? "k_long<halo>,k_mix," : "k_mix,";
 			mixed = true;
 		}
@@ -1177,7 +1178,7 @@ static int batch_launch(lw_batch *b, void *d_out, hipStream_t st, bool all_gener
 		const LwShortLaunch S = short_launch(0);
 		if (lw_mix10_applicable(L, S, d->n_cus)) { // a mixed batch the chip holds at once: long and short blocks in ONE launch (k_mix10)
 			uint32_t *flags = (uint32_t *)(b->d_edge + b->max_packets * 2 * d->T.ch * lw_edge_values(d));
-			HIP_TRY(lw_launch_mix10(d->T, Bc[1], L, S, flags, b->d_err, break_spin, break_spin != 0, d_out, b->fmt, st));
+			HIP_TRY(lw_launch_mix10(d->T, Bc[1], L, S, flags, b->d_err, break_spin, break_spin != 0, d_out, kfmt, st));
 			b->last_kernels += b->n_halo_items ? "k_long10<halo>,k_mix10," : "k_mix10,";
 			mixed = true;
 		}
@@ -1185,13 +1186,13 @@ static int batch_launch(lw_batch *b, void *d_out, hipStream_t st, bool all_gener
 	if (run_fast && b->use_l10 && mixed) {
 		// (done above)
 	} else if (run_fast && b->use_l10) {
-		HIP_TRY(lw_launch_long10(d->T, Bc[fast_cls], L, d_out, b->fmt, st));
+		HIP_TRY(lw_launch_long10(d->T, Bc[fast_cls], L, d_out, kfmt, st));
 		b->last_kernels += b->n_halo_items ? "k_long10<halo>,k_long10," : "k_long10,";
 	} else if (run_fast && b->use_l12) {
-		HIP_TRY(lw_launch_long12(d->T, Bc[1], L, d_out, b->fmt, st));
+		HIP_TRY(lw_launch_long12(d->T, Bc[1], L, d_out, kfmt, st));
 		b->last_kernels += b->n_halo_items ? "k_long12<halo>,k_long12," : "k_long12,";
 	} else if (run_fast && !mixed) {
-		HIP_TRY(lw_launch_long(d->T, Bc[1], L, d_out, b->fmt, st));
+		HIP_TRY(lw_launch_long(d->T, Bc[1], L, d_out, kfmt, st));
 		b->last_kernels += b->n_halo_items ? "k_long<halo>,k_long," : "k_long,";
 	}
 	if (run_short && !mixed)
@@ -1200,15 +1201,15 @@ static int batch_launch(lw_batch *b, void *d_out, hipStream_t st, bool all_gener
 				continue;
 			const LwShortLaunch S = short_launch(cls);
 			if (S.lanes > 64) {
-				HIP_TRY(lw_launch_big(d->T, Bc[cls], S, d_out, b->fmt, st));
+				HIP_TRY(lw_launch_big(d->T, Bc[cls], S, d_out, kfmt, st));
 				b->last_kernels += "k_big,";
 			} else {
-				HIP_TRY(lw_launch_short(d->T, Bc[cls], S, d_out, b->fmt, st));
+				HIP_TRY(lw_launch_short(d->T, Bc[cls], S, d_out, kfmt, st));
 				b->last_kernels += "k_short,";
 			}
 		}
 	if (run_generic) {
-		lw_launch_generic_ola(d->T, B, d_out, b->fmt, st, all_generic);
+		lw_launch_generic_ola(d->T, B, d_out, kfmt, st, all_generic);
 		b->last_kernels += "k_ola_generic,";
 	}
 	if (!b->last_kernels.empty())

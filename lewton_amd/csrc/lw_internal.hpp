@@ -9,6 +9,7 @@
 #include "lw_fast.hpp"
 #include "lw_host.hpp"
 #include "lw_dev_entropy.h"
+#include "lw_formats.hpp"
 #include "lw_kernels.hpp"
 
 #include <memory>
@@ -175,9 +176,17 @@ struct lw_batch {
 };
 
 
-inline size_t lw_elem_size(int fmt)
+// public format -> the launchers' kernel-internal one (LwOutFmt, lw_kernels.hpp).  A mono stream's interleaved f32 samples
+// are byte for byte its planar ones, so it runs the f32-planar kernels.
+inline int lw_kernel_fmt(int fmt, uint32_t ch)
 {
-	return fmt == LW_FMT_F32_PLANAR ? 4 : 2;
+	switch (fmt) {
+	case LW_FMT_I16_PLANAR: return LW_OUT_I16_PLANAR;
+	case LW_FMT_I16_INTERLEAVED: return LW_OUT_I16_INTERLEAVED;
+	case LW_FMT_F32_PLANAR: return LW_OUT_F32_PLANAR;
+	case LW_FMT_F32_INTERLEAVED: return ch == 1 ? LW_OUT_F32_PLANAR : LW_OUT_F32_INTERLEAVED;
+	}
+	return -1;
 }
 int lw_decoder_set_device(const lw_decoder *d);
 // grow the state pool to at least `slots` (caller holds d->mu)

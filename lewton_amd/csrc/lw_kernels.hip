@@ -808,7 +808,7 @@ __global__ void __launch_bounds__(LW_BLOCK) k_ola_generic(LwDevTables T, LwBatch
 			const uint32_t prev_stride = o.prev_stride;
 			// four samples per thread and step (16-byte loads, one 8- or 16-byte store) when everything is a multiple of four
 			// -- it always is for block sizes >= 64; the long blocks next to short ones move 40 KB each through here
-			const bool quads = FMT != LW_OUT_I16_INTERLEAVED && ((ls | m | plen | n | prev_stride | o.prev_off | o.cur_off | o.out_off) & 3u) == 0 &&
+			const bool quads = !lw_out_itl(FMT) && ((ls | m | plen | n | prev_stride | o.prev_off | o.cur_off | o.out_off) & 3u) == 0 &&
 				((uintptr_t)out_v & 15u) == 0;
 			if (quads) {
 				const uint32_t mq = m >> 2;
@@ -841,6 +841,8 @@ __global__ void __launch_bounds__(LW_BLOCK) k_ola_generic(LwDevTables T, LwBatch
 					((int16_t *)out_v)[o.out_off + c * m + i] = to_i16(x);
 				else if (FMT == LW_OUT_I16_INTERLEAVED)
 					((int16_t *)out_v)[o.out_off + i * T.ch + c] = to_i16(x);
+				else if (FMT == LW_OUT_F32_INTERLEAVED)
+					((float *)out_v)[o.out_off + i * T.ch + c] = x;
 				else
 					((float *)out_v)[o.out_off + c * m + i] = x;
 			}
@@ -902,6 +904,8 @@ __global__ void __launch_bounds__(LW_BLOCK) k_ola_generic(LwDevTables T, LwBatch
 				((int16_t *)out_v)[rec.out_off + c * m + i] = to_i16(x);
 			else if (FMT == LW_OUT_I16_INTERLEAVED)
 				((int16_t *)out_v)[rec.out_off + i * T.ch + c] = to_i16(x);
+			else if (FMT == LW_OUT_F32_INTERLEAVED)
+				((float *)out_v)[rec.out_off + i * T.ch + c] = x;
 			else
 				((float *)out_v)[rec.out_off + c * m + i] = x;
 		}
@@ -972,6 +976,8 @@ void lw_launch_generic_ola(const LwDevTables &T, const LwBatchDev &B, void *out,
 		hipLaunchKernelGGL(k_ola_generic<LW_OUT_I16_PLANAR>, g, b, 0, st, T, B, out, skip_mask);
 	else if (fmt == LW_OUT_I16_INTERLEAVED)
 		hipLaunchKernelGGL(k_ola_generic<LW_OUT_I16_INTERLEAVED>, g, b, 0, st, T, B, out, skip_mask);
-	else
+	else if (fmt == LW_OUT_F32_INTERLEAVED)
+		hipLaunchKernelGGL(k_ola_generic<LW_OUT_F32_INTERLEAVED>, g, b, 0, st, T, B, out, skip_mask);
+	else if (fmt == LW_OUT_F32_PLANAR)
 		hipLaunchKernelGGL(k_ola_generic<LW_OUT_F32_PLANAR>, g, b, 0, st, T, B, out, skip_mask);
 }

@@ -75,7 +75,21 @@ struct LwDevTables {
 // a 256-thread workgroup (host: lw_runtime.cpp builds one task list per class)
 #define LW_SMALL_BS 9
 
-enum LwOutFmt { LW_OUT_I16_PLANAR = 0, LW_OUT_I16_INTERLEAVED = 1, LW_OUT_F32_PLANAR = 2 };
+// Kernel-internal sample formats (the `fmt` argument of the launchers; the host maps the public LW_FMT_* onto them,
+// lw_kernel_fmt in lw_internal.hpp).  3 is LW_OUT_I16_ITL_STEREO and 5 LW_OUT_F32_ITL_STEREO, the stereo unit forms that
+// only k_long's launcher chooses (lw_kernels_long.hip).
+enum LwOutFmt { LW_OUT_I16_PLANAR = 0, LW_OUT_I16_INTERLEAVED = 1, LW_OUT_F32_PLANAR = 2, LW_OUT_F32_INTERLEAVED = 4 };
+#define LW_OUT_F32_ITL_STEREO 5
+
+// f32 samples (no conversion), and the generic interleaved stores (element i of channel c at i * ch + c)
+__host__ __device__ constexpr bool lw_out_f32(int f)
+{
+	return f == LW_OUT_F32_PLANAR || f == LW_OUT_F32_INTERLEAVED || f == LW_OUT_F32_ITL_STEREO;
+}
+__host__ __device__ constexpr bool lw_out_itl(int f)
+{
+	return f == LW_OUT_I16_INTERLEAVED || f == LW_OUT_F32_INTERLEAVED;
+}
 
 struct LwBatchDev {
 	const LwPacketRec *recs;

@@ -211,6 +211,10 @@ __device__ __forceinline__ void store_pair(void *out, uint32_t elem0, uint32_t p
 {
 	if (FMT == LW_OUT_F32_PLANAR) {
 		*reinterpret_cast<float2_t *>(reinterpret_cast<float *>(out) + elem0 + pos) = float2_t{a, b};
+	} else if (FMT == LW_OUT_F32_INTERLEAVED) {
+		float *o = reinterpret_cast<float *>(out) + elem0;
+		o[pos * stride] = a;
+		o[(pos + 1u) * stride] = b;
 	} else {
 		// samples.rs:92-103: x * 32768, truncate toward zero (v_cvt_i32_f32: saturating, NaN -> 0), clamp to i16 by the saturating
 		// pack (clamping the integer = clamping the float first: the bounds are integers)
@@ -504,8 +508,8 @@ __global__ void __launch_bounds__(1 << (BS - 5)) __attribute__((amdgpu_waves_per
 			// ---- E: bit-reverse gather (imdct.rs:490-528), step 7 (:533-580), step 8 (:589-658), window / overlap-add, stores
 			if (work) {
 				const bool samples = cur.kind == LW_SS_BLOCK && cur.prev_kind != LW_SP_NONE;
-				const uint32_t elem0 = FMT == LW_OUT_I16_INTERLEAVED ? cur.out_off + chn[c] : cur.out_off + chn[c] * n2;
-				const uint32_t stride = FMT == LW_OUT_I16_INTERLEAVED ? F.ch : 1u;
+				const uint32_t elem0 = lw_out_itl(FMT) ? cur.out_off + chn[c] : cur.out_off + chn[c] * n2;
+				const uint32_t stride = lw_out_itl(FMT) ? F.ch : 1u;
 				float *st_dst = (cur.kind == LW_SS_BLOCK && cur.state_out >= 0)
 					? F.state + ((size_t)cur.state_out * 2u + ((cur.flags & LW_RF_PARITY_OUT) ? 1u : 0u)) * F.state_stride + chn[c] * F.state_chan_stride
 					: nullptr;
@@ -600,6 +604,10 @@ static hipError_t launch_big(const LwBigArgs &F, int fmt, hipStream_t st)
 		return lw_launch_k(k_big<LW_OUT_I16_PLANAR, BS>, g, b, 0, st, A);
 	if (fmt == LW_OUT_I16_INTERLEAVED)
 		return lw_launch_k(k_big<LW_OUT_I16_INTERLEAVED, BS>, g, b, 0, st, A);
+	if (fmt == LW_OUT_F32_INTERLEAVED)
+		return lw_launch_k(k_big<LW_OUT_F32_INTERLEAVED, BS>, g, b, 0, st, A);
+	if (fmt != LW_OUT_F32_PLANAR)
+		return hipErrorInvalidValue;
 	return lw_launch_k(k_big<LW_OUT_F32_PLANAR, BS>, g, b, 0, st, A);
 }
 

@@ -1172,6 +1172,12 @@ __device__ __forceinline__ void store16_wt(void *p, float4_t v)
 // kernel-internal output format: LW_OUT_I16_INTERLEAVED of a 2-channel stream whose channels form ONE unit (a coupled pair)
 #define LW_OUT_I16_ITL_STEREO 3
 
+// the generic format of a stereo unit form (the kernel variants without one: PRE, SPLIT, EDGE)
+constexpr int lw_out_unit_free(int f)
+{
+	return f == LW_OUT_I16_ITL_STEREO ? LW_OUT_I16_INTERLEAVED : f == LW_OUT_F32_ITL_STEREO ? LW_OUT_F32_INTERLEAVED : f;
+}
+
 // ---- interleaved stereo (InterleavedSamples<i16>, samples.rs:48-78; `read_dec_packet_itl`): one channel's window +
 //      overlap-add + conversion, packed two samples per dword: D[g][h] = positions (p_g + 2h, p_g + 2h + 1), with
 //      p_0 = 4l, p_1 = 508 - 4l, p_2 = 512 + 4l, p_3 = 1020 - 4l
@@ -1218,6 +1224,52 @@ __device__ __forceinline__ void store_interleaved2(const LwFastArgs &F, uint32_t
 	}
 }
 
+// kernel-internal output format LW_OUT_F32_ITL_STEREO (lw_kernels.hpp): LW_OUT_F32_INTERLEAVED of a 2-channel stream whose
+// channels form ONE unit.  ---- interleaved stereo f32 (InterleavedSamples<f32>, samples.rs:48-78, :86-90): one channel's window +
+// overlap-add, V[g] = its samples at positions p_g .. p_g + 3 (p_g as in ola_pack_i16)
+__device__ __forceinline__ void ola_quads_f32(const char *img, uint32_t lane, const float2_t (&Rc)[2][4], const PrevHalf &h, float4_t (&V)[4])
+{
+	float2_t O[2][4];
+#pragma unroll
+	for (int c2 = 0; c2 < 2; c2++) {
+		const float4_t w0 = lds4(img + LWI_WIN, 32u * (64u * c2 + lane));
+		const float4_t w1 = lds4(img + LWI_WIN, 32u * (64u * c2 + lane) + 16u);
+		ola_block<false>(Rc[c2], h.pp[c2][0], h.pp[c2][1], w0, w1, O[c2]);
+	}
+	V[0] = float4_t{O[0][3].x, O[0][2].x, O[1][3].x, O[1][2].x};
+	V[1] = float4_t{O[1][1].x, O[1][0].x, O[0][1].x, O[0][0].x};
+	V[2] = float4_t{O[0][0].y, O[0][1].y, O[1][0].y, O[1][1].y};
+	V[3] = float4_t{O[1][2].y, O[1][3].y, O[0][2].y, O[0][3].y};
+}
+
+// (L, R) frames of four consecutive positions = 32 contiguous bytes per lane and group.  Stored as they lie, every 16-byte store
+// would cover every other 16 bytes of 2 KB: half-written lines, which the write-through turns into partial HBM writes (1.8x the
+// planar store time).  So the frames go to the lanes that store them first (ds_bpermute, no LDS memory): per group two 16-byte
+// stores, each writing 1 KB of consecutive frames -- lane l the frames of positions b + 2l, b + 2l + 1 (first store) and
+// b + 128 + 2l, +1 (second), b = the group's first position; 8 stores in all, the stores and bytes of the planar form
+__device__ __forceinline__ void store_interleaved2_f32(const LwFastArgs &F, uint32_t lane, uint32_t out_off, const float4_t (&L)[4],
+		const float4_t (&R)[4])
+{
+	float *o = reinterpret_cast<float *>(F.out) + out_off;
+	const bool odd = (lane & 1u) != 0; // this lane stores the second two of the source lane's four frames
+#pragma unroll
+	for (int g = 0; g < 4; g++) {
+		// groups 0 / 2 ascend with the lane (positions b + 4 l ..), 1 / 3 descend (b + 252 - 4 l ..)
+		const uint32_t b = 256u * (uint32_t)g;
+#pragma unroll
+		for (int h = 0; h < 2; h++) {
+			const uint32_t k = 32u * (uint32_t)h + (lane >> 1);           // the frames' 4-position slot in the group
+			const int src = (int)((g & 1) ? 63u - k : k) << 2;            // the lane that holds it (byte address)
+#define LW_BP(v) __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(v)))
+			const float lx = LW_BP(L[g].x), ly = LW_BP(L[g].y), lz = LW_BP(L[g].z), lw = LW_BP(L[g].w);
+			const float rx = LW_BP(R[g].x), ry = LW_BP(R[g].y), rz = LW_BP(R[g].z), rw = LW_BP(R[g].w);
+#undef LW_BP
+			const float4_t v = odd ? float4_t{lz, rz, lw, rw} : float4_t{lx, rx, ly, ry};
+			store16_wt(o + 2u * (b + 128u * (uint32_t)h + 2u * lane), v);
+		}
+	}
+}
+
 // ---- window + overlap-add (audio.rs:1116-1118), sample conversion (samples.rs:92-103), stores of one channel
 // (mch = samples per channel of the packet's output block: 1024 unless the block has a short right slope, EDGE kernels)
 template <int FMT>
@@ -1230,7 +1282,7 @@ __device__ __forceinline__ void ola_store(const LwFastArgs &F, const char *img, 
 	for (int c2 = 0; c2 < 2; c2++) {
 		const float4_t w0 = lds4(img + LWI_WIN, 32u * (64u * c2 + lane));
 		const float4_t w1 = lds4(img + LWI_WIN, 32u * (64u * c2 + lane) + 16u);
-		ola_block<FMT != LW_OUT_F32_PLANAR>(Rc[c2], h.pp[c2][0], h.pp[c2][1], w0, w1, O[c2]);
+		ola_block<!lw_out_f32(FMT)>(Rc[c2], h.pp[c2][0], h.pp[c2][1], w0, w1, O[c2]);
 	}
 	// positions: [4l..4l+3] = .x of (0,3) (0,2) (1,3) (1,2); [508-4l..] = .x of (1,1) (1,0) (0,1) (0,0)
 	//            [512+4l..] = .y of (0,0) (0,1) (1,0) (1,1); [1020-4l..] = .y of (1,2) (1,3) (0,2) (0,3)
@@ -1241,6 +1293,22 @@ __device__ __forceinline__ void ola_store(const LwFastArgs &F, const char *img, 
 		store16_wt(o + p1, float4_t{O[1][1].x, O[1][0].x, O[0][1].x, O[0][0].x});
 		store16_wt(o + p2, float4_t{O[0][0].y, O[0][1].y, O[1][0].y, O[1][1].y});
 		store16_wt(o + p3, float4_t{O[1][2].y, O[1][3].y, O[0][2].y, O[0][3].y});
+	} else if (FMT == LW_OUT_F32_INTERLEAVED) {
+		// any channel count: 4-byte stores at stride ch (the stereo unit form never gets here, see store_interleaved2_f32)
+		float *o = reinterpret_cast<float *>(F.out) + out_off + (uint32_t)chn;
+		const uint32_t pos[4] = {p0, p1, p2, p3};
+		const float v[4][4] = {{O[0][3].x, O[0][2].x, O[1][3].x, O[1][2].x}, {O[1][1].x, O[1][0].x, O[0][1].x, O[0][0].x},
+			{O[0][0].y, O[0][1].y, O[1][0].y, O[1][1].y}, {O[1][2].y, O[1][3].y, O[0][2].y, O[0][3].y}};
+#pragma unroll
+		for (int g = 0; g < 4; g++) {
+			uint32_t off = pos[g] * F.ch; // one running offset per group keeps the address registers few
+			asm volatile("" : "+v"(off));
+#pragma unroll
+			for (int k = 0; k < 4; k++) {
+				o[off] = v[g][k];
+				off += F.ch;
+			}
+		}
 	} else {
 		// samples.rs:92-103: x*32768, truncate toward zero (v_cvt_i32_f32: saturating, NaN -> 0), clamp to
 		// i16 by the saturating pack v_cvt_pk_i16_i32 -- equal to the reference's compare/clamp/`as i16`
@@ -1331,6 +1399,14 @@ __device__ __forceinline__ void store_quad(const LwFastArgs &F, int chn, uint32_
 		return;
 	if (FMT == LW_OUT_F32_PLANAR) {
 		store16_wt(reinterpret_cast<float *>(F.out) + out_off + (uint32_t)chn * mch + rel, v);
+		return;
+	}
+	if (FMT == LW_OUT_F32_INTERLEAVED) {
+		float *o = reinterpret_cast<float *>(F.out) + out_off + rel * F.ch + (uint32_t)chn;
+		o[0] = v.x;
+		o[F.ch] = v.y;
+		o[2u * F.ch] = v.z;
+		o[3u * F.ch] = v.w;
 		return;
 	}
 	typedef short short2_t __attribute__((ext_vector_type(2)));
@@ -1723,7 +1799,7 @@ __device__ __forceinline__ void short_ola_store(const char *img, uint32_t l, voi
 	for (int c2 = 0; c2 < 2; c2++) {
 		const float4_t w0 = lds4(img + LwBlkLayout<L>::WIN, 32u * (L * c2 + l));
 		const float4_t w1 = lds4(img + LwBlkLayout<L>::WIN, 32u * (L * c2 + l) + 16u);
-		ola_block<FMT != LW_OUT_F32_PLANAR>(Rc[c2], h.pp[c2][0], h.pp[c2][1], w0, w1, O[c2]);
+		ola_block<!lw_out_f32(FMT)>(Rc[c2], h.pp[c2][0], h.pp[c2][1], w0, w1, O[c2]);
 	}
 	// positions: [4l..4l+3] = .x of (0,3) (0,2) (1,3) (1,2); [8L-4-4l..] = .x of (1,1) (1,0) (0,1) (0,0)
 	//            [8L+4l..] = .y of (0,0) (0,1) (1,0) (1,1); [16L-4-4l..] = .y of (1,2) (1,3) (0,2) (0,3)
@@ -1734,6 +1810,13 @@ __device__ __forceinline__ void short_ola_store(const char *img, uint32_t l, voi
 	for (int q = 0; q < 4; q++) {
 		if (FMT == LW_OUT_F32_PLANAR) {
 			store16_wt(reinterpret_cast<float *>(out) + elem0 + pos[q], float4_t{v[q][0], v[q][1], v[q][2], v[q][3]});
+		} else if (FMT == LW_OUT_F32_INTERLEAVED) {
+			float *o = reinterpret_cast<float *>(out) + elem0;
+			const uint32_t off = pos[q] * stride;
+			o[off] = v[q][0];
+			o[off + stride] = v[q][1];
+			o[off + 2u * stride] = v[q][2];
+			o[off + 3u * stride] = v[q][3];
 		} else {
 			// samples.rs:92-103: x * 32768 (done in ola_block), truncate toward zero (v_cvt_i32_f32: saturating, NaN -> 0), clamp
 			// to i16 by the saturating pack
@@ -1901,6 +1984,10 @@ static hipError_t launch_short(LwShortArgs &F, int fmt, hipStream_t st)
 		return lw_launch_k(k_short<LW_OUT_I16_PLANAR, L>, grid, block, 0, st, F);
 	if (fmt == LW_OUT_I16_INTERLEAVED)
 		return lw_launch_k(k_short<LW_OUT_I16_INTERLEAVED, L>, grid, block, 0, st, F);
+	if (fmt == LW_OUT_F32_INTERLEAVED)
+		return lw_launch_k(k_short<LW_OUT_F32_INTERLEAVED, L>, grid, block, 0, st, F);
+	if (fmt != LW_OUT_F32_PLANAR)
+		return hipErrorInvalidValue;
 	return lw_launch_k(k_short<LW_OUT_F32_PLANAR, L>, grid, block, 0, st, F);
 }
 
@@ -2001,7 +2088,15 @@ static hipError_t long_prepare(const LwDevTables &T, const LwBatchDev &B, const 
 			(const void *)k_long<LW_OUT_I16_PLANAR, false, true, false, false, true>, (const void *)k_long<LW_OUT_I16_INTERLEAVED, false, true, false, false, true>,
 			(const void *)k_long<LW_OUT_F32_PLANAR, false, true, false, false, true>,
 			(const void *)k_long<LW_OUT_I16_PLANAR, false, false, true, false, true>, (const void *)k_long<LW_OUT_I16_INTERLEAVED, false, false, true, false, true>,
-			(const void *)k_long<LW_OUT_F32_PLANAR, false, false, true, false, true>};
+			(const void *)k_long<LW_OUT_F32_PLANAR, false, false, true, false, true>,
+			// f32 interleaved: the stereo unit form (plain, TD) and the generic one in every form
+			(const void *)k_long<LW_OUT_F32_ITL_STEREO, false>, (const void *)k_long<LW_OUT_F32_ITL_STEREO, false, true>,
+			(const void *)k_long<LW_OUT_F32_INTERLEAVED, false>, (const void *)k_long<LW_OUT_F32_INTERLEAVED, false, true>,
+			(const void *)k_long<LW_OUT_F32_INTERLEAVED, false, false, true>, (const void *)k_long<LW_OUT_F32_INTERLEAVED, false, false, false, true>,
+			(const void *)k_long<LW_OUT_F32_INTERLEAVED, false, false, true, true>,
+			(const void *)k_long<LW_OUT_F32_INTERLEAVED, false, false, false, false, true>,
+			(const void *)k_long<LW_OUT_F32_INTERLEAVED, false, true, false, false, true>,
+			(const void *)k_long<LW_OUT_F32_INTERLEAVED, false, false, true, false, true>, (const void *)k_mix<LW_OUT_F32_INTERLEAVED>};
 		for (const void *f : fns) {
 			const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 			if (e != hipSuccess)
@@ -2050,7 +2145,7 @@ hipError_t lw_launch_long(const LwDevTables &T, const LwBatchDev &B, const LwFas
 #define LW_LAUNCH_MAIN(F_)                                                                                     \
 	do {                                                                                                      \
 		if (L.pre_on) { /* coupling steps inside the waves (never with split units, never the stereo frame stores) */ \
-			constexpr int FP = F_ == LW_OUT_I16_ITL_STEREO ? LW_OUT_I16_INTERLEAVED : F_;                      \
+			constexpr int FP = lw_out_unit_free(F_);                                                           \
 			if (L.edge_mode)                                                                                  \
 				return lw_launch_k(k_long<FP, false, false, true, false, true>, dim3(grid), dim3(LW_WG), lds, st, F); \
 			if (L.has_tdonly)                                                                                 \
@@ -2059,13 +2154,13 @@ hipError_t lw_launch_long(const LwDevTables &T, const LwBatchDev &B, const LwFas
 		}                                                                                                     \
 		if (L.split && !L.has_tdonly) { /* sparse launch: one channel per wave (generic interleaved stores: a wave has one channel) */ \
 			if (L.edge_mode)                                                                                  \
-				return lw_launch_k(k_long<F_ == LW_OUT_I16_ITL_STEREO ? LW_OUT_I16_INTERLEAVED : F_, false, false, true, true>,  \
+				return lw_launch_k(k_long<lw_out_unit_free(F_), false, false, true, true>,                     \
 						dim3(grid), dim3(LW_WG), lds, st, F);                                                  \
-			return lw_launch_k(k_long<F_ == LW_OUT_I16_ITL_STEREO ? LW_OUT_I16_INTERLEAVED : F_, false, false, false, true>, \
+			return lw_launch_k(k_long<lw_out_unit_free(F_), false, false, false, true>,                        \
 					dim3(grid), dim3(LW_WG), lds, st, F);                                                      \
 		}                                                                                                     \
 		if (L.edge_mode)                                                                                      \
-			return lw_launch_k(k_long<F_ == LW_OUT_I16_ITL_STEREO ? LW_OUT_I16_INTERLEAVED : F_, false, false, true>, dim3(grid), \
+			return lw_launch_k(k_long<lw_out_unit_free(F_), false, false, true>, dim3(grid),                   \
 					dim3(LW_WG), lds, st, F);                                                                  \
 		if (L.has_tdonly)                                                                                     \
 			return lw_launch_k(k_long<F_, false, true>, dim3(grid), dim3(LW_WG), lds, st, F);                  \
@@ -2077,8 +2172,14 @@ hipError_t lw_launch_long(const LwDevTables &T, const LwBatchDev &B, const LwFas
 			LW_LAUNCH_MAIN(LW_OUT_I16_ITL_STEREO);
 		else if (fmt == LW_OUT_I16_INTERLEAVED)
 			LW_LAUNCH_MAIN(LW_OUT_I16_INTERLEAVED);
-		else
+		else if (fmt == LW_OUT_F32_INTERLEAVED && F.ch == 2 && L.n_units == 1 && L.units[0].ch_b >= 0)
+			LW_LAUNCH_MAIN(LW_OUT_F32_ITL_STEREO);
+		else if (fmt == LW_OUT_F32_INTERLEAVED)
+			LW_LAUNCH_MAIN(LW_OUT_F32_INTERLEAVED);
+		else if (fmt == LW_OUT_F32_PLANAR)
 			LW_LAUNCH_MAIN(LW_OUT_F32_PLANAR);
+		else
+			return hipErrorInvalidValue;
 #undef LW_LAUNCH_MAIN
 	}
 	return hipSuccess;
@@ -2177,6 +2278,10 @@ hipError_t lw_launch_mix(const LwDevTables &T, const LwBatchDev &B, const LwFast
 		return launched(lw_launch_k(k_mix<LW_OUT_I16_PLANAR>, dim3(grid), dim3(LW_WG), lds, st, F, FS, M));
 	if (fmt == LW_OUT_I16_INTERLEAVED)
 		return launched(lw_launch_k(k_mix<LW_OUT_I16_INTERLEAVED>, dim3(grid), dim3(LW_WG), lds, st, F, FS, M));
+	if (fmt == LW_OUT_F32_INTERLEAVED)
+		return launched(lw_launch_k(k_mix<LW_OUT_F32_INTERLEAVED>, dim3(grid), dim3(LW_WG), lds, st, F, FS, M));
+	if (fmt != LW_OUT_F32_PLANAR)
+		return launched(hipErrorInvalidValue);
 	return launched(lw_launch_k(k_mix<LW_OUT_F32_PLANAR>, dim3(grid), dim3(LW_WG), lds, st, F, FS, M));
 }
 

@@ -332,6 +332,34 @@ __device__ __forceinline__ void ola_store_itl2_10(const char *img, uint32_t lane
 	}
 }
 
+// ---- the same for interleaved f32 (InterleavedSamples<f32>, samples.rs:48-78, :86-90): per group of four positions, two
+//      v_permlane32_swap bring both channels' samples of two positions -- +2, +3 to the lower half, +0, +1 to the upper -- to one
+//      lane, which stores the two (L, R) frames as 16 bytes: four 16-byte stores per lane, as for f32 planar
+__device__ __forceinline__ void ola_store_itl2_10_f32(const char *img, uint32_t lane, uint32_t l, void *out, uint32_t out_off,
+		bool first_is_ch0, const float2_t (&Rc)[2][4], const PrevHalf &h)
+{
+	float2_t O[2][4];
+#pragma unroll
+	for (int c2 = 0; c2 < 2; c2++) {
+		const float4_t w0 = lds4(img + Y10::WIN, 32u * (32u * c2 + l));
+		const float4_t w1 = lds4(img + Y10::WIN, 32u * (32u * c2 + l) + 16u);
+		ola_block<false>(Rc[c2], h.pp[c2][0], h.pp[c2][1], w0, w1, O[c2]);
+	}
+	const uint32_t pos[4] = {4u * l, 252u - 4u * l, 256u + 4u * l, 508u - 4u * l};
+	const float v[4][4] = {{O[0][3].x, O[0][2].x, O[1][3].x, O[1][2].x}, {O[1][1].x, O[1][0].x, O[0][1].x, O[0][0].x},
+		{O[0][0].y, O[0][1].y, O[1][0].y, O[1][1].y}, {O[1][2].y, O[1][3].y, O[0][2].y, O[0][3].y}};
+	float *o = reinterpret_cast<float *>(out) + out_off;
+	const uint32_t sub = lane >= 32u ? 0u : 2u; // which two of the group's four positions this lane stores
+#pragma unroll
+	for (int q = 0; q < 4; q++) {
+		// lanes 32-63 of (v2, v3) <-> lanes 0-31 of (v0, v1): afterwards X = the first channel's two samples, Y = the second's
+		auto r0 = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[q][2]), __float_as_uint(v[q][0]), false, false);
+		auto r1 = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[q][3]), __float_as_uint(v[q][1]), false, false);
+		const float x0 = __uint_as_float(r0[0]), x1 = __uint_as_float(r1[0]), y0 = __uint_as_float(r0[1]), y1 = __uint_as_float(r1[1]);
+		store16_wt(o + 2u * (pos[q] + sub), first_is_ch0 ? float4_t{x0, y0, x1, y1} : float4_t{y0, x0, y1, x1});
+	}
+}
+
 // raw halves at this lane's q positions (see Half8): lo = q in [4l, 4l+4), hi = q in [252 - 4l, 256 - 4l)
 #define L10_PB_LO(R_) float4_t{R_[0][3].y, R_[0][2].y, R_[1][3].y, R_[1][2].y}
 #define L10_PB_HI(R_) float4_t{R_[1][1].y, R_[1][0].y, R_[0][1].y, R_[0][0].y}
@@ -624,9 +652,11 @@ __device__ __forceinline__ void long10_body(const LwFastArgs &F, const LwShortAr
 					}
 					if (FMT == LW_OUT_I16_INTERLEAVED && two && F.ch == 2u) {
 						ola_store_itl2_10(img, lane, l, F.out, it.out_off, un.ch_a == 0, R, ph); // (both halves: a frame needs both channels)
+					} else if (FMT == LW_OUT_F32_INTERLEAVED && two && F.ch == 2u) {
+						ola_store_itl2_10_f32(img, lane, l, F.out, it.out_off, un.ch_a == 0, R, ph);
 					} else if (mine) {
-						const uint32_t e0 = FMT == LW_OUT_I16_INTERLEAVED ? it.out_off + chn : it.out_off + chn * e_m;
-						short_ola_store<FMT, 32>(img, l, F.out, e0, FMT == LW_OUT_I16_INTERLEAVED ? F.ch : 1u, R, ph);
+						const uint32_t e0 = lw_out_itl(FMT) ? it.out_off + chn : it.out_off + chn * e_m;
+						short_ola_store<FMT, 32>(img, l, F.out, e0, lw_out_itl(FMT) ? F.ch : 1u, R, ph);
 					}
 					if (it.src_kind == LW_SRC_LDS) {
 						asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -739,12 +769,20 @@ hipError_t lw_launch_long10(const LwDevTables &T, const LwBatchDev &B, const LwF
 			return lw_launch_k(k_long10<LW_OUT_I16_PLANAR, false, true>, grid, block, lds, st, F);
 		if (fmt == LW_OUT_I16_INTERLEAVED)
 			return lw_launch_k(k_long10<LW_OUT_I16_INTERLEAVED, false, true>, grid, block, lds, st, F);
+		if (fmt == LW_OUT_F32_INTERLEAVED)
+			return lw_launch_k(k_long10<LW_OUT_F32_INTERLEAVED, false, true>, grid, block, lds, st, F);
+		if (fmt != LW_OUT_F32_PLANAR)
+			return hipErrorInvalidValue;
 		return lw_launch_k(k_long10<LW_OUT_F32_PLANAR, false, true>, grid, block, lds, st, F);
 	}
 	if (fmt == LW_OUT_I16_PLANAR)
 		return lw_launch_k(k_long10<LW_OUT_I16_PLANAR, false>, grid, block, lds, st, F);
 	if (fmt == LW_OUT_I16_INTERLEAVED)
 		return lw_launch_k(k_long10<LW_OUT_I16_INTERLEAVED, false>, grid, block, lds, st, F);
+	if (fmt == LW_OUT_F32_INTERLEAVED)
+		return lw_launch_k(k_long10<LW_OUT_F32_INTERLEAVED, false>, grid, block, lds, st, F);
+	if (fmt != LW_OUT_F32_PLANAR)
+		return hipErrorInvalidValue;
 	return lw_launch_k(k_long10<LW_OUT_F32_PLANAR, false>, grid, block, lds, st, F);
 }
 
@@ -791,6 +829,10 @@ hipError_t lw_launch_mix10(const LwDevTables &T, const LwBatchDev &B, const LwFa
 			return order.end(lw_launch_k(k_mix10<LW_OUT_I16_PLANAR, L_>, grid, block, lds, st, F, FS, M), st);                         \
 		if (fmt == LW_OUT_I16_INTERLEAVED)                                                                                             \
 			return order.end(lw_launch_k(k_mix10<LW_OUT_I16_INTERLEAVED, L_>, grid, block, lds, st, F, FS, M), st);                    \
+		if (fmt == LW_OUT_F32_INTERLEAVED)                                                                                             \
+			return order.end(lw_launch_k(k_mix10<LW_OUT_F32_INTERLEAVED, L_>, grid, block, lds, st, F, FS, M), st);                    \
+		if (fmt != LW_OUT_F32_PLANAR)                                                                                                  \
+			return order.end(hipErrorInvalidValue, st);                                                                                \
 		return order.end(lw_launch_k(k_mix10<LW_OUT_F32_PLANAR, L_>, grid, block, lds, st, F, FS, M), st);                             \
 	} while (0)
 	if (LS.lanes == 8)
@@ -830,7 +872,9 @@ static hipError_t long10_prepare(const LwDevTables &T, const LwBatchDev &B, cons
 			(const void *)k_long10<LW_OUT_F32_PLANAR, false, true>, (const void *)k_mix10<LW_OUT_I16_PLANAR, 8>,
 			(const void *)k_mix10<LW_OUT_I16_INTERLEAVED, 8>, (const void *)k_mix10<LW_OUT_F32_PLANAR, 8>,
 			(const void *)k_mix10<LW_OUT_I16_PLANAR, 16>, (const void *)k_mix10<LW_OUT_I16_INTERLEAVED, 16>,
-			(const void *)k_mix10<LW_OUT_F32_PLANAR, 16>};
+			(const void *)k_mix10<LW_OUT_F32_PLANAR, 16>, (const void *)k_long10<LW_OUT_F32_INTERLEAVED, false>,
+			(const void *)k_long10<LW_OUT_F32_INTERLEAVED, false, true>, (const void *)k_mix10<LW_OUT_F32_INTERLEAVED, 8>,
+			(const void *)k_mix10<LW_OUT_F32_INTERLEAVED, 16>};
 		for (const void *f : fns) {
 			const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 			if (e != hipSuccess)

@@ -290,7 +290,7 @@ __device__ __forceinline__ void ola_store12(const LwFastArgs &F, const char *img
 		for (int c2 = 0; c2 < 2; c2++) {
 			const float4_t w0 = lds4(img + Y12::WIN, 32u * (64u * (2 * h + c2) + lane));
 			const float4_t w1 = lds4(img + Y12::WIN, 32u * (64u * (2 * h + c2) + lane) + 16u);
-			ola_block<FMT != LW_OUT_F32_PLANAR>(R[2 * h + c2], ph.pp[2 * h + c2][0], ph.pp[2 * h + c2][1], w0, w1, O[c2]);
+			ola_block<!lw_out_f32(FMT)>(R[2 * h + c2], ph.pp[2 * h + c2][0], ph.pp[2 * h + c2][1], w0, w1, O[c2]);
 		}
 		const uint32_t pos[4] = {256u * h + 4u * lane, 1020u - 256u * h - 4u * lane, 1024u + 256u * h + 4u * lane, 2044u - 256u * h - 4u * lane};
 		const float v[4][4] = {{O[0][3].x, O[0][2].x, O[1][3].x, O[1][2].x}, {O[1][1].x, O[1][0].x, O[0][1].x, O[0][0].x},
@@ -299,6 +299,13 @@ __device__ __forceinline__ void ola_store12(const LwFastArgs &F, const char *img
 		for (int g = 0; g < 4; g++) {
 			if (FMT == LW_OUT_F32_PLANAR) {
 				store16_wt(reinterpret_cast<float *>(F.out) + out_off + chn * mch + pos[g], float4_t{v[g][0], v[g][1], v[g][2], v[g][3]});
+			} else if (FMT == LW_OUT_F32_INTERLEAVED) {
+				float *o = reinterpret_cast<float *>(F.out) + out_off;
+				const uint32_t off = pos[g] * F.ch + chn;
+				o[off] = v[g][0];
+				o[off + F.ch] = v[g][1];
+				o[off + 2u * F.ch] = v[g][2];
+				o[off + 3u * F.ch] = v[g][3];
 			} else {
 				// samples.rs:92-103: x * 32768 (ola_block), truncate toward zero (v_cvt_i32_f32: saturating, NaN -> 0), clamp by the saturating pack
 				typedef short short2_t __attribute__((ext_vector_type(2)));
@@ -620,7 +627,8 @@ hipError_t lw_launch_long12(const LwDevTables &T, const LwBatchDev &B, const LwF
 		const void *fns[] = {(const void *)k_long12<LW_OUT_I16_PLANAR, false>, (const void *)k_long12<LW_OUT_I16_INTERLEAVED, false>,
 			(const void *)k_long12<LW_OUT_F32_PLANAR, false>, (const void *)k_long12<LW_OUT_I16_PLANAR, true>,
 			(const void *)k_long12<LW_OUT_I16_PLANAR, false, true>, (const void *)k_long12<LW_OUT_I16_INTERLEAVED, false, true>,
-			(const void *)k_long12<LW_OUT_F32_PLANAR, false, true>};
+			(const void *)k_long12<LW_OUT_F32_PLANAR, false, true>, (const void *)k_long12<LW_OUT_F32_INTERLEAVED, false>,
+			(const void *)k_long12<LW_OUT_F32_INTERLEAVED, false, true>};
 		for (const void *f : fns) {
 			const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 			if (e != hipSuccess)
@@ -654,11 +662,19 @@ hipError_t lw_launch_long12(const LwDevTables &T, const LwBatchDev &B, const LwF
 			return lw_launch_k(k_long12<LW_OUT_I16_PLANAR, false, true>, grid, block, lds, st, F);
 		if (fmt == LW_OUT_I16_INTERLEAVED)
 			return lw_launch_k(k_long12<LW_OUT_I16_INTERLEAVED, false, true>, grid, block, lds, st, F);
+		if (fmt == LW_OUT_F32_INTERLEAVED)
+			return lw_launch_k(k_long12<LW_OUT_F32_INTERLEAVED, false, true>, grid, block, lds, st, F);
+		if (fmt != LW_OUT_F32_PLANAR)
+			return hipErrorInvalidValue;
 		return lw_launch_k(k_long12<LW_OUT_F32_PLANAR, false, true>, grid, block, lds, st, F);
 	}
 	if (fmt == LW_OUT_I16_PLANAR)
 		return lw_launch_k(k_long12<LW_OUT_I16_PLANAR, false>, grid, block, lds, st, F);
 	if (fmt == LW_OUT_I16_INTERLEAVED)
 		return lw_launch_k(k_long12<LW_OUT_I16_INTERLEAVED, false>, grid, block, lds, st, F);
+	if (fmt == LW_OUT_F32_INTERLEAVED)
+		return lw_launch_k(k_long12<LW_OUT_F32_INTERLEAVED, false>, grid, block, lds, st, F);
+	if (fmt != LW_OUT_F32_PLANAR)
+		return hipErrorInvalidValue;
 	return lw_launch_k(k_long12<LW_OUT_F32_PLANAR, false>, grid, block, lds, st, F);
 }

@@ -281,6 +281,22 @@
 							store_interleaved2(F, lane, it.out_off, D[0], D[1]);
 						else
 							store_interleaved2(F, lane, it.out_off, D[1], D[0]);
+					} else if (FMT == LW_OUT_F32_ITL_STEREO) {
+						// the same for f32: a lane's four positions of both channels are 32 contiguous bytes
+						float4_t V[2][4];
+#pragma unroll
+						for (int c = 0; c < 2; c++) {
+							PrevHalf ph;
+							if (src)
+								prev_from_lds(src + 2048 * c, lane, ph);
+							else
+								prev_from_global(g + (uint32_t)chn[c] * cstride, lane, ph);
+							ola_quads_f32(img, lane, R[c], ph, V[c]);
+						}
+						if (chn[0] == 0)
+							store_interleaved2_f32(F, lane, it.out_off, V[0], V[1]);
+						else
+							store_interleaved2_f32(F, lane, it.out_off, V[1], V[0]);
 					} else {
 #pragma unroll
 						for (int c = 0; c < 2; c++)

@@ -3,6 +3,7 @@
 // `OggStreamReader` (src/inside_ogg.rs:30-314) on top of this library's packet decoder.  Host code only; everything
 // below the packet boundary goes through the public C ABI of include/lewton_amd.h.
 #include "../../include/lewton_amd.h"
+#include "lw_formats.hpp"
 
 #include <algorithm>
 #include <condition_variable>
@@ -990,9 +991,9 @@ struct lw_ogg_stream {
 
 	static void truncate(int fmt, int ch, void *out, size_t m, size_t target)
 	{
-		if (fmt == LW_FMT_I16_INTERLEAVED || target >= m)
+		if (lw_fmt_interleaved(fmt) || target >= m)
 			return; // interleaved: the first target * ch elements are already in place
-		const size_t es = fmt == LW_FMT_F32_PLANAR ? 4 : 2;
+		const size_t es = lw_elem_size(fmt);
 		for (int c = 1; c < ch; c++)
 			std::memmove((char *)out + (size_t)c * target * es, (char *)out + (size_t)c * m * es, target * es);
 	}
@@ -1224,13 +1225,13 @@ static int read_ahead_packet(lw_ogg_stream *s, int fmt, void *out, size_t cap_el
 		}
 		if (s->serving()) {
 			lw_ogg_stream::Served &e = s->served[s->served_next++];
-			const size_t es = fmt == LW_FMT_F32_PLANAR ? 4 : 2;
+			const size_t es = lw_elem_size(fmt);
 			const int st = e.status;
 			s->view_has_absgp = e.has_absgp;
 			s->view_absgp = e.absgp;
 			if (st == LW_OK) {
 				const char *src = (const char *)s->served_pcm + e.off * es;
-				if (fmt == LW_FMT_I16_INTERLEAVED || e.n == e.full) {
+				if (lw_fmt_interleaved(fmt) || e.n == e.full) {
 					std::memcpy(out, src, (size_t)e.n * ch * es);
 				} else { // the stream's last packet, truncated (inside_ogg.rs:219-227): the first n samples of every channel
 					for (size_t c = 0; c < ch; c++)
@@ -1266,7 +1267,7 @@ int lw_ogg_stream_read_dec_packet(lw_ogg_stream *s, int fmt, void *out, size_t c
 {
 	if (!s || !out || !n_samples)
 		return LW_ERR_NULL_ARG;
-	if (s->ra_k && fmt >= 0 && fmt <= 2) {
+	if (s->ra_k && lw_fmt_valid(fmt)) {
 		int rc = LW_OK;
 		if (!read_ahead_packet(s, fmt, out, cap_elems, n_samples, &rc))
 			return rc;
@@ -1296,7 +1297,7 @@ int lw_ogg_stream_set_entropy_on_device(lw_ogg_stream *s, int on)
 int lw_ogg_stream_read_dec_packets(lw_ogg_stream *s, int fmt, size_t max_packets, int n_threads, void *out,
 		size_t cap_elems, uint32_t *n_samples, int32_t *status, size_t *n_packets)
 {
-	if (!s || !out || !n_samples || !status || !n_packets || max_packets == 0 || fmt < 0 || fmt > 2)
+	if (!s || !out || !n_samples || !status || !n_packets || max_packets == 0 || !lw_fmt_valid(fmt))
 		return LW_ERR_NULL_ARG;
 	if (s->serving())
 		s->unserve(); // (the two reading calls mixed with the read-ahead on: this one continues behind the last packet handed out)
@@ -1370,7 +1371,7 @@ static int read_batch(lw_ogg_stream *s, int fmt, size_t max_packets, int n_threa
 	// per packet: truncation of the stream's last packet and granule bookkeeping, blocks packed back to back
 	lw_ident_info info;
 	lw_ident_get_info(s->ident, &info);
-	const size_t es = fmt == LW_FMT_F32_PLANAR ? 4 : 2;
+	const size_t es = lw_elem_size(fmt);
 	size_t w = 0; // write cursor in elements
 	if (serve) {
 		s->served.clear();

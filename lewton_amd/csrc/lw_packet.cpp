@@ -15,7 +15,7 @@ int lw_read_audio_packet(lw_decoder *d, const uint8_t *packet, size_t len, lw_pw
 		return LW_ERR_NULL_ARG;
 	if (pwr->dec != d)
 		return LW_ERR_STATE_MISMATCH;
-	if (fmt < 0 || fmt > 2)
+	if (!lw_fmt_valid(fmt))
 		return LW_ERR_NULL_ARG;
 	if (int rc = lw_decoder_set_device(d))
 		return rc;

@@ -18,6 +18,7 @@
 // launches' kernels one launch after the other, and its PCM copies are issued by the device's COPIER thread once their kernels
 // have finished, on one copy stream for all tenants of the device (see Copier below for the measurement behind it).
 #include "../../include/lewton_amd.h"
+#include "lw_formats.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -222,7 +223,7 @@ lw_ring *lw_ring_create(lw_decoder *d, size_t n_slots, size_t max_packets, int f
 	if (!err)
 		err = &dummy;
 	*err = LW_OK;
-	if (!d || n_slots < 1 || n_slots > 64 || max_packets == 0 || fmt < 0 || fmt > 2) {
+	if (!d || n_slots < 1 || n_slots > 64 || max_packets == 0 || !lw_fmt_valid(fmt)) {
 		*err = LW_ERR_NULL_ARG;
 		return nullptr;
 	}
@@ -231,7 +232,7 @@ lw_ring *lw_ring_create(lw_decoder *d, size_t n_slots, size_t max_packets, int f
 	r->device = lw_decoder_device(d);
 	r->fmt = fmt;
 	r->max_packets = max_packets;
-	r->esz = fmt == LW_FMT_F32_PLANAR ? 4 : 2;
+	r->esz = lw_elem_size(fmt);
 	r->cap_elems = max_packets * lw_decoder_max_block_elems(d);
 	r->slots.resize(n_slots);
 	bool good = ok(hipSetDevice(r->device));

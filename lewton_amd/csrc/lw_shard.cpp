@@ -9,6 +9,7 @@
 // is tested on a one-GPU box.  The process-per-GPU form (bench.py under torch.distributed.run) uses the same rule through
 // lewton_amd/shard.py; this is the single-process form INTEGRATION.md section 3 describes.
 #include "../../include/lewton_amd.h"
+#include "lw_formats.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -325,14 +326,14 @@ lw_sharder *lw_sharder_create(const lw_ident *id, const lw_setup *setup, const i
 	if (!err)
 		err = &dummy;
 	*err = LW_OK;
-	if (!id || !setup || !devices || n_shards == 0 || n_shards > 1024 || max_packets_per_shard == 0 || fmt < 0 || fmt > 2) {
+	if (!id || !setup || !devices || n_shards == 0 || n_shards > 1024 || max_packets_per_shard == 0 || !lw_fmt_valid(fmt)) {
 		*err = LW_ERR_NULL_ARG;
 		return nullptr;
 	}
 	auto sh = std::make_unique<lw_sharder>();
 	sh->max_packets = max_packets_per_shard;
 	sh->fmt = fmt;
-	sh->esz = fmt == LW_FMT_F32_PLANAR ? 4 : 2;
+	sh->esz = lw_elem_size(fmt);
 	for (size_t g = 0; g < n_shards; g++) {
 		auto s = std::make_unique<Shard>();
 		s->index = g;

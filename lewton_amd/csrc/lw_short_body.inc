@@ -170,7 +170,7 @@
 	}
 	lds_fence();
 	// ---- window / overlap-add / stores of the slot's own samples; state; the successor's left edge
-	const uint32_t esz_stride = FMT == LW_OUT_I16_INTERLEAVED ? F.ch : 1u;
+	const uint32_t esz_stride = lw_out_itl(FMT) ? F.ch : 1u;
 #pragma unroll
 	for (int c = 0; c < 2; c++) {
 		if (!mine[c])
@@ -187,7 +187,7 @@
 			} else {
 				prev_from_half8(prv[c], ph);
 			}
-			const uint32_t e0 = FMT == LW_OUT_I16_INTERLEAVED ? out_off + chn[c] : out_off + chn[c] * (16u * L);
+			const uint32_t e0 = lw_out_itl(FMT) ? out_off + chn[c] : out_off + chn[c] * (16u * L);
 			short_ola_store<FMT, L>(img, l, F.out, e0, esz_stride, R[c], ph);
 		}
 		if (kind == LW_SS_BLOCK && state_out >= 0)
@@ -210,7 +210,7 @@
 				ph.pp[c2][0] = float2_t{R[c][c2][0].y, R[c][c2][1].y};
 				ph.pp[c2][1] = float2_t{R[c][c2][2].y, R[c][c2][3].y};
 			}
-			const uint32_t e0 = FMT == LW_OUT_I16_INTERLEAVED ? next_out + chn[c] : next_out + chn[c] * next_m;
+			const uint32_t e0 = lw_out_itl(FMT) ? next_out + chn[c] : next_out + chn[c] * next_m;
 			short_ola_store<FMT, L>(img, l, F.out, e0, esz_stride, Rn, ph);
 		}
 	}

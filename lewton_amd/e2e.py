@@ -75,7 +75,7 @@ def measure(dec, pool, n_batches=32, packets=4096, streams=256, threads=0, slots
     rec_bytes = ch * half * 4 + 132 + 32   # f32 residues + floor records + packet record
     if device_entropy:
         rec_bytes = payload / packets + 8 + 16 + 32                     # the packet, its padding and descriptor, the packet record
-    esz = 4 if samples == "f32" else 2
+    esz = 4 if samples in ("f32", "f32_interleaved") else 2
     out = {
         "value": npk / dt, "unit": "packets/s", "packets": npk, "seconds": dt,
         "records": "raw packets, entropy stage on the device (k_entropy)" if device_entropy else "f32 residue vectors (host entropy stage)",

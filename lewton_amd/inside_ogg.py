@@ -107,11 +107,11 @@ class OggStreamReader:
         fmt = _FMT[samples]
         ch = self.ident_hdr.audio_channels
         cap = 1 << self.ident_hdr.blocksize_1
-        return fmt, ch, cap, np.zeros(ch * cap * packets, np.float32 if fmt == N.FMT_F32_PLANAR else np.int16)
+        return fmt, ch, cap, np.zeros(ch * cap * packets, N.fmt_dtype(fmt))
 
     @staticmethod
     def _shape(out, fmt, ch, m):
-        if fmt == N.FMT_I16_INTERLEAVED:
+        if N.fmt_interleaved(fmt):
             return out[: ch * m].copy()
         return out[: ch * m].reshape(ch, m).copy()
 

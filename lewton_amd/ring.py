@@ -90,7 +90,7 @@ class Ring:
         n, pcm, elems = C.c_size_t(0), C.c_void_p(0), C.c_size_t(0)
         self._call("lw_ring_collect", N.lw_ring_collect(self._h, C.byref(res), C.byref(n), C.byref(pcm), C.byref(elems)))
         out = [(res[i].status, res[i].n_samples, res[i].out_offset) for i in range(n.value)]
-        dt = np.float32 if self.fmt == N.FMT_F32_PLANAR else np.int16
+        dt = N.fmt_dtype(self.fmt)
         if elems.value:
             buf = (C.c_char * (elems.value * np.dtype(dt).itemsize)).from_address(pcm.value)
             a = np.frombuffer(buf, dtype=dt)

@@ -99,7 +99,7 @@ class Sharder:
             arr[i].len = len(data)
         ch = self.ident.audio_channels
         cap = n * ch * (1 << self.ident.blocksize_1)
-        out = np.zeros(cap, np.float32 if self.fmt == N.FMT_F32_PLANAR else np.int16)
+        out = np.zeros(cap, N.fmt_dtype(self.fmt))
         res = (N.PacketResult * n)()
         rc = N.lw_sharder_decode(self._h, arr, n, n_threads, out.ctypes.data_as(C.c_void_p), cap, res)
         if rc:
@@ -108,7 +108,7 @@ class Sharder:
         for i in range(n):
             if res[i].status != 0:
                 blocks.append(None)
-            elif self.fmt == N.FMT_I16_INTERLEAVED:
+            elif N.fmt_interleaved(self.fmt):
                 blocks.append(out[res[i].out_offset: res[i].out_offset + res[i].n_samples * ch])
             else:
                 blocks.append(out[res[i].out_offset: res[i].out_offset + res[i].n_samples * ch].reshape(ch, res[i].n_samples))
@@ -163,7 +163,7 @@ class Sharder:
         N, C = self._N, self._C
         n, elems = self._pending[0]
         if out is None or out.size < elems:
-            out = np.zeros(max(1, elems), np.float32 if self.fmt == N.FMT_F32_PLANAR else np.int16)
+            out = np.zeros(max(1, elems), N.fmt_dtype(self.fmt))
         if getattr(self, "_res_cap", 0) < n:
             self._res = (N.PacketResult * max(1, n))()
             self._res_cap = n
@@ -203,7 +203,7 @@ class Sharder:
             if N.lw_sharder_in_flight(self._h) < before:
                 self._pending.pop(0)
             raise RuntimeError("lw_sharder_collect_pinned: %d %s" % (rc, N.device_error()))
-        dt = np.float32 if self.fmt == N.FMT_F32_PLANAR else np.int16
+        dt = N.fmt_dtype(self.fmt)
         views = []
         for g in range(G):
             if el[g]:

@@ -7,7 +7,10 @@
 Same method as bench.py: records resident in HBM, hipGraph replay of rotated batches, HIP events -- and, like bench.py,
 the PCM the timed launches left for batch 0 is compared with the oracle, every packet (`parity` of each line; --no-verify
 skips it).  The oracle is the checker only; nothing timed touches it.
-    python tools/bench_configs.py [--steps 400] [--only 3,4]"""
+--format picks the sample format (i16, i16_interleaved, f32, f32_interleaved); several, comma-separated, are measured alternately
+(--rounds times each) in the same process, e.g. the interleaved f32 form against f32 planar on the bench line's shape ("1" =
+BASELINE configs[1], 256 stereo streams x 16 long packets):
+    python tools/bench_configs.py [--steps 400] [--only 3,4] [--format f32_interleaved,f32 --rounds 3]"""
 import argparse
 import dataclasses
 import ctypes as C
@@ -34,7 +37,17 @@ def rotation_batches(alg_bytes):
     return max(2, need, min(8, (3 * (1 << 29)) // max(1, alg_bytes)))
 
 
-def measure(w, steps=400, nb=NB, verify=True, force_generic=False, distinct=None, settle_ms=40.0, mix=None, branches=1, long10=None):
+def _planar_copy(flat, results, ch):
+    """interleaved output ([m][ch] per packet) re-laid as planar ([ch][m] per packet) at the same offsets"""
+    out = np.array(flat, copy=True)
+    for status, m, off in results:
+        if status == 0 and m:
+            out[off:off + m * ch] = flat[off:off + m * ch].reshape(m, ch).T.reshape(-1)
+    return out
+
+
+def measure(w, steps=400, nb=NB, verify=True, force_generic=False, distinct=None, settle_ms=40.0, mix=None, branches=1, long10=None,
+            fmt="i16"):
     """Time workload `w` (lewton_amd.workloads.Workload): `nb` rotated batches resident in HBM (default: as many as
     rotation_batches() asks for -- a footprint of at least 0.5 GiB), one hipGraph of `nb` steps replayed, HIP events; then
     (verify) every packet of timed batch 0 against the oracle.  Returns the result line as a dict.
@@ -57,12 +70,12 @@ def measure(w, steps=400, nb=NB, verify=True, force_generic=False, distinct=None
         r_ = b % len(seqs0)
         seqs = seqs0[r_:] + seqs0[:r_]
         prime_items, items = wl.items_of(w, seqs, pw)
-        prime = Batch(dec, w.n_streams, "i16")
+        prime = Batch(dec, w.n_streams, fmt)
         prime.entropy(prime_items, n_threads=0)
         prime.upload(None)
         prime.synth_to_host(None)
         prime.close()
-        bt = Batch(dec, NP, "i16")
+        bt = Batch(dec, NP, fmt)
         if mix is not None:
             bt.debug_set_mix(mix)   # lw_debug_batch_set_mix: 0 = mixed batches as two launches, -1 = as one where k_mix applies
         if force_generic:
@@ -71,7 +84,7 @@ def measure(w, steps=400, nb=NB, verify=True, force_generic=False, distinct=None
             bt.debug_set_long10(long10)   # lw_debug_batch_set_long10: 1 = k_long10 / k_long12 without their EDGE form, 0 = k_short<32> / k_big<12>
         bt.entropy(items, n_threads=0)
         bt.upload(None)
-        outs.append(torch.empty(max(1, bt.out_elems), dtype=torch.int16, device="cuda"))
+        outs.append(torch.empty(max(1, bt.out_elems), dtype=torch.float32 if fmt.startswith("f32") else torch.int16, device="cuda"))
         batches.append((bt, pw))
         material.append(seqs)
         if nb is None:
@@ -135,11 +148,14 @@ def measure(w, steps=400, nb=NB, verify=True, force_generic=False, distinct=None
         try:
             sys.path.insert(0, os.path.join(ROOT, "tests"))
             from common import verify_workload_batch
-            bad = verify_workload_batch(w, setup, material[0], batches[0][0].results(), outs[0].cpu().numpy(), "i16")
-            parity = ("timed batch 0: %d packets i16 bit-exact vs oracle" % NP) if bad == 0 else "MISMATCH: %d of %d packets" % (bad, NP)
+            flat, vfmt = outs[0].cpu().numpy(), fmt
+            if fmt == "f32_interleaved":
+                flat, vfmt = _planar_copy(flat, batches[0][0].results(), setup.channels), "f32"
+            bad = verify_workload_batch(w, setup, material[0], batches[0][0].results(), flat, vfmt)
+            parity = ("timed batch 0: %d packets %s bit-exact vs oracle" % (NP, fmt)) if bad == 0 else "MISMATCH: %d of %d packets" % (bad, NP)
         except Exception as e:  # the oracle is only a checker here
             parity = "unchecked: %r" % (e,)
-    res = {"config": w.name, "packets_per_launch": NP, "streams": w.n_streams, "steps": reps * nb, "us_per_launch": round(us, 2),
+    res = {"config": w.name, "format": fmt, "packets_per_launch": NP, "streams": w.n_streams, "steps": reps * nb, "us_per_launch": round(us, 2),
            "M_packets_per_s": round(NP / us, 2), "algorithmic_bytes_per_launch": alg,
            "batches_rotated": nb, "footprint_bytes": nb * alg,
            "pct_of_8TBps": round(100 * alg / (us * 1e-6) / 8e12, 2),
@@ -164,8 +180,17 @@ if __name__ == "__main__":
     ap.add_argument("--branches", type=int, default=1, help="experiment: the rotated batches as this many parallel chains of the graph (use --mix 0 with mixed shapes)")
     ap.add_argument("--long10", type=int, default=None, help="lw_debug_batch_set_long10: 1 = without the EDGE form (long blocks next to short ones on the generic kernels)")
     ap.add_argument("--mix", type=int, default=None, help="lw_debug_batch_set_mix: 0 = mixed batches as two launches, -1 = as one where k_mix applies (default)")
+    ap.add_argument("--format", default="i16", help="sample format(s), comma-separated: measured alternately (i16, i16_interleaved, f32, f32_interleaved)")
+    ap.add_argument("--rounds", type=int, default=1, help="with several formats: alternations per config")
     args = ap.parse_args()
     ONLY = set(args.only.split(",")) if args.only else {"3", "4", "5"}
-    for w in wl.configs(args.packets):
-        if w.key in ONLY:
-            print(json.dumps(measure(w, args.steps, args.nb or None, not args.no_verify, args.force_generic, mix=args.mix, branches=args.branches, long10=args.long10)), flush=True)
+    fmts = args.format.split(",")
+    todo = [w for w in wl.configs(args.packets) if w.key in ONLY]
+    if "1" in ONLY:   # BASELINE configs[1], the bench line's shape: 256 stereo streams x packets / 256 long packets
+        todo.insert(0, dataclasses.replace(wl.by_key("9", args.packets // 2), key="1", name="1 stereo long blocks (bench line)",
+                                           note="256 coupled stereo streams x %d consecutive long packets" % (args.packets // 256)))
+    for w in todo:
+        for _ in range(args.rounds if len(fmts) > 1 else 1):
+            for fmt in fmts:
+                print(json.dumps(measure(w, args.steps, args.nb or None, not args.no_verify, args.force_generic, mix=args.mix,
+                                         branches=args.branches, long10=args.long10, fmt=fmt)), flush=True)

@@ -17,7 +17,8 @@ def funcs(path):
             continue
         ins = ln.split("//")[0].strip()
         ins = re.sub(r"<[^>]+>", "<L>", ins)            # symbolic branch targets
-        if ins and not ins.startswith("s_nop") and not ins.startswith("s_code_end"):
+        # ("...": objdump's mark for elided zero bytes, the padding behind the section's last function)
+        if ins and ins != "..." and not ins.startswith("s_nop") and not ins.startswith("s_code_end"):
             cur.append(ins)
     return out
 

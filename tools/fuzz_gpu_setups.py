@@ -32,8 +32,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from common import f32_identical  # noqa: E402
 
-FMTS = ["i16", "f32", "i16_interleaved"]
-OFMT = {"i16": "i16", "f32": "f32", "i16_interleaved": "i16_itl"}
+FMTS = ["i16", "f32", "i16_interleaved", "f32_interleaved"]
+OFMT = {"i16": "i16", "f32": "f32", "i16_interleaved": "i16_itl", "f32_interleaved": "f32"}  # (f32 planar, interleaved here)
 DISTINCT = 3          # distinct packet sequences generated per setup (stream s carries sequence s % DISTINCT)
 
 
@@ -74,7 +74,7 @@ def run_setup(seed, ch, idp, stp, seqs, packets, rng, mods, length=None):
     o_st = po.Setup(stp, o_id)
     line = census_line(N, ident, st)
     dec = audio.Decoder(ident, st, 0)
-    fmt = FMTS[seed % 3]
+    fmt = FMTS[seed % len(FMTS)]
     if length is None:
         n_streams, length = shape_of(seed, packets)
     else:
@@ -86,7 +86,8 @@ def run_setup(seed, ch, idp, stp, seqs, packets, rng, mods, length=None):
         rows = []
         for p in seqs[q]:
             try:
-                rows.append((0, np.asarray(po.read_audio_packet(o_id, o_st, p, opw, OFMT[fmt]))))
+                w = np.asarray(po.read_audio_packet(o_id, o_st, p, opw, OFMT[fmt]))
+                rows.append((0, np.ascontiguousarray(w.T).reshape(-1) if fmt == "f32_interleaved" else w))
             except po.OracleError as e:
                 rows.append((e.code, None))
         want.append((rows, opw.data(ch)))
@@ -130,11 +131,11 @@ def run_setup(seed, ch, idp, stp, seqs, packets, rng, mods, length=None):
                     if rc:
                         continue
                     g = pcm[i]
-                    same = g.size == w.size and (f32_identical(g, w) if fmt == "f32" else np.array_equal(g.reshape(-1), w.reshape(-1)))
+                    same = g.size == w.size and (f32_identical(g, w) if fmt.startswith("f32") else np.array_equal(g.reshape(-1), w.reshape(-1)))
                     if not same:
                         bad = -1
                         if g.size == w.size:
-                            bad = int(np.flatnonzero(g.reshape(-1) != w.reshape(-1))[0]) if fmt != "f32" else int(
+                            bad = int(np.flatnonzero(g.reshape(-1) != w.reshape(-1))[0]) if not fmt.startswith("f32") else int(
                                 np.flatnonzero(g.reshape(-1).view(np.uint32) != w.reshape(-1).view(np.uint32))[0])
                         print("PCM MISMATCH setup %d (%s path) fmt %s stream %d packet %d (first differing element %d of %d; kernels %s)\n  %s" % (
                             seed, name, fmt, s, t, bad, w.size, paths[0][1].last_kernels, line))
