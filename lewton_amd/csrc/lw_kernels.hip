@@ -15,6 +15,7 @@
 //                    :1006-1039 (floor x residue), src/imdct.rs:291-659 (all steps)
 //   k_ola_generic    src/audio.rs:1082-1154 (overlap add, state), src/samples.rs:32-103 (conversion)
 #include "lw_kernels.hpp"
+#include "lw_pcm_store.inc"
 
 #define LW_BLOCK 256
 // workgroup size of k_decouple / k_ola_generic (64-thread workgroups measured slower: 20.7 / 14.2 us vs 11.9 / 11.6 us on the
@@ -779,17 +780,6 @@ k_imdct_generic(LwDevTables T, LwBatchDev B, float *tap_spec, int use_decoupled,
 // ---------------------------------------------------------------------------------------------
 // window + overlap-add + state + sample conversion, one workgroup per (packet, channel)
 // ---------------------------------------------------------------------------------------------
-// samples.rs:92-103: x*32768, clamp to [-32768, 32767], truncate toward zero; NaN -> 0
-__device__ __forceinline__ int16_t to_i16(float x)
-{
-	const float t = x * 32768.0f;
-	if (t > 32767.0f)
-		return 32767;
-	if (t < -32768.0f)
-		return -32768;
-	return (int16_t)(int)t; // in range: truncation toward zero; NaN -> 0 (v_cvt_i32_f32), like Rust `as`
-}
-
 template <int FMT>
 __global__ void __launch_bounds__(LW_BLOCK) k_ola_generic(LwDevTables T, LwBatchDev B, void *out_v, uint32_t skip_mask)
 {
@@ -837,14 +827,7 @@ __global__ void __launch_bounds__(LW_BLOCK) k_ola_generic(LwDevTables T, LwBatch
 				float x = cur0[c * n + ls + i];
 				if (i < plen)
 					x = (x * slope[i]) + (prev0[c * prev_stride + i] * slope[plen - 1 - i]); // audio.rs:1116-1118
-				if (FMT == LW_OUT_I16_PLANAR)
-					((int16_t *)out_v)[o.out_off + c * m + i] = to_i16(x);
-				else if (FMT == LW_OUT_I16_INTERLEAVED)
-					((int16_t *)out_v)[o.out_off + i * T.ch + c] = to_i16(x);
-				else if (FMT == LW_OUT_F32_INTERLEAVED)
-					((float *)out_v)[o.out_off + i * T.ch + c] = x;
-				else
-					((float *)out_v)[o.out_off + c * m + i] = x;
+				pcm_store1<FMT>(out_v, lw_out_itl(FMT) ? o.out_off + i * T.ch + c : o.out_off + c * m + i, x);
 			}
 		}
 		if (o.state_out >= 0 && re > rs) { // audio.rs:1121, :1142-1147: the raw (un-windowed) right part
@@ -900,14 +883,7 @@ __global__ void __launch_bounds__(LW_BLOCK) k_ola_generic(LwDevTables T, LwBatch
 			float x = cur0[c * n + ls + i];
 			if (i < plen)
 				x = (x * slope[i]) + (prev0[c * prev_stride + i] * slope[plen - 1 - i]); // audio.rs:1116-1118
-			if (FMT == LW_OUT_I16_PLANAR)
-				((int16_t *)out_v)[rec.out_off + c * m + i] = to_i16(x);
-			else if (FMT == LW_OUT_I16_INTERLEAVED)
-				((int16_t *)out_v)[rec.out_off + i * T.ch + c] = to_i16(x);
-			else if (FMT == LW_OUT_F32_INTERLEAVED)
-				((float *)out_v)[rec.out_off + i * T.ch + c] = x;
-			else
-				((float *)out_v)[rec.out_off + c * m + i] = x;
+			pcm_store1<FMT>(out_v, lw_out_itl(FMT) ? rec.out_off + i * T.ch + c : rec.out_off + c * m + i, x);
 		}
 	}
 	if (rec.state_out >= 0 && re > rs) { // audio.rs:1121, :1142-1147: the raw (un-windowed) right part
@@ -972,12 +948,8 @@ void lw_launch_generic_ola(const LwDevTables &T, const LwBatchDev &B, void *out,
 	const dim3 g(B.gen_ola ? B.n_gen_ola : B.n_packets), b(LW_ELEMENTWISE_BLOCK);
 	if (g.x == 0)
 		return;
-	if (fmt == LW_OUT_I16_PLANAR)
-		hipLaunchKernelGGL(k_ola_generic<LW_OUT_I16_PLANAR>, g, b, 0, st, T, B, out, skip_mask);
-	else if (fmt == LW_OUT_I16_INTERLEAVED)
-		hipLaunchKernelGGL(k_ola_generic<LW_OUT_I16_INTERLEAVED>, g, b, 0, st, T, B, out, skip_mask);
-	else if (fmt == LW_OUT_F32_INTERLEAVED)
-		hipLaunchKernelGGL(k_ola_generic<LW_OUT_F32_INTERLEAVED>, g, b, 0, st, T, B, out, skip_mask);
-	else if (fmt == LW_OUT_F32_PLANAR)
-		hipLaunchKernelGGL(k_ola_generic<LW_OUT_F32_PLANAR>, g, b, 0, st, T, B, out, skip_mask);
+	(void)lw_with_out_fmt(fmt, [&](auto f) { // (an unknown tag launches nothing)
+		hipLaunchKernelGGL(k_ola_generic<f.value>, g, b, 0, st, T, B, out, skip_mask);
+		return hipSuccess;
+	});
 }

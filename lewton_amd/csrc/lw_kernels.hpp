@@ -76,10 +76,16 @@ struct LwDevTables {
 #define LW_SMALL_BS 9
 
 // Kernel-internal sample formats (the `fmt` argument of the launchers; the host maps the public LW_FMT_* onto them,
-// lw_kernel_fmt in lw_internal.hpp).  3 is LW_OUT_I16_ITL_STEREO and 5 LW_OUT_F32_ITL_STEREO, the stereo unit forms that
-// only k_long's launcher chooses (lw_kernels_long.hip).
-enum LwOutFmt { LW_OUT_I16_PLANAR = 0, LW_OUT_I16_INTERLEAVED = 1, LW_OUT_F32_PLANAR = 2, LW_OUT_F32_INTERLEAVED = 4 };
-#define LW_OUT_F32_ITL_STEREO 5
+// lw_kernel_fmt in lw_internal.hpp).  The launchers take 0, 1, 2 and 4 (lw_with_out_fmt); 3 and 5 are the stereo unit forms,
+// the interleaved formats of a 2-channel stream whose channels form ONE unit (a coupled pair), that only k_long's launcher chooses.
+enum LwOutFmt {
+	LW_OUT_I16_PLANAR = 0,
+	LW_OUT_I16_INTERLEAVED = 1,
+	LW_OUT_F32_PLANAR = 2,
+	LW_OUT_I16_ITL_STEREO = 3,
+	LW_OUT_F32_INTERLEAVED = 4,
+	LW_OUT_F32_ITL_STEREO = 5
+};
 
 // f32 samples (no conversion), and the generic interleaved stores (element i of channel c at i * ch + c)
 __host__ __device__ constexpr bool lw_out_f32(int f)
@@ -89,6 +95,29 @@ __host__ __device__ constexpr bool lw_out_f32(int f)
 __host__ __device__ constexpr bool lw_out_itl(int f)
 {
 	return f == LW_OUT_I16_INTERLEAVED || f == LW_OUT_F32_INTERLEAVED;
+}
+// the generic format of a stereo unit form (the kernel variants without one: PRE, SPLIT, EDGE)
+__host__ __device__ constexpr int lw_out_unit_free(int f)
+{
+	return f == LW_OUT_I16_ITL_STEREO ? LW_OUT_I16_INTERLEAVED : f == LW_OUT_F32_ITL_STEREO ? LW_OUT_F32_INTERLEAVED : f;
+}
+
+// The one place where a launcher's runtime `fmt` becomes a template argument: fn(std::integral_constant<int, FMT>{}) for the four
+// tags a launcher takes, hipErrorInvalidValue for any other value.
+template <class Fn>
+static inline hipError_t lw_with_out_fmt(int fmt, Fn &&fn)
+{
+	switch (fmt) {
+	case LW_OUT_I16_PLANAR:
+		return fn(std::integral_constant<int, LW_OUT_I16_PLANAR>{});
+	case LW_OUT_I16_INTERLEAVED:
+		return fn(std::integral_constant<int, LW_OUT_I16_INTERLEAVED>{});
+	case LW_OUT_F32_INTERLEAVED:
+		return fn(std::integral_constant<int, LW_OUT_F32_INTERLEAVED>{});
+	case LW_OUT_F32_PLANAR:
+		return fn(std::integral_constant<int, LW_OUT_F32_PLANAR>{});
+	}
+	return hipErrorInvalidValue;
 }
 
 struct LwBatchDev {

@@ -8,7 +8,7 @@
 //   src/audio.rs:762-777 (inverse coupling)     decouple()
 //   src/imdct.rs:291-659 (inverse MDCT)         passes P0 .. P3 + E below
 //   src/audio.rs:1082-1154 (overlap-add, state) phase E of the kernel
-//   src/samples.rs:92-103 (conversion)          store_pair()
+//   src/samples.rs:92-103 (conversion)          pcm_store2() (lw_pcm_store.inc)
 //   src/header_cached.rs:104-108 (bit reversal) computed (v_bfrev_b32) in phase E
 //
 // One workgroup of T = n / 32 threads (2 / 4 waves) works through the `passes` consecutive slots of one task (the block kernel's
@@ -29,9 +29,7 @@
 // data movement (tests/big_model.py) reproduces the oracle bit for bit on the CPU.
 #include "lw_fast.hpp"
 #include "lw_kernels.hpp"
-
-typedef float float2_t __attribute__((ext_vector_type(2)));
-typedef float float4_t __attribute__((ext_vector_type(4)));
+#include "lw_pcm_store.inc"
 
 struct LwBigArgs {
 	const float *residue;
@@ -204,34 +202,6 @@ __device__ __forceinline__ float floor_bin(const float *inv_s, float kf, float4_
 {
 	const float t = __builtin_fmaf(__builtin_fmaf(kf, ent.x, ent.y), ent.z, ent.w);
 	return *reinterpret_cast<const float *>(reinterpret_cast<const char *>(inv_s) + ((__float_as_uint(t) & LW_BIG_FLOOR_MASK) - 4u));
-}
-
-template <int FMT>
-__device__ __forceinline__ void store_pair(void *out, uint32_t elem0, uint32_t pos, uint32_t stride, float a, float b)
-{
-	if (FMT == LW_OUT_F32_PLANAR) {
-		*reinterpret_cast<float2_t *>(reinterpret_cast<float *>(out) + elem0 + pos) = float2_t{a, b};
-	} else if (FMT == LW_OUT_F32_INTERLEAVED) {
-		float *o = reinterpret_cast<float *>(out) + elem0;
-		o[pos * stride] = a;
-		o[(pos + 1u) * stride] = b;
-	} else {
-		// samples.rs:92-103: x * 32768, truncate toward zero (v_cvt_i32_f32: saturating, NaN -> 0), clamp to i16 by the saturating
-		// pack (clamping the integer = clamping the float first: the bounds are integers)
-		typedef short short2_t __attribute__((ext_vector_type(2)));
-		union {
-			short2_t s;
-			uint32_t u;
-		} v;
-		v.s = __builtin_amdgcn_cvt_pk_i16((int)(a * 32768.0f), (int)(b * 32768.0f));
-		int16_t *o = reinterpret_cast<int16_t *>(out) + elem0;
-		if (FMT == LW_OUT_I16_PLANAR) {
-			*reinterpret_cast<uint32_t *>(o + pos) = v.u;
-		} else {
-			o[pos * stride] = v.s.x;
-			o[(pos + 1u) * stride] = v.s.y;
-		}
-	}
 }
 
 } // namespace
@@ -567,10 +537,10 @@ __global__ void __launch_bounds__(1 << (BS - 5)) __attribute__((amdgpu_waves_per
 						const float s2 = (pa[2] * wC.y) + (pp[2] * wD.x), s2m = ((-pa[2]) * wD.x) + (pp[2] * wC.y);
 						const float s3 = (pa[3] * wC.x) + (pp[3] * wD.y), s3m = ((-pa[3]) * wD.y) + (pp[3] * wC.x);
 						const uint32_t mt = tl + T * e;
-						store_pair<FMT>(F.out, elem0, n4 - 2u - 2u * mt, stride, s1, s0);
-						store_pair<FMT>(F.out, elem0, n4 + 2u * mt, stride, s0m, s1m);
-						store_pair<FMT>(F.out, elem0, 2u * mt, stride, s3, s2);
-						store_pair<FMT>(F.out, elem0, n2 - 2u - 2u * mt, stride, s2m, s3m);
+						pcm_store2<FMT>(F.out, elem0, n4 - 2u - 2u * mt, stride, s1, s0);
+						pcm_store2<FMT>(F.out, elem0, n4 + 2u * mt, stride, s0m, s1m);
+						pcm_store2<FMT>(F.out, elem0, 2u * mt, stride, s3, s2);
+						pcm_store2<FMT>(F.out, elem0, n2 - 2u - 2u * mt, stride, s2m, s3m);
 					}
 					// the raw right part (audio.rs:1121, :1142-1147): pb(p) at n/4 - 1 - p and mirrored at n/4 + p
 #pragma unroll
@@ -600,15 +570,7 @@ static hipError_t launch_big(const LwBigArgs &F, int fmt, hipStream_t st)
 {
 	const dim3 g(F.n_wg), b(1u << (BS - 5));
 	LwBigArgs A = F;
-	if (fmt == LW_OUT_I16_PLANAR)
-		return lw_launch_k(k_big<LW_OUT_I16_PLANAR, BS>, g, b, 0, st, A);
-	if (fmt == LW_OUT_I16_INTERLEAVED)
-		return lw_launch_k(k_big<LW_OUT_I16_INTERLEAVED, BS>, g, b, 0, st, A);
-	if (fmt == LW_OUT_F32_INTERLEAVED)
-		return lw_launch_k(k_big<LW_OUT_F32_INTERLEAVED, BS>, g, b, 0, st, A);
-	if (fmt != LW_OUT_F32_PLANAR)
-		return hipErrorInvalidValue;
-	return lw_launch_k(k_big<LW_OUT_F32_PLANAR, BS>, g, b, 0, st, A);
+	return lw_with_out_fmt(fmt, [&](auto f) { return lw_launch_k(k_big<f.value, BS>, g, b, 0, st, A); });
 }
 
 hipError_t lw_launch_big(const LwDevTables &T, const LwBatchDev &B, const LwShortLaunch &L, void *out, int fmt, hipStream_t st)

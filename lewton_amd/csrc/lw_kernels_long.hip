@@ -33,6 +33,7 @@
 
 #include "lw_fast.hpp"
 #include "lw_kernels.hpp"
+#include "lw_pcm_store.inc"
 
 #define LW_WG (64 * LW_FAST_WAVES)
 // wave priorities (s_setprio 0..3) of the three kinds of phases; measured on MI355X (tools/exp.sh)
@@ -76,8 +77,6 @@ struct LwFastArgs {
 };
 static_assert(offsetof(LwFastArgs, waves) == 48, "kernel reads waves[] through the kernarg segment pointer");
 
-typedef float float2_t __attribute__((ext_vector_type(2)));
-typedef float float4_t __attribute__((ext_vector_type(4)));
 typedef unsigned int uint2_t __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ void lds_fence()
@@ -1154,30 +1153,6 @@ __device__ __forceinline__ void prev_from_global(const float *g, uint32_t lane, 
 	h.pp[0][0] = float2_t{g1.w, g1.z}; // (c2=0: k=0 -> 511-4l, k=1 -> 510-4l)
 }
 
-// 8-byte PCM store as a write-through (sc1) store: the bytes leave the L2 while the kernel is still running instead of
-// staying dirty until the end-of-kernel write-back (16.8 MB of dirty PCM cost ~2.7 us at every kernel boundary)
-__device__ __forceinline__ void store_pcm8(void *p, uint32_t lo, uint32_t hi)
-{
-	__hip_atomic_store(reinterpret_cast<unsigned long long *>(p), ((unsigned long long)hi << 32) | lo, __ATOMIC_RELAXED,
-			__HIP_MEMORY_SCOPE_AGENT);
-}
-
-// 16-byte write-through store (f32 PCM, stream state).  Inline asm because the builtin path offers sc1 only up to 8
-// bytes; the trailing s_nop keeps hipcc from overwriting the data registers before the store has read them.
-__device__ __forceinline__ void store16_wt(void *p, float4_t v)
-{
-	asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-}
-
-// kernel-internal output format: LW_OUT_I16_INTERLEAVED of a 2-channel stream whose channels form ONE unit (a coupled pair)
-#define LW_OUT_I16_ITL_STEREO 3
-
-// the generic format of a stereo unit form (the kernel variants without one: PRE, SPLIT, EDGE)
-constexpr int lw_out_unit_free(int f)
-{
-	return f == LW_OUT_I16_ITL_STEREO ? LW_OUT_I16_INTERLEAVED : f == LW_OUT_F32_ITL_STEREO ? LW_OUT_F32_INTERLEAVED : f;
-}
-
 // ---- interleaved stereo (InterleavedSamples<i16>, samples.rs:48-78; `read_dec_packet_itl`): one channel's window +
 //      overlap-add + conversion, packed two samples per dword: D[g][h] = positions (p_g + 2h, p_g + 2h + 1), with
 //      p_0 = 4l, p_1 = 508 - 4l, p_2 = 512 + 4l, p_3 = 1020 - 4l
@@ -1236,10 +1211,10 @@ __device__ __forceinline__ void ola_quads_f32(const char *img, uint32_t lane, co
 		const float4_t w1 = lds4(img + LWI_WIN, 32u * (64u * c2 + lane) + 16u);
 		ola_block<false>(Rc[c2], h.pp[c2][0], h.pp[c2][1], w0, w1, O[c2]);
 	}
-	V[0] = float4_t{O[0][3].x, O[0][2].x, O[1][3].x, O[1][2].x};
-	V[1] = float4_t{O[1][1].x, O[1][0].x, O[0][1].x, O[0][0].x};
-	V[2] = float4_t{O[0][0].y, O[0][1].y, O[1][0].y, O[1][1].y};
-	V[3] = float4_t{O[1][2].y, O[1][3].y, O[0][2].y, O[0][3].y};
+	const LwQuads q = pcm_quads(O);
+#pragma unroll
+	for (int g = 0; g < 4; g++)
+		V[g] = float4_t{q.v[g][0], q.v[g][1], q.v[g][2], q.v[g][3]};
 }
 
 // (L, R) frames of four consecutive positions = 32 contiguous bytes per lane and group.  Stored as they lie, every 16-byte store
@@ -1368,7 +1343,6 @@ __device__ __forceinline__ void ola_store(const LwFastArgs &F, const char *img, 
 // ---- raw left half of one channel to a td block: q ascending, then mirrored with the sign flipped (imdct.rs:589-658)
 #define LW_PA_LO0(c) float4_t{R[c][0][3].x, R[c][0][2].x, R[c][1][3].x, R[c][1][2].x}
 #define LW_PA_LO1(c) float4_t{R[c][1][1].x, R[c][1][0].x, R[c][0][1].x, R[c][0][0].x}
-__device__ __forceinline__ void store16_wt(void *p, float4_t v);
 __device__ __forceinline__ void store_left_half(float *dst, uint32_t lane, float4_t lo0, float4_t lo1)
 {
 	const float4_t hi0 = float4_t{-lo1.w, -lo1.z, -lo1.y, -lo1.x}; // 1023-q for q = 511-4l .. 508-4l
@@ -1801,44 +1775,11 @@ __device__ __forceinline__ void short_ola_store(const char *img, uint32_t l, voi
 		const float4_t w1 = lds4(img + LwBlkLayout<L>::WIN, 32u * (L * c2 + l) + 16u);
 		ola_block<!lw_out_f32(FMT)>(Rc[c2], h.pp[c2][0], h.pp[c2][1], w0, w1, O[c2]);
 	}
-	// positions: [4l..4l+3] = .x of (0,3) (0,2) (1,3) (1,2); [8L-4-4l..] = .x of (1,1) (1,0) (0,1) (0,0)
-	//            [8L+4l..] = .y of (0,0) (0,1) (1,0) (1,1); [16L-4-4l..] = .y of (1,2) (1,3) (0,2) (0,3)
 	const uint32_t pos[4] = {4u * l, 8u * L - 4u - 4u * l, 8u * L + 4u * l, 16u * L - 4u - 4u * l};
-	const float v[4][4] = {{O[0][3].x, O[0][2].x, O[1][3].x, O[1][2].x}, {O[1][1].x, O[1][0].x, O[0][1].x, O[0][0].x},
-		{O[0][0].y, O[0][1].y, O[1][0].y, O[1][1].y}, {O[1][2].y, O[1][3].y, O[0][2].y, O[0][3].y}};
+	const LwQuads q = pcm_quads(O);
 #pragma unroll
-	for (int q = 0; q < 4; q++) {
-		if (FMT == LW_OUT_F32_PLANAR) {
-			store16_wt(reinterpret_cast<float *>(out) + elem0 + pos[q], float4_t{v[q][0], v[q][1], v[q][2], v[q][3]});
-		} else if (FMT == LW_OUT_F32_INTERLEAVED) {
-			float *o = reinterpret_cast<float *>(out) + elem0;
-			const uint32_t off = pos[q] * stride;
-			o[off] = v[q][0];
-			o[off + stride] = v[q][1];
-			o[off + 2u * stride] = v[q][2];
-			o[off + 3u * stride] = v[q][3];
-		} else {
-			// samples.rs:92-103: x * 32768 (done in ola_block), truncate toward zero (v_cvt_i32_f32: saturating, NaN -> 0), clamp
-			// to i16 by the saturating pack
-			typedef short short2_t __attribute__((ext_vector_type(2)));
-			union {
-				short2_t s;
-				uint32_t u;
-			} a, b;
-			a.s = __builtin_amdgcn_cvt_pk_i16((int)v[q][0], (int)v[q][1]);
-			b.s = __builtin_amdgcn_cvt_pk_i16((int)v[q][2], (int)v[q][3]);
-			int16_t *o = reinterpret_cast<int16_t *>(out) + elem0;
-			if (FMT == LW_OUT_I16_PLANAR) {
-				store_pcm8(o + pos[q], a.u, b.u);
-			} else {
-				uint32_t off = pos[q] * stride;
-				o[off] = a.s.x;
-				o[off + stride] = a.s.y;
-				o[off + 2u * stride] = b.s.x;
-				o[off + 3u * stride] = b.s.y;
-			}
-		}
-	}
+	for (int g = 0; g < 4; g++)
+		pcm_store4<FMT>(out, elem0, 0u, pos[g], stride, q.v[g]);
 }
 
 // raw right part (16 L floats: pb(q) for q ascending, then mirrored) of one channel to a state slot / td block
@@ -1980,15 +1921,7 @@ static hipError_t launch_short(LwShortArgs &F, int fmt, hipStream_t st)
 	// one wave per workgroup with 17-30 KB of LDS (below the 64 KB that need no attribute): the waves a CU holds at a time
 	// are bounded by LDS for L = 16 / 32 and by registers for L = 8
 	const dim3 grid(F.n_waves), block(64);
-	if (fmt == LW_OUT_I16_PLANAR)
-		return lw_launch_k(k_short<LW_OUT_I16_PLANAR, L>, grid, block, 0, st, F);
-	if (fmt == LW_OUT_I16_INTERLEAVED)
-		return lw_launch_k(k_short<LW_OUT_I16_INTERLEAVED, L>, grid, block, 0, st, F);
-	if (fmt == LW_OUT_F32_INTERLEAVED)
-		return lw_launch_k(k_short<LW_OUT_F32_INTERLEAVED, L>, grid, block, 0, st, F);
-	if (fmt != LW_OUT_F32_PLANAR)
-		return hipErrorInvalidValue;
-	return lw_launch_k(k_short<LW_OUT_F32_PLANAR, L>, grid, block, 0, st, F);
+	return lw_with_out_fmt(fmt, [&](auto f) { return lw_launch_k(k_short<f.value, L>, grid, block, 0, st, F); });
 }
 
 // the kernel arguments of a k_short launch (also the short role of k_mix)
@@ -2133,56 +2066,45 @@ static hipError_t long_prepare(const LwDevTables &T, const LwBatchDev &B, const 
 	return hipSuccess;
 }
 
+// the main pass of k_long in format FMT (a stereo unit form only where the kernel variant has one)
+template <int FMT>
+static hipError_t launch_long_main(const LwFastLaunch &L, LwFastArgs &F, uint32_t grid, size_t lds, hipStream_t st)
+{
+	constexpr int FP = lw_out_unit_free(FMT);
+	if (L.pre_on) { // coupling steps inside the waves (never with split units, never the stereo frame stores)
+		if (L.edge_mode)
+			return lw_launch_k(k_long<FP, false, false, true, false, true>, dim3(grid), dim3(LW_WG), lds, st, F);
+		if (L.has_tdonly)
+			return lw_launch_k(k_long<FP, false, true, false, false, true>, dim3(grid), dim3(LW_WG), lds, st, F);
+		return lw_launch_k(k_long<FP, false, false, false, false, true>, dim3(grid), dim3(LW_WG), lds, st, F);
+	}
+	if (L.split && !L.has_tdonly) { // sparse launch: one channel per wave (generic interleaved stores: a wave has one channel)
+		if (L.edge_mode)
+			return lw_launch_k(k_long<FP, false, false, true, true>, dim3(grid), dim3(LW_WG), lds, st, F);
+		return lw_launch_k(k_long<FP, false, false, false, true>, dim3(grid), dim3(LW_WG), lds, st, F);
+	}
+	if (L.edge_mode)
+		return lw_launch_k(k_long<FP, false, false, true>, dim3(grid), dim3(LW_WG), lds, st, F);
+	if (L.has_tdonly)
+		return lw_launch_k(k_long<FMT, false, true>, dim3(grid), dim3(LW_WG), lds, st, F);
+	return lw_launch_k(k_long<FMT, false, false>, dim3(grid), dim3(LW_WG), lds, st, F);
+}
+
 hipError_t lw_launch_long(const LwDevTables &T, const LwBatchDev &B, const LwFastLaunch &L, void *out, int fmt, hipStream_t st)
 {
 	LwFastArgs F{};
 	uint32_t grid = 0;
 	const hipError_t pe = long_prepare(T, B, L, out, st, F, grid);
-	if (pe != hipSuccess)
+	if (pe != hipSuccess || !L.n_items)
 		return pe;
 	const size_t lds = LW_LDS_BYTES + LW_STAMP_LDS_EXTRA;
-	if (L.n_items) {
-#define LW_LAUNCH_MAIN(F_)                                                                                     \
-	do {                                                                                                      \
-		if (L.pre_on) { /* coupling steps inside the waves (never with split units, never the stereo frame stores) */ \
-			constexpr int FP = lw_out_unit_free(F_);                                                           \
-			if (L.edge_mode)                                                                                  \
-				return lw_launch_k(k_long<FP, false, false, true, false, true>, dim3(grid), dim3(LW_WG), lds, st, F); \
-			if (L.has_tdonly)                                                                                 \
-				return lw_launch_k(k_long<FP, false, true, false, false, true>, dim3(grid), dim3(LW_WG), lds, st, F); \
-			return lw_launch_k(k_long<FP, false, false, false, false, true>, dim3(grid), dim3(LW_WG), lds, st, F); \
-		}                                                                                                     \
-		if (L.split && !L.has_tdonly) { /* sparse launch: one channel per wave (generic interleaved stores: a wave has one channel) */ \
-			if (L.edge_mode)                                                                                  \
-				return lw_launch_k(k_long<lw_out_unit_free(F_), false, false, true, true>,                     \
-						dim3(grid), dim3(LW_WG), lds, st, F);                                                  \
-			return lw_launch_k(k_long<lw_out_unit_free(F_), false, false, false, true>,                        \
-					dim3(grid), dim3(LW_WG), lds, st, F);                                                      \
-		}                                                                                                     \
-		if (L.edge_mode)                                                                                      \
-			return lw_launch_k(k_long<lw_out_unit_free(F_), false, false, true>, dim3(grid),                   \
-					dim3(LW_WG), lds, st, F);                                                                  \
-		if (L.has_tdonly)                                                                                     \
-			return lw_launch_k(k_long<F_, false, true>, dim3(grid), dim3(LW_WG), lds, st, F);                  \
-		return lw_launch_k(k_long<F_, false, false>, dim3(grid), dim3(LW_WG), lds, st, F);                    \
-	} while (0)
-		if (fmt == LW_OUT_I16_PLANAR)
-			LW_LAUNCH_MAIN(LW_OUT_I16_PLANAR);
-		else if (fmt == LW_OUT_I16_INTERLEAVED && F.ch == 2 && L.n_units == 1 && L.units[0].ch_b >= 0)
-			LW_LAUNCH_MAIN(LW_OUT_I16_ITL_STEREO);
-		else if (fmt == LW_OUT_I16_INTERLEAVED)
-			LW_LAUNCH_MAIN(LW_OUT_I16_INTERLEAVED);
-		else if (fmt == LW_OUT_F32_INTERLEAVED && F.ch == 2 && L.n_units == 1 && L.units[0].ch_b >= 0)
-			LW_LAUNCH_MAIN(LW_OUT_F32_ITL_STEREO);
-		else if (fmt == LW_OUT_F32_INTERLEAVED)
-			LW_LAUNCH_MAIN(LW_OUT_F32_INTERLEAVED);
-		else if (fmt == LW_OUT_F32_PLANAR)
-			LW_LAUNCH_MAIN(LW_OUT_F32_PLANAR);
-		else
-			return hipErrorInvalidValue;
-#undef LW_LAUNCH_MAIN
-	}
-	return hipSuccess;
+	// a 2-channel stream whose channels form ONE unit (a coupled pair) stores its interleaved frames whole: the stereo unit forms
+	const bool unit2 = F.ch == 2 && L.n_units == 1 && L.units[0].ch_b >= 0;
+	return lw_with_out_fmt(fmt, [&](auto f) {
+		constexpr int FS = f.value == LW_OUT_I16_INTERLEAVED ? LW_OUT_I16_ITL_STEREO
+			: f.value == LW_OUT_F32_INTERLEAVED ? LW_OUT_F32_ITL_STEREO : f.value;
+		return unit2 ? launch_long_main<FS>(L, F, grid, lds, st) : launch_long_main<f.value>(L, F, grid, lds, st);
+	});
 }
 
 // ---- k_mix: can this pair of launches run as one, and the launch itself
@@ -2253,6 +2175,25 @@ struct LwMixOrder {
 	}
 };
 
+// the short role's arguments of a mixed launch (k_mix, k_mix10) and the launch itself, launch(FS, M), in the LwMixOrder bracket
+template <class Launch>
+static hipError_t mix_launch(const LwDevTables &T, const LwBatchDev &B, const LwShortLaunch &LS, uint32_t *d_flags, uint32_t *d_err,
+		uint32_t spin, bool drop_flags, void *out, hipStream_t st, Launch &&launch)
+{
+	LwShortArgs FS{};
+	short_prepare(T, B, LS, out, FS);
+	LwMixArgs M{};
+	M.flags = d_flags;
+	M.err = d_err;
+	M.spin = spin ? spin : LW_MIX_SPIN;
+	M.drop_flags = drop_flags ? 1u : 0u;
+	LwMixOrder order;
+	const hipError_t oe = order.begin(st);
+	if (oe != hipSuccess)
+		return oe;
+	return order.end(launch(FS, M), st);
+}
+
 hipError_t lw_launch_mix(const LwDevTables &T, const LwBatchDev &B, const LwFastLaunch &LL, const LwShortLaunch &LS, uint32_t *d_flags,
 		uint32_t *d_err, uint32_t spin, bool drop_flags, void *out, int fmt, hipStream_t st)
 {
@@ -2261,28 +2202,10 @@ hipError_t lw_launch_mix(const LwDevTables &T, const LwBatchDev &B, const LwFast
 	const hipError_t pe = long_prepare(T, B, LL, out, st, F, grid);
 	if (pe != hipSuccess)
 		return pe;
-	LwShortArgs FS{};
-	short_prepare(T, B, LS, out, FS);
-	LwMixArgs M{};
-	M.flags = d_flags;
-	M.err = d_err;
-	M.spin = spin ? spin : LW_MIX_SPIN;
-	M.drop_flags = drop_flags ? 1u : 0u;
 	const size_t lds = LW_MIX_LDS_BYTES + LW_STAMP_LDS_EXTRA;
-	LwMixOrder order;
-	const hipError_t oe = order.begin(st);
-	if (oe != hipSuccess)
-		return oe;
-	auto launched = [&](hipError_t e) { return order.end(e, st); };
-	if (fmt == LW_OUT_I16_PLANAR)
-		return launched(lw_launch_k(k_mix<LW_OUT_I16_PLANAR>, dim3(grid), dim3(LW_WG), lds, st, F, FS, M));
-	if (fmt == LW_OUT_I16_INTERLEAVED)
-		return launched(lw_launch_k(k_mix<LW_OUT_I16_INTERLEAVED>, dim3(grid), dim3(LW_WG), lds, st, F, FS, M));
-	if (fmt == LW_OUT_F32_INTERLEAVED)
-		return launched(lw_launch_k(k_mix<LW_OUT_F32_INTERLEAVED>, dim3(grid), dim3(LW_WG), lds, st, F, FS, M));
-	if (fmt != LW_OUT_F32_PLANAR)
-		return launched(hipErrorInvalidValue);
-	return launched(lw_launch_k(k_mix<LW_OUT_F32_PLANAR>, dim3(grid), dim3(LW_WG), lds, st, F, FS, M));
+	return mix_launch(T, B, LS, d_flags, d_err, spin, drop_flags, out, st, [&](LwShortArgs &FS, LwMixArgs &M) {
+		return lw_with_out_fmt(fmt, [&](auto f) { return lw_launch_k(k_mix<f.value>, dim3(grid), dim3(LW_WG), lds, st, F, FS, M); });
+	});
 }
 
 // ---------------------------------------------------------------------------------------------

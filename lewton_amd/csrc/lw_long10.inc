@@ -764,26 +764,9 @@ hipError_t lw_launch_long10(const LwDevTables &T, const LwBatchDev &B, const LwF
 		return pe;
 	const dim3 block(LW_WG);
 	const size_t lds = L10_LDS_BYTES;
-	if (L.edge_mode || L.has_tdonly) { // (chosen per batch: an all-(1,1) batch keeps the plain kernel)
-		if (fmt == LW_OUT_I16_PLANAR)
-			return lw_launch_k(k_long10<LW_OUT_I16_PLANAR, false, true>, grid, block, lds, st, F);
-		if (fmt == LW_OUT_I16_INTERLEAVED)
-			return lw_launch_k(k_long10<LW_OUT_I16_INTERLEAVED, false, true>, grid, block, lds, st, F);
-		if (fmt == LW_OUT_F32_INTERLEAVED)
-			return lw_launch_k(k_long10<LW_OUT_F32_INTERLEAVED, false, true>, grid, block, lds, st, F);
-		if (fmt != LW_OUT_F32_PLANAR)
-			return hipErrorInvalidValue;
-		return lw_launch_k(k_long10<LW_OUT_F32_PLANAR, false, true>, grid, block, lds, st, F);
-	}
-	if (fmt == LW_OUT_I16_PLANAR)
-		return lw_launch_k(k_long10<LW_OUT_I16_PLANAR, false>, grid, block, lds, st, F);
-	if (fmt == LW_OUT_I16_INTERLEAVED)
-		return lw_launch_k(k_long10<LW_OUT_I16_INTERLEAVED, false>, grid, block, lds, st, F);
-	if (fmt == LW_OUT_F32_INTERLEAVED)
-		return lw_launch_k(k_long10<LW_OUT_F32_INTERLEAVED, false>, grid, block, lds, st, F);
-	if (fmt != LW_OUT_F32_PLANAR)
-		return hipErrorInvalidValue;
-	return lw_launch_k(k_long10<LW_OUT_F32_PLANAR, false>, grid, block, lds, st, F);
+	if (L.edge_mode || L.has_tdonly) // (chosen per batch: an all-(1,1) batch keeps the plain kernel)
+		return lw_with_out_fmt(fmt, [&](auto f) { return lw_launch_k(k_long10<f.value, false, true>, grid, block, lds, st, F); });
+	return lw_with_out_fmt(fmt, [&](auto f) { return lw_launch_k(k_long10<f.value, false>, grid, block, lds, st, F); });
 }
 
 // ---- k_mix10: can the two launches of a mixed batch run as one, and the launch itself (see lw_mix_applicable / lw_launch_mix)
@@ -810,35 +793,13 @@ hipError_t lw_launch_mix10(const LwDevTables &T, const LwBatchDev &B, const LwFa
 	const hipError_t pe = long10_prepare(T, B, LL, out, st, F, grid);
 	if (pe != hipSuccess)
 		return pe;
-	LwShortArgs FS{};
-	short_prepare(T, B, LS, out, FS);
-	LwMixArgs M{};
-	M.flags = d_flags;
-	M.err = d_err;
-	M.spin = spin ? spin : LW_MIX_SPIN;
-	M.drop_flags = drop_flags ? 1u : 0u;
-	LwMixOrder order; // ONE mixed grid per device at a time (see lw_launch_mix)
-	const hipError_t oe = order.begin(st);
-	if (oe != hipSuccess)
-		return oe;
 	const dim3 block(LW_WG);
-#define L10_MIX_LAUNCH(L_)                                                                                                             \
-	do {                                                                                                                               \
-		const size_t lds = L10Mix<L_>::LDS_BYTES;                                                                                      \
-		if (fmt == LW_OUT_I16_PLANAR)                                                                                                  \
-			return order.end(lw_launch_k(k_mix10<LW_OUT_I16_PLANAR, L_>, grid, block, lds, st, F, FS, M), st);                         \
-		if (fmt == LW_OUT_I16_INTERLEAVED)                                                                                             \
-			return order.end(lw_launch_k(k_mix10<LW_OUT_I16_INTERLEAVED, L_>, grid, block, lds, st, F, FS, M), st);                    \
-		if (fmt == LW_OUT_F32_INTERLEAVED)                                                                                             \
-			return order.end(lw_launch_k(k_mix10<LW_OUT_F32_INTERLEAVED, L_>, grid, block, lds, st, F, FS, M), st);                    \
-		if (fmt != LW_OUT_F32_PLANAR)                                                                                                  \
-			return order.end(hipErrorInvalidValue, st);                                                                                \
-		return order.end(lw_launch_k(k_mix10<LW_OUT_F32_PLANAR, L_>, grid, block, lds, st, F, FS, M), st);                             \
-	} while (0)
-	if (LS.lanes == 8)
-		L10_MIX_LAUNCH(8);
-	L10_MIX_LAUNCH(16);
-#undef L10_MIX_LAUNCH
+	return mix_launch(T, B, LS, d_flags, d_err, spin, drop_flags, out, st, [&](LwShortArgs &FS, LwMixArgs &M) {
+		const size_t lds8 = L10Mix<8>::LDS_BYTES, lds16 = L10Mix<16>::LDS_BYTES;
+		if (LS.lanes == 8)
+			return lw_with_out_fmt(fmt, [&](auto f) { return lw_launch_k(k_mix10<f.value, 8>, grid, block, lds8, st, F, FS, M); });
+		return lw_with_out_fmt(fmt, [&](auto f) { return lw_launch_k(k_mix10<f.value, 16>, grid, block, lds16, st, F, FS, M); });
+	});
 }
 
 static hipError_t long10_prepare(const LwDevTables &T, const LwBatchDev &B, const LwFastLaunch &L, void *out, hipStream_t st, LwFastArgs &F,
@@ -866,15 +827,16 @@ static hipError_t long10_prepare(const LwDevTables &T, const LwBatchDev &B, cons
 	const size_t lds = L10_LDS_BYTES;
 	static LwPerDeviceOnce once; // the kernels' 109 KB of dynamic LDS, opted in once per device
 	const hipError_t attr_err = once.run([] {
-		const void *fns[] = {(const void *)k_long10<LW_OUT_I16_PLANAR, false>, (const void *)k_long10<LW_OUT_I16_INTERLEAVED, false>,
-			(const void *)k_long10<LW_OUT_F32_PLANAR, false>, (const void *)k_long10<LW_OUT_I16_PLANAR, true>,
-			(const void *)k_long10<LW_OUT_I16_PLANAR, false, true>, (const void *)k_long10<LW_OUT_I16_INTERLEAVED, false, true>,
-			(const void *)k_long10<LW_OUT_F32_PLANAR, false, true>, (const void *)k_mix10<LW_OUT_I16_PLANAR, 8>,
-			(const void *)k_mix10<LW_OUT_I16_INTERLEAVED, 8>, (const void *)k_mix10<LW_OUT_F32_PLANAR, 8>,
+		// (per variant in the launchers' format order: the order in which the kernels are emitted into the code object)
+		const void *fns[] = {(const void *)k_long10<LW_OUT_I16_PLANAR, false, true>, (const void *)k_long10<LW_OUT_I16_INTERLEAVED, false, true>,
+			(const void *)k_long10<LW_OUT_F32_INTERLEAVED, false, true>, (const void *)k_long10<LW_OUT_F32_PLANAR, false, true>,
+			(const void *)k_long10<LW_OUT_I16_PLANAR, false>, (const void *)k_long10<LW_OUT_I16_INTERLEAVED, false>,
+			(const void *)k_long10<LW_OUT_F32_INTERLEAVED, false>, (const void *)k_long10<LW_OUT_F32_PLANAR, false>,
+			(const void *)k_mix10<LW_OUT_I16_PLANAR, 8>, (const void *)k_mix10<LW_OUT_I16_INTERLEAVED, 8>,
+			(const void *)k_mix10<LW_OUT_F32_INTERLEAVED, 8>, (const void *)k_mix10<LW_OUT_F32_PLANAR, 8>,
 			(const void *)k_mix10<LW_OUT_I16_PLANAR, 16>, (const void *)k_mix10<LW_OUT_I16_INTERLEAVED, 16>,
-			(const void *)k_mix10<LW_OUT_F32_PLANAR, 16>, (const void *)k_long10<LW_OUT_F32_INTERLEAVED, false>,
-			(const void *)k_long10<LW_OUT_F32_INTERLEAVED, false, true>, (const void *)k_mix10<LW_OUT_F32_INTERLEAVED, 8>,
-			(const void *)k_mix10<LW_OUT_F32_INTERLEAVED, 16>};
+			(const void *)k_mix10<LW_OUT_F32_INTERLEAVED, 16>, (const void *)k_mix10<LW_OUT_F32_PLANAR, 16>,
+			(const void *)k_long10<LW_OUT_I16_PLANAR, true>};
 		for (const void *f : fns) {
 			const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 			if (e != hipSuccess)

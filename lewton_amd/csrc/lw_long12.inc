@@ -293,40 +293,10 @@ __device__ __forceinline__ void ola_store12(const LwFastArgs &F, const char *img
 			ola_block<!lw_out_f32(FMT)>(R[2 * h + c2], ph.pp[2 * h + c2][0], ph.pp[2 * h + c2][1], w0, w1, O[c2]);
 		}
 		const uint32_t pos[4] = {256u * h + 4u * lane, 1020u - 256u * h - 4u * lane, 1024u + 256u * h + 4u * lane, 2044u - 256u * h - 4u * lane};
-		const float v[4][4] = {{O[0][3].x, O[0][2].x, O[1][3].x, O[1][2].x}, {O[1][1].x, O[1][0].x, O[0][1].x, O[0][0].x},
-			{O[0][0].y, O[0][1].y, O[1][0].y, O[1][1].y}, {O[1][2].y, O[1][3].y, O[0][2].y, O[0][3].y}};
+		const LwQuads q = pcm_quads(O);
 #pragma unroll
-		for (int g = 0; g < 4; g++) {
-			if (FMT == LW_OUT_F32_PLANAR) {
-				store16_wt(reinterpret_cast<float *>(F.out) + out_off + chn * mch + pos[g], float4_t{v[g][0], v[g][1], v[g][2], v[g][3]});
-			} else if (FMT == LW_OUT_F32_INTERLEAVED) {
-				float *o = reinterpret_cast<float *>(F.out) + out_off;
-				const uint32_t off = pos[g] * F.ch + chn;
-				o[off] = v[g][0];
-				o[off + F.ch] = v[g][1];
-				o[off + 2u * F.ch] = v[g][2];
-				o[off + 3u * F.ch] = v[g][3];
-			} else {
-				// samples.rs:92-103: x * 32768 (ola_block), truncate toward zero (v_cvt_i32_f32: saturating, NaN -> 0), clamp by the saturating pack
-				typedef short short2_t __attribute__((ext_vector_type(2)));
-				union {
-					short2_t s;
-					uint32_t u;
-				} a, b;
-				a.s = __builtin_amdgcn_cvt_pk_i16((int)v[g][0], (int)v[g][1]);
-				b.s = __builtin_amdgcn_cvt_pk_i16((int)v[g][2], (int)v[g][3]);
-				int16_t *o = reinterpret_cast<int16_t *>(F.out) + out_off;
-				if (FMT == LW_OUT_I16_PLANAR) {
-					store_pcm8(o + chn * mch + pos[g], a.u, b.u);
-				} else {
-					uint32_t off = pos[g] * F.ch + chn;
-					o[off] = a.s.x;
-					o[off + F.ch] = a.s.y;
-					o[off + 2u * F.ch] = b.s.x;
-					o[off + 3u * F.ch] = b.s.y;
-				}
-			}
-		}
+		for (int g = 0; g < 4; g++)
+			pcm_store4<FMT>(F.out, out_off, lw_out_itl(FMT) ? chn : chn * mch, pos[g], F.ch, q.v[g]);
 	}
 }
 
@@ -657,24 +627,7 @@ hipError_t lw_launch_long12(const LwDevTables &T, const LwBatchDev &B, const LwF
 	F.late_from = L12_PACE;
 	const uint32_t chunk = L.per_round * L.rounds;
 	const dim3 grid((L.n_items + chunk - 1) / chunk), block(LW_WG);
-	if (L.edge_mode || L.has_tdonly) { // (chosen per batch: an all-(1,1) batch keeps the plain kernel)
-		if (fmt == LW_OUT_I16_PLANAR)
-			return lw_launch_k(k_long12<LW_OUT_I16_PLANAR, false, true>, grid, block, lds, st, F);
-		if (fmt == LW_OUT_I16_INTERLEAVED)
-			return lw_launch_k(k_long12<LW_OUT_I16_INTERLEAVED, false, true>, grid, block, lds, st, F);
-		if (fmt == LW_OUT_F32_INTERLEAVED)
-			return lw_launch_k(k_long12<LW_OUT_F32_INTERLEAVED, false, true>, grid, block, lds, st, F);
-		if (fmt != LW_OUT_F32_PLANAR)
-			return hipErrorInvalidValue;
-		return lw_launch_k(k_long12<LW_OUT_F32_PLANAR, false, true>, grid, block, lds, st, F);
-	}
-	if (fmt == LW_OUT_I16_PLANAR)
-		return lw_launch_k(k_long12<LW_OUT_I16_PLANAR, false>, grid, block, lds, st, F);
-	if (fmt == LW_OUT_I16_INTERLEAVED)
-		return lw_launch_k(k_long12<LW_OUT_I16_INTERLEAVED, false>, grid, block, lds, st, F);
-	if (fmt == LW_OUT_F32_INTERLEAVED)
-		return lw_launch_k(k_long12<LW_OUT_F32_INTERLEAVED, false>, grid, block, lds, st, F);
-	if (fmt != LW_OUT_F32_PLANAR)
-		return hipErrorInvalidValue;
-	return lw_launch_k(k_long12<LW_OUT_F32_PLANAR, false>, grid, block, lds, st, F);
+	if (L.edge_mode || L.has_tdonly) // (chosen per batch: an all-(1,1) batch keeps the plain kernel)
+		return lw_with_out_fmt(fmt, [&](auto f) { return lw_launch_k(k_long12<f.value, false, true>, grid, block, lds, st, F); });
+	return lw_with_out_fmt(fmt, [&](auto f) { return lw_launch_k(k_long12<f.value, false>, grid, block, lds, st, F); });
 }
