@@ -218,6 +218,46 @@ int lw_batch_device_entropy(lw_batch *b, void *hip_stream);
 /* names of the kernels the last lw_batch_synth used, comma separated (introspection for tests/bench) */
 const char *lw_batch_last_kernels(const lw_batch *b);
 
+/* ---- stream-major rows ------------------------------------------------------------------------------------------------
+ * Everything above hands PCM back packet-major: a batch's output is a run of per-packet blocks ([ch][m] or [m][ch], at
+ * lw_packet_result.out_offset) in submission order, the packets of many streams mixed -- lewton's call shape (audio.rs:919).  A
+ * caller that decodes many WHOLE streams and goes on working on the GPU wants each stream's waveform as one contiguous array that
+ * stays there: d_rows = n_rows rows of ch * row_capacity elements in DEVICE memory,
+ *   [row][ch][row_capacity] for the planar formats, [row][row_capacity][ch] for the interleaved ones.
+ * lw_rows_synth = lw_batch_synth of `b` (entropy stage done and uploaded; same decoder and fmt as `r`) into a staging PCM buffer
+ * that `r` owns, then one more kernel on the same stream (k_rows, a segmented copy) that moves, for packet i of the batch
+ * (n == lw_batch_size(b)), the samples [skip, skip + kept) of every channel of its block to the positions [t0, t0 + kept) of row
+ * place[i].row, kept = min(keep, n_samples - skip).  `skip` is the leading part a seek drops (skip_samples_linear,
+ * inside_ogg.rs:244-283), `keep` the truncation of a stream's last packet to its final granule position (inside_ogg.rs:219-227);
+ * the caller keeps the per-row cursor (inside_ogg.rs:209-229 is its bookkeeping for one stream).  A packet whose status is not
+ * LW_OK, that has no samples (the first of a stream, audio.rs:1140-1152) or whose skip >= n_samples contributes nothing.
+ * Only the destination ranges are written: padding and other rows keep what the caller put there.  Destinations of different
+ * packets that overlap are the caller's business (the result is then one of them, unspecified which).
+ * Everything is decided on the host from lw_batch_results BEFORE anything is queued, so a refused call has written nothing:
+ *   LW_ERR_NULL_ARG        r or b NULL, place NULL with n > 0, d_rows NULL when anything would be copied
+ *   LW_ERR_STATE_MISMATCH  b belongs to another decoder or has another fmt than r
+ *   LW_ERR_CAPACITY        n != lw_batch_size(b), n > max_packets, a place with row >= n_rows (any packet) or
+ *                          t0 + kept > row_capacity
+ * Asynchronous, and idempotent like lw_batch_synth.  Calls on one object may be queued back to back without synchronising
+ * (on another stream than the call before, the new call's work is ordered behind it).  Device errors: lw_batch_device_status(b)
+ * keeps its contract -- after LW_ERR_DEVICE the row ranges the call wrote are void along with the batch's PCM.
+ * All destination offsets are 64-bit: a rows buffer may hold more than 2^32 elements. */
+typedef struct lw_rows lw_rows;
+typedef struct {
+	uint32_t row;   /* destination row */
+	uint32_t skip;  /* samples per channel dropped from the front of this packet's block */
+	uint32_t keep;  /* samples per channel kept behind skip; UINT32_MAX = all that remain */
+	uint32_t pad_;
+	uint64_t t0;    /* sample position in the row that receives the first kept sample */
+} lw_row_place;
+lw_rows *lw_rows_create(lw_decoder *d, size_t max_packets, int fmt, int *err);
+void lw_rows_destroy(lw_rows *r);
+int lw_rows_synth(lw_rows *r, lw_batch *b, const lw_row_place *place, size_t n, void *d_rows, size_t n_rows, size_t row_capacity,
+		void *hip_stream);
+/* introspection: the pieces (segments cut to at most 2048 elements, one GPU wave each) of the last call, and the elements they moved */
+size_t lw_rows_last_segments(const lw_rows *r);
+uint64_t lw_rows_last_copied_elems(const lw_rows *r);
+
 /* ---- staging ring (BASELINE north_star: "pinned hipMemcpyAsync staging ring so entropy decode of packet N+1 overlaps
  * GPU synthesis of packet N") ------------------------------------------------------------------------------------------
  * A ring of `slots` staging slots on the decoder's device; a slot = one batch object (pinned records + device mirror), a device

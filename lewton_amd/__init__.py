@@ -2,4 +2,4 @@
 
 Submodules import the HIP library lazily; `import lewton_amd.streamgen` works without it.
 """
-__all__ = ["audio", "header", "batch", "streamgen", "build"]
+__all__ = ["audio", "header", "batch", "rows", "streamgen", "build"]

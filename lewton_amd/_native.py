@@ -45,6 +45,10 @@ class PwrState(C.Structure):
     _fields_ = [("present", C.c_uint8), ("parity", C.c_uint8), ("len", C.c_uint32)]
 
 
+class RowPlace(C.Structure):
+    _fields_ = [("row", C.c_uint32), ("skip", C.c_uint32), ("keep", C.c_uint32), ("pad_", C.c_uint32), ("t0", C.c_uint64)]
+
+
 class OggPacket(C.Structure):
     _fields_ = [("data", C.c_void_p), ("len", C.c_size_t), ("stream_serial", C.c_uint32), ("absgp_page", C.c_uint64),
                 ("first_in_stream", C.c_uint8), ("last_in_stream", C.c_uint8), ("first_in_page", C.c_uint8),
@@ -127,6 +131,11 @@ SYMBOLS = {
     "lw_decoder_supports_device_entropy": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p)]),
     "lw_batch_set_entropy_on_device": (C.c_int, [C.c_void_p, C.c_int]),
     "lw_batch_device_entropy": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "lw_rows_create": (C.c_void_p, [C.c_void_p, C.c_size_t, C.c_int, intp]),
+    "lw_rows_destroy": (None, [C.c_void_p]),
+    "lw_rows_synth": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]),
+    "lw_rows_last_segments": (C.c_size_t, [C.c_void_p]),
+    "lw_rows_last_copied_elems": (C.c_uint64, [C.c_void_p]),
     "lw_ring_create": (C.c_void_p, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, intp]),
     "lw_ring_destroy": (None, [C.c_void_p]),
     "lw_ring_stage": (C.c_int, [C.c_void_p, C.POINTER(Packet), C.c_size_t, C.c_int]),

@@ -156,6 +156,19 @@ hipError_t lw_launch_entropy(const LwEntTables &T, const LwEntPacket *d_pk, cons
 		uint16_t *d_floor, float *d_res, uint32_t n, hipStream_t st);
 void lw_launch_generic_ola(const LwDevTables &T, const LwBatchDev &B, void *out, int fmt, hipStream_t st, bool include_fast);
 
+// Stream-major rows (k_rows, lw_kernels_rows.hip): a segmented copy of a batch's packet-major PCM (elements of elem_size = 2 or 4
+// bytes at d_src) into a rows buffer at d_dst.  A piece = `count` consecutive elements from element src_elem of the source to
+// element dst_elem of the destination (64-bit: a rows buffer may hold more than 2^32 elements); the host cuts segments into pieces
+// of at most LW_ROWS_PIECE elements (lw_rows.cpp), one wave moves one piece.  Nothing outside the pieces' destinations is written.
+struct LwRowSeg {
+	uint32_t src_elem;
+	uint32_t count;
+	uint64_t dst_elem;
+};
+static_assert(sizeof(LwRowSeg) == 16, "LwRowSeg is read as one 16-byte descriptor");
+#define LW_ROWS_PIECE 2048u
+hipError_t lw_launch_rows(const void *d_src, void *d_dst, const LwRowSeg *d_segs, uint32_t n_segs, int elem_size, hipStream_t st);
+
 // Specialised long-block path (lw_kernels_long.hip): optional halo pre-pass + main pass.
 struct LwFastLaunch;
 hipError_t lw_launch_long(const LwDevTables &T, const LwBatchDev &B, const LwFastLaunch &L, void *out, int fmt, hipStream_t st);

@@ -1,0 +1,439 @@
+"""Stream-major rows: whole streams decoded into ONE device tensor that stays on the GPU.
+
+Everything else in this package hands PCM back packet-major (a batch's output is a run of per-packet blocks, the packets of
+many streams mixed: lewton's call shape).  A caller that decodes many whole streams and goes on working on the GPU wants
+`[stream][channel][sample]`, padded to a common length:
+
+    pcm, lengths, errors = decode_streams(ident, setup, streams)          # streams: list of lists of audio-packet bytes
+    pcm, lengths, rate = decode_ogg_files(["a.ogg", "b.ogg", data])       # first logical stream of each file
+
+    rows = Rows(decoder, max_packets, "f32")                              # the layer below: lw_rows_* of include/lewton_amd.h
+    rows.synth(batch, places, tensor)                                     # lw_batch_synth + k_rows on torch's current stream
+
+`pcm` is a torch tensor on `cuda:device`: [B, C, T] for the planar formats, [B, T, C] for the interleaved ones, int16 or
+float32, zero beyond each row's length.  The synthesis kernels write a batch's blocks into a staging buffer as always; one more
+kernel behind them (k_rows, csrc/lw_kernels_rows.hip) moves the samples into their rows, so no sample crosses PCIe.
+torch is imported inside the functions, never at module import.
+"""
+import ctypes as C
+from collections import deque
+
+import numpy as np
+
+# The HIP library is loaded on first use, BEHIND torch: torch ships its own copy of the HIP runtime, and a process has to run on
+# one.  The dynamic loader lets liblewton_amd.so share the runtime torch has loaded, not the other way round, so a process that
+# uses this module imports torch (or calls into this module) before it imports any other lewton_amd module that loads the library.
+N = _FMT = AudioReadError = PreviousWindowRight = decoder_for = get_decoded_sample_count = None
+_one_runtime = None
+
+
+def _host():
+    """the library and the names of lewton_amd.audio this module uses (no torch needed: headers, demultiplexing, sample counts)"""
+    global N, _FMT, AudioReadError, PreviousWindowRight, decoder_for, get_decoded_sample_count
+    if N is None:
+        from . import _native, audio
+        _FMT, AudioReadError, PreviousWindowRight = audio._FMT, audio.AudioReadError, audio.PreviousWindowRight
+        decoder_for, get_decoded_sample_count = audio.decoder_for, audio.get_decoded_sample_count
+        N = _native
+    return N
+
+
+def _gpu():
+    """torch, then the library; refuses to go on when the two ended up on two copies of the HIP runtime (a stream or a device
+    pointer of one means nothing to the other)"""
+    global _one_runtime
+    import torch
+    _host()
+    if _one_runtime is None:
+        try:
+            with open("/proc/self/maps") as f:
+                copies = {ln.split()[-1] for ln in f if "libamdhip64" in ln}
+        except OSError:
+            copies = set()
+        _one_runtime = len(copies) <= 1
+    if not _one_runtime:
+        raise RuntimeError("lewton_amd.rows: the HIP library was loaded before torch, so this process holds two copies of the HIP "
+                           "runtime; import torch (or use lewton_amd.rows) before any other lewton_amd module")
+    return torch
+
+ALL = 0xFFFFFFFF  # lw_row_place.keep: all samples that remain behind skip
+PLACE_DTYPE = np.dtype([("row", "<u4"), ("skip", "<u4"), ("keep", "<u4"), ("pad_", "<u4"), ("t0", "<u8")])   # lw_row_place
+_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n_samples", "<u4"), ("out_offset", "<u8")])                    # lw_packet_result
+_NO_LIMIT = 1 << 62
+
+
+def places_array(places):
+    """lw_row_place array from an iterable of (row, skip, keep, t0); keep None = all that remain."""
+    if isinstance(places, np.ndarray) and places.dtype == PLACE_DTYPE:
+        return np.ascontiguousarray(places)
+    places = list(places)
+    arr = np.zeros(len(places), PLACE_DTYPE)
+    for i, (row, skip, keep, t0) in enumerate(places):
+        arr[i] = (row, skip, ALL if keep is None else keep, 0, t0)
+    return arr
+
+
+def torch_dtype(fmt):
+    torch = _gpu()
+    return torch.float32 if fmt in (N.FMT_F32_PLANAR, N.FMT_F32_INTERLEAVED) else torch.int16
+
+
+class Rows:
+    """lw_rows: the staging PCM buffer and the segment arrays behind lw_rows_synth, for batches of one decoder and format."""
+
+    def __init__(self, decoder, max_packets, samples="f32"):
+        _gpu()
+        err = C.c_int(0)
+        self.dec = decoder
+        self.fmt = _FMT[samples]
+        self.max_packets = max_packets
+        self._h = N.lw_rows_create(decoder._h, max_packets, self.fmt, C.byref(err))
+        if not self._h:
+            raise RuntimeError("lw_rows_create failed (%d): %s" % (err.value, N.device_error()))
+
+    create = classmethod(lambda cls, decoder, max_packets, samples="f32": cls(decoder, max_packets, samples))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            N.lw_rows_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        if N is not None and getattr(N, "lw_rows_destroy", None) is not None:  # not during interpreter shutdown
+            self.close()
+
+    def check_tensor(self, tensor):
+        """(n_rows, row_capacity) of a rows tensor, or ValueError: dtype, device, contiguity and shape against the format"""
+        ch = self.dec.ident.audio_channels
+        if tensor.dtype != torch_dtype(self.fmt):
+            raise ValueError("rows tensor is %s, the format needs %s" % (tensor.dtype, torch_dtype(self.fmt)))
+        if tensor.device.type != "cuda" or tensor.device.index != self.dec.device:
+            raise ValueError("rows tensor is on %s, the decoder on cuda:%d" % (tensor.device, self.dec.device))
+        if not tensor.is_contiguous():
+            raise ValueError("rows tensor is not contiguous")
+        if tensor.dim() != 3:
+            raise ValueError("rows tensor must have three dimensions, not %d" % tensor.dim())
+        if N.fmt_interleaved(self.fmt):
+            if tensor.shape[2] != ch:
+                raise ValueError("interleaved rows are [rows][samples][%d channels], not %s" % (ch, tuple(tensor.shape)))
+            return tensor.shape[0], tensor.shape[1]
+        if tensor.shape[1] != ch:
+            raise ValueError("planar rows are [rows][%d channels][samples], not %s" % (ch, tuple(tensor.shape)))
+        return tensor.shape[0], tensor.shape[2]
+
+    def synth(self, batch, places, tensor, stream=None):
+        """lw_rows_synth: the synthesis kernels of `batch` (entropy stage done, uploaded) and k_rows behind them.  places: one
+        (row, skip, keep, t0) per packet of the batch, or an array of PLACE_DTYPE.  stream: a hipStream_t value; None = torch's
+        current stream on the decoder's device.  Asynchronous."""
+        torch = _gpu()
+        n_rows, cap = self.check_tensor(tensor)
+        arr = places_array(places)
+        if stream is None:
+            stream = torch.cuda.current_stream(self.dec.device).cuda_stream or None
+        rc = N.lw_rows_synth(self._h, batch._h, arr.ctypes.data_as(C.c_void_p) if arr.size else None, arr.size,
+                             C.c_void_p(tensor.data_ptr()), n_rows, cap, stream)
+        if rc in (N.ERR_NULL_ARG, N.ERR_CAPACITY, N.ERR_STATE_MISMATCH):
+            raise ValueError("lw_rows_synth refused the call (%d)" % rc)
+        if rc:
+            raise RuntimeError("lw_rows_synth: %d %s" % (rc, N.device_error()))
+
+    @property
+    def last_segments(self):
+        return N.lw_rows_last_segments(self._h)
+
+    @property
+    def last_copied_elems(self):
+        return N.lw_rows_last_copied_elems(self._h)
+
+
+def _round_up(n, to):
+    to = max(1, int(to))
+    return (n + to - 1) // to * to
+
+
+def _sample_bound(ident, setup, packets, packet_keep=None):
+    """upper bound of the samples a stream yields (audio.rs:874-909): its first packet adds nothing, a packet that fails nothing"""
+    _host()
+    total = 0
+    for t, p in enumerate(packets):
+        if t == 0:
+            continue
+        try:
+            m = get_decoded_sample_count(ident, setup, p)
+        except AudioReadError:
+            continue
+        total += min(m, packet_keep[t]) if packet_keep and t in packet_keep else m
+    return total
+
+
+def _row_length(total, skip, keep):
+    return min(max(total - skip, 0), _NO_LIMIT if keep is None else keep)
+
+
+def plan_places(st_idx, m, decoded, skip, keep, row_of):
+    """The per-row cursor for one batch, vectorised: st_idx[i] = stream of packet i (a stream's packets in order), m[i] = the
+    samples it yields (0 for a failed packet), decoded[s] = samples stream s has yielded before this batch (updated in place),
+    skip[s] / keep[s] = leading samples of the stream to drop / cap on its row's length, row_of[s] = its row.  Returns the
+    lw_row_place array: packet i covers the stream positions [s0, s0 + m[i]), of which [skip, skip + keep) go to the row."""
+    n = len(st_idx)
+    # the stream position of every packet's first sample: the stream's cursor + the packets of it earlier in this batch
+    order = np.argsort(st_idx, kind="stable")
+    so, mo = st_idx[order], m[order]
+    cs = np.cumsum(mo) - mo
+    starts = np.r_[True, so[1:] != so[:-1]] if n else np.zeros(0, bool)
+    base = np.maximum.accumulate(np.where(starts, cs, 0)) if n else cs
+    s0 = np.empty(n, np.int64)
+    s0[order] = decoded[so] + cs - base
+    np.add.at(decoded, st_idx, m)
+    sk, kp = skip[st_idx], keep[st_idx]
+    lo = np.clip(sk - s0, 0, m)
+    hi = np.clip(np.minimum(sk + kp, _NO_LIMIT) - s0, 0, m)
+    kept = np.maximum(hi - lo, 0)
+    places = np.zeros(n, PLACE_DTYPE)
+    places["row"] = row_of[st_idx]
+    places["skip"] = lo
+    places["keep"] = kept
+    places["t0"] = np.where(kept > 0, s0 + lo - sk, 0)
+    return places
+
+
+def _decode_group(dec, streams, samples, max_packets, run, entropy_on_device, skip, keep, pcm, row_of, packet_keep):
+    """The streams of ONE decoder into the rows `row_of` of pcm, on torch's current stream.  Returns (samples decoded per stream
+    before skip / keep, errors as (stream, packet, code))."""
+    torch = _gpu()
+    from .batch import Batch
+    n_streams = len(streams)
+    total = sum(len(s) for s in streams)
+    decoded = np.zeros(n_streams, np.int64)
+    errors = []
+    if total == 0:
+        return decoded, errors
+    cap = max(1, min(int(max_packets), total))
+    run = max(1, int(run))
+    skip_a = np.asarray(skip, np.int64)
+    keep_a = np.asarray([_NO_LIMIT if k is None else k for k in keep], np.int64)
+    row_a = np.asarray(row_of, np.int64)
+    rows = Rows(dec, cap, samples)
+    # two batches in turn: the host stage of one runs while the GPU works on the other; a batch's pinned staging is
+    # rewritten only once its previous launches have completed
+    slots = [[Batch(dec, cap, samples), None] for _ in range(2 if total > cap else 1)]
+    try:
+        if entropy_on_device == "auto":
+            why = C.c_char_p()
+            entropy_on_device = bool(N.lw_decoder_supports_device_entropy(dec._h, C.byref(why)))
+        for bt, _ in slots:
+            if entropy_on_device and not bt.set_entropy_on_device(True):
+                raise ValueError("this stream's entropy stage cannot run on the device")
+        pws = [PreviousWindowRight() for _ in streams]
+        pos = [0] * n_streams
+        active = deque(s for s in range(n_streams) if streams[s])
+        k = 0
+
+        def finish(slot):
+            if slot[1] is not None:
+                slot[1].synchronize()
+                slot[1] = None
+                if slot[0].device_status():
+                    raise RuntimeError("device error in a batch: " + N.device_error())
+
+        while active:
+            # up to `run` consecutive packets of each stream in turn (a stream's window state moves once per run, not per packet)
+            items = []
+            while active and len(items) < cap:
+                s = active.popleft()
+                take = min(run, len(streams[s]) - pos[s], cap - len(items))
+                items += [(s, pos[s] + j) for j in range(take)]
+                pos[s] += take
+                if pos[s] < len(streams[s]):
+                    active.append(s)
+            slot = slots[k % len(slots)]
+            k += 1
+            finish(slot)
+            bt = slot[0]
+            bt.entropy_marshalled(bt.marshal([(streams[s][t], pws[s]) for s, t in items]))
+            n = len(items)
+            res = np.ctypeslib.as_array(C.cast(N.lw_batch_results(bt._h), C.POINTER(C.c_uint8)), shape=(n * 16,)).view(_RESULT_DTYPE)
+            st_idx = np.fromiter((s for s, _ in items), np.int64, n)
+            bad = np.nonzero(res["status"])[0]
+            errors += [(items[i][0], items[i][1], int(res["status"][i])) for i in bad]
+            m = np.where(res["status"] == 0, res["n_samples"], 0).astype(np.int64)
+            if packet_keep:
+                for i, (s, t) in enumerate(items):
+                    if packet_keep[s] and t in packet_keep[s]:
+                        m[i] = min(m[i], packet_keep[s][t])
+            places = plan_places(st_idx, m, decoded, skip_a, keep_a, row_a)
+            bt.upload(torch.cuda.current_stream(dec.device).cuda_stream or None)
+            rows.synth(bt, places, pcm)
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(dec.device))
+            slot[1] = ev
+        for slot in slots:
+            finish(slot)
+    finally:
+        torch.cuda.current_stream(dec.device).synchronize()
+        for bt, _ in slots:
+            bt.close()
+        rows.close()
+    return decoded, errors
+
+
+def _alloc(fmt, n_rows, ch, T, device, out):
+    torch = _gpu()
+    shape = (n_rows, T, ch) if N.fmt_interleaved(fmt) else (n_rows, ch, T)
+    if out is None:
+        return torch.zeros(shape, dtype=torch_dtype(fmt), device="cuda:%d" % device)
+    t_out = out.shape[1 if N.fmt_interleaved(fmt) else 2] if out.dim() == 3 else -1
+    want = shape[:1] + ((t_out, ch) if N.fmt_interleaved(fmt) else (ch, t_out))
+    if (out.dim() != 3 or tuple(out.shape) != want or t_out < T or out.dtype != torch_dtype(fmt) or not out.is_contiguous() or
+            out.device.type != "cuda" or out.device.index != device):
+        raise ValueError("out= must be a contiguous %s tensor on cuda:%d of shape %s with at least %d samples per row" % (
+            torch_dtype(fmt), device, shape, T))
+    out.zero_()
+    return out
+
+
+def _per_stream(v, n, what):
+    if v is None:
+        return [None] * n
+    v = list(v)
+    if len(v) != n:
+        raise ValueError("%s= needs one entry per stream" % what)
+    return v
+
+
+def decode_streams(ident, setup, streams, samples="f32", device=0, max_packets=16384, run=16, entropy_on_device="auto",
+                   skip=None, keep=None, pad_to=64, out=None):
+    """Whole streams of one (ident, setup) pair -> (pcm, lengths, errors).
+
+    streams: list of lists of audio-packet bytes (a stream's first packet only primes the window, audio.rs:1140-1152).
+    pcm: tensor on cuda:device, [B, C, T] (planar) or [B, T, C] (interleaved), zero beyond each row's length; T = the longest
+    row's upper bound (get_decoded_sample_count over its packets) rounded up to pad_to.  out=: a tensor of that shape (or more
+    samples per row) to fill instead; it is zeroed first.  lengths: int64 [B], a host tensor.  errors: (stream, packet, code)
+    of the packets whose status is not LW_OK -- they add no samples and decoding goes on (lw_ogg_stream_read_dec_packets).
+    skip[s] drops leading samples of stream s, keep[s] caps its length.  Batches of up to max_packets packets take up to `run`
+    consecutive packets of each stream in turn.  entropy_on_device: "auto" = k_entropy where the stream is eligible.  The GPU
+    work is queued on torch's current stream; the call returns when it has completed."""
+    import torch
+    _host()
+    fmt = _FMT[samples]
+    streams = [list(s) for s in streams]
+    B = len(streams)
+    skip = [0 if v is None else int(v) for v in _per_stream(skip, B, "skip")]
+    keep = _per_stream(keep, B, "keep")
+    bound = [_row_length(_sample_bound(ident, setup, s), skip[i], keep[i]) for i, s in enumerate(streams)]
+    T = _round_up(max(bound, default=0), pad_to)
+    with torch.cuda.device(device):
+        pcm = _alloc(fmt, B, ident.audio_channels, T, device, out)
+        decoded, errors = _decode_group(decoder_for(ident, setup, device), streams, samples, max_packets, run, entropy_on_device,
+                                        skip, keep, pcm, list(range(B)), None)
+    lengths = torch.tensor([_row_length(int(decoded[i]), skip[i], keep[i]) for i in range(B)], dtype=torch.int64)
+    return pcm, lengths, errors
+
+
+def _read_ogg(src, name):
+    """(ident packet, setup packet, audio packets, per-packet keep) of the first logical stream of one file, with lewton's own
+    bookkeeping (inside_ogg.rs:209-229): cur_absgp, and the packet with last_in_stream truncated to absgp_page - cur_absgp"""
+    _host()
+    from .ogg import PacketReader
+
+    def same_stream(pck, serial):
+        if pck.stream_serial() != serial:
+            raise ValueError("%s: more than one logical stream (chained or multiplexed file)" % name)
+        return pck
+
+    rdr = PacketReader(src)
+    try:
+        pck = rdr.read_packet_expected()
+        idp, serial = pck.data, pck.stream_serial()
+        same_stream(rdr.read_packet_expected(), serial)                 # comment header
+        stp = same_stream(rdr.read_packet_expected(), serial).data
+        rdr.delete_unread_packets()
+        packets = []
+        while True:
+            pck = rdr.read_packet()
+            if pck is None:
+                break
+            packets.append(same_stream(pck, serial))
+    finally:
+        rdr.close()
+    return idp, stp, packets
+
+
+def _ogg_keeps(ident, setup, packets, name):
+    _host()
+    from .inside_ogg import VorbisError
+    keeps, cur_absgp = {}, None
+    for t, pck in enumerate(packets):
+        try:
+            m = get_decoded_sample_count(ident, setup, pck.data) if t else 0
+        except AudioReadError as e:
+            raise ValueError("%s: audio packet %d: %s" % (name, t, VorbisError(e.code)))
+        if cur_absgp is not None and pck.last_in_stream():
+            target = max(pck.absgp_page() - cur_absgp, 0)
+            if target < m:
+                keeps[t] = m = target
+        if pck.last_in_page():
+            cur_absgp = pck.absgp_page()
+        elif cur_absgp is not None:
+            cur_absgp += m
+    return keeps
+
+
+def decode_ogg_files(sources, samples="f32", device=0, **kw):
+    """Ogg/Vorbis files (paths or bytes) -> (pcm, lengths, sample_rate); pcm and lengths as decode_streams returns them, row i =
+    the first logical stream of sources[i] = the concatenation of what OggStreamReader.read_dec_packet_generic returns for it
+    (the last packet truncated to the final granule position, inside_ogg.rs:219-227).  Files whose ident and setup packets are
+    byte-identical share one decoder.  ValueError naming the file: a chained or multiplexed file, a packet that does not decode,
+    files that differ in channel count or sample rate.  kw: max_packets, run, entropy_on_device, skip, keep, pad_to, out."""
+    import torch
+    _host()
+    from . import header as H
+    fmt = _FMT[samples]
+    sources = list(sources)
+    B = len(sources)
+    names = [s if isinstance(s, str) else "source %d" % i for i, s in enumerate(sources)]
+    skip = [0 if v is None else int(v) for v in _per_stream(kw.pop("skip", None), B, "skip")]
+    keep = _per_stream(kw.pop("keep", None), B, "keep")
+    pad_to, out = kw.pop("pad_to", 64), kw.pop("out", None)
+    max_packets, run = kw.pop("max_packets", 16384), kw.pop("run", 16)
+    entropy_on_device = kw.pop("entropy_on_device", "auto")
+    if kw:
+        raise TypeError("unexpected arguments: %s" % ", ".join(sorted(kw)))
+    groups = {}   # (ident packet, setup packet) -> [ident, setup, [file index], [packets], [packet keeps]]
+    shape = None
+    bound = [0] * B
+    for i, src in enumerate(sources):
+        idp, stp, packets = _read_ogg(src, names[i])
+        g = groups.get((idp, stp))
+        if g is None:
+            try:
+                ident = H.read_header_ident(idp)
+                setup = H.read_header_setup(stp, ident.audio_channels, (ident.blocksize_0, ident.blocksize_1))
+            except H.HeaderReadError as e:
+                raise ValueError("%s: %s" % (names[i], e))
+            g = groups[(idp, stp)] = [ident, setup, [], [], []]
+        ident, setup = g[0], g[1]
+        if shape is None:
+            shape = (ident.audio_channels, ident.audio_sample_rate)
+        elif shape != (ident.audio_channels, ident.audio_sample_rate):
+            raise ValueError("%s: %d channels at %d Hz, the files before it %d at %d Hz" % (
+                (names[i], ident.audio_channels, ident.audio_sample_rate) + shape))
+        keeps = _ogg_keeps(ident, setup, packets, names[i])
+        data = [p.data for p in packets]
+        g[2].append(i), g[3].append(data), g[4].append(keeps)
+        bound[i] = _row_length(_sample_bound(ident, setup, data, keeps), skip[i], keep[i])
+    if shape is None:
+        raise ValueError("no sources")
+    T = _round_up(max(bound), pad_to)
+    lengths = [0] * B
+    with torch.cuda.device(device):
+        pcm = _alloc(fmt, B, shape[0], T, device, out)
+        for ident, setup, idx, streams, keeps in groups.values():
+            decoded, errors = _decode_group(decoder_for(ident, setup, device), streams, samples, max_packets, run, entropy_on_device,
+                                            [skip[i] for i in idx], [keep[i] for i in idx], pcm, idx, keeps)
+            if errors:
+                s, t, code = errors[0]
+                raise ValueError("%s: audio packet %d does not decode (%d)" % (names[idx[s]], t, code))
+            for j, i in enumerate(idx):
+                lengths[i] = _row_length(int(decoded[j]), skip[i], keep[i])
+    return pcm, torch.tensor(lengths, dtype=torch.int64), shape[1]
