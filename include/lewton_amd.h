@@ -257,6 +257,35 @@ int lw_rows_synth(lw_rows *r, lw_batch *b, const lw_row_place *place, size_t n, 
 /* introspection: the pieces (segments cut to at most 2048 elements, one GPU wave each) of the last call, and the elements they moved */
 size_t lw_rows_last_segments(const lw_rows *r);
 uint64_t lw_rows_last_copied_elems(const lw_rows *r);
+/* lw_rows_synth through a channel matrix: select, reorder, downmix.  The rows buffer has mix->out_ch channels per row,
+ *   [row][out_ch][row_capacity] for the planar formats, [row][row_capacity][out_ch] for the interleaved ones,
+ * and destination sample t of output channel o is folded from the source samples x_c of the same packet position -- bit for bit:
+ *   - the input channels c are taken in ascending order; every c whose coef[o][c] compares equal to 0 (either sign) is skipped;
+ *   - a coefficient equal to 1.0f contributes x_c itself, with no multiply: a lone 1.0 is a bit copy, NaN payloads included;
+ *   - any other coefficient contributes coef * x_c: one f32 multiply, rounded;
+ *   - the first contribution is the accumulator, every later one is added with one rounded f32 add -- no fused multiply-add,
+ *     no reassociation, subnormals are kept;
+ *   - with no non-zero coefficient the result is +0.0 (i16 formats: 0).
+ * Every destination position [t0, t0 + kept) of all out_ch channels is written, nothing else.
+ * The f32 formats accept any matrix; the i16 formats accept routing matrices only (every row holds at most one non-zero
+ * coefficient, and that one equals 1.0): mixing quantised samples is not what anybody wants.
+ * Refusals, decided on the host before anything is queued like lw_rows_synth's, which all apply unchanged:
+ *   LW_ERR_NULL_ARG        mix or mix->coef NULL
+ *   LW_ERR_CAPACITY        out_ch == 0 or > LW_ROWS_MIX_MAX_OUT (t0 + kept > row_capacity as before)
+ *   LW_ERR_STATE_MISMATCH  in_ch is not the decoder's channel count
+ *   LW_ERR_UNSUPPORTED     a matrix that is not a routing matrix with an i16 format
+ * The coefficients are copied during the call.  Calls with different matrices may be queued back to back on one lw_rows, and may
+ * be mixed with lw_rows_synth calls.  lw_rows_last_copied_elems reports kept * out_ch summed over the call, lw_rows_last_segments
+ * the pieces (time ranges of one packet with all its channels, at most 512 positions, one GPU wave each).  Idempotence, device
+ * errors and 64-bit destination offsets as for lw_rows_synth. */
+#define LW_ROWS_MIX_MAX_OUT 8
+typedef struct {
+	uint32_t out_ch;    /* channels of the rows buffer, 1..LW_ROWS_MIX_MAX_OUT */
+	uint32_t in_ch;     /* must equal the decoder's channel count */
+	const float *coef;  /* out_ch * in_ch host floats, coef[o * in_ch + c] */
+} lw_row_mix;
+int lw_rows_synth_mix(lw_rows *r, lw_batch *b, const lw_row_place *place, size_t n, const lw_row_mix *mix,
+		void *d_rows, size_t n_rows, size_t row_capacity, void *hip_stream);
 
 /* ---- staging ring (BASELINE north_star: "pinned hipMemcpyAsync staging ring so entropy decode of packet N+1 overlaps
  * GPU synthesis of packet N") ------------------------------------------------------------------------------------------

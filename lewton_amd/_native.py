@@ -49,6 +49,10 @@ class RowPlace(C.Structure):
     _fields_ = [("row", C.c_uint32), ("skip", C.c_uint32), ("keep", C.c_uint32), ("pad_", C.c_uint32), ("t0", C.c_uint64)]
 
 
+class RowMix(C.Structure):
+    _fields_ = [("out_ch", C.c_uint32), ("in_ch", C.c_uint32), ("coef", C.c_void_p)]
+
+
 class OggPacket(C.Structure):
     _fields_ = [("data", C.c_void_p), ("len", C.c_size_t), ("stream_serial", C.c_uint32), ("absgp_page", C.c_uint64),
                 ("first_in_stream", C.c_uint8), ("last_in_stream", C.c_uint8), ("first_in_page", C.c_uint8),
@@ -134,6 +138,7 @@ SYMBOLS = {
     "lw_rows_create": (C.c_void_p, [C.c_void_p, C.c_size_t, C.c_int, intp]),
     "lw_rows_destroy": (None, [C.c_void_p]),
     "lw_rows_synth": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]),
+    "lw_rows_synth_mix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]),
     "lw_rows_last_segments": (C.c_size_t, [C.c_void_p]),
     "lw_rows_last_copied_elems": (C.c_uint64, [C.c_void_p]),
     "lw_ring_create": (C.c_void_p, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, intp]),

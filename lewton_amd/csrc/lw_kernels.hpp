@@ -169,6 +169,26 @@ static_assert(sizeof(LwRowSeg) == 16, "LwRowSeg is read as one 16-byte descripto
 #define LW_ROWS_PIECE 2048u
 hipError_t lw_launch_rows(const void *d_src, void *d_dst, const LwRowSeg *d_segs, uint32_t n_segs, int elem_size, hipStream_t st);
 
+// Stream-major rows through a channel matrix (k_rows_mix, lw_kernels_rows_mix.hip).  A piece = `count` sample positions of ONE
+// packet, all channels: input channel c of position p is element src_elem + c * src_stride + p of the source (planar;
+// src_stride = the packet's n_samples) or src_elem + p * in_ch + c (interleaved; src_stride = 1), output channel o of position p
+// is element dst_elem + o * row_capacity + p (planar) or dst_elem + p * out_ch + o (interleaved) of the destination, 64-bit.
+// The host cuts a packet's kept range into pieces of at most LW_ROWS_MIX_PIECE positions (lw_rows_mix.cpp), one wave takes one
+// piece.  d_coef: out_ch * in_ch floats in device memory, coef[o * in_ch + c]; the folding rule is the one of
+// include/lewton_amd.h (lw_rows_synth_mix).  Nothing outside the pieces' destinations is written.
+struct LwRowMixPiece {
+	uint32_t src_elem;
+	uint32_t src_stride;
+	uint32_t count;
+	uint32_t pad_;
+	uint64_t dst_elem;
+};
+static_assert(sizeof(LwRowMixPiece) == 24, "LwRowMixPiece is read as six dwords");
+#define LW_ROWS_MIX_PIECE 512u
+#define LW_ROWS_MIX_OUT 8u // == LW_ROWS_MIX_MAX_OUT of the public header
+hipError_t lw_launch_rows_mix(const void *d_src, void *d_dst, const LwRowMixPiece *d_pieces, uint32_t n_pieces, const float *d_coef,
+		uint32_t in_ch, uint32_t out_ch, uint64_t row_capacity, int elem_size, bool interleaved, hipStream_t st);
+
 // Specialised long-block path (lw_kernels_long.hip): optional halo pre-pass + main pass.
 struct LwFastLaunch;
 hipError_t lw_launch_long(const LwDevTables &T, const LwBatchDev &B, const LwFastLaunch &L, void *out, int fmt, hipStream_t st);

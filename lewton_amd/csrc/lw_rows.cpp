@@ -5,34 +5,10 @@
 // (a leading skip as in skip_samples_linear, inside_ogg.rs:244-283; the last packet's trim, inside_ogg.rs:219-227), the
 // refusals, and the cut of segments into pieces of at most LW_ROWS_PIECE elements.
 // Built on the public batch calls; no other source of the library calls into this one.
-#include "lw_internal.hpp"
+#include "lw_rows_internal.hpp"
 
 #include <algorithm>
 #include <cstring>
-
-#define LW_ROWS_SLOTS 3 // descriptor arrays in rotation: calls queued back to back do not wait for each other's kernels
-
-struct lw_rows_slot {
-	LwRowSeg *h_seg = nullptr, *d_seg = nullptr; // pinned / device, seg_cap descriptors each
-	hipEvent_t done = nullptr;                  // recorded behind the k_rows launch that read them
-	bool pending = false;
-};
-
-struct lw_rows {
-	lw_decoder *dec = nullptr;
-	size_t max_packets = 0;
-	int fmt = 0;
-	void *d_stage = nullptr; // the batch's packet-major PCM
-	size_t stage_elems = 0;
-	size_t seg_cap = 0;
-	lw_rows_slot slot[LW_ROWS_SLOTS];
-	unsigned next = 0;
-	int last = -1;              // slot of the most recent launch
-	void *last_stream = nullptr;
-	std::vector<LwRowSeg> plan; // the call's pieces, complete before anything is queued
-	size_t last_segments = 0;
-	uint64_t last_copied = 0;
-};
 
 // pieces one packet can be cut into: a first piece up to the destination's 16-byte boundary, whole pieces, a rest -- per
 // channel for the planar formats, once for the interleaved ones
@@ -89,6 +65,14 @@ void lw_rows_destroy(lw_rows *r)
 			(void)hipHostFree(s.h_seg);
 		if (s.d_seg)
 			(void)hipFree(s.d_seg);
+		if (s.done)
+			(void)hipEventDestroy(s.done);
+	}
+	for (auto &s : r->mix) { // (made by lw_rows_synth_mix, lw_rows_mix.cpp, on first use)
+		if (s.h)
+			(void)hipHostFree(s.h);
+		if (s.d)
+			(void)hipFree(s.d);
 		if (s.done)
 			(void)hipEventDestroy(s.done);
 	}
@@ -157,8 +141,8 @@ int lw_rows_synth(lw_rows *r, lw_batch *b, const lw_row_place *place, size_t n, 
 	if (int rc = lw_decoder_set_device(r->dec))
 		return rc;
 	hipStream_t st = (hipStream_t)hip_stream;
-	if (r->last >= 0 && r->last_stream != hip_stream) // another stream than last time: the staging buffer is still that call's
-		HIP_TRY(hipStreamWaitEvent(st, r->slot[r->last].done, 0));
+	if (r->last_done && r->last_stream != hip_stream) // another stream than last time: the staging buffer is still that call's
+		HIP_TRY(hipStreamWaitEvent(st, r->last_done, 0));
 	if (out_elems > r->stage_elems) {
 		HIP_TRY(hipDeviceSynchronize());
 		(void)hipFree(r->d_stage);
@@ -183,7 +167,7 @@ int lw_rows_synth(lw_rows *r, lw_batch *b, const lw_row_place *place, size_t n, 
 	HIP_TRY(lw_launch_rows(r->d_stage, d_rows, s.d_seg, (uint32_t)r->plan.size(), (int)es, st));
 	HIP_TRY(hipEventRecord(s.done, st));
 	s.pending = true;
-	r->last = (int)r->next;
+	r->last_done = s.done;
 	r->last_stream = hip_stream;
 	r->next = (r->next + 1) % LW_ROWS_SLOTS;
 	return LW_OK;

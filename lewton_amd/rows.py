@@ -9,10 +9,14 @@ many streams mixed: lewton's call shape).  A caller that decodes many whole stre
 
     rows = Rows(decoder, max_packets, "f32")                              # the layer below: lw_rows_* of include/lewton_amd.h
     rows.synth(batch, places, tensor)                                     # lw_batch_synth + k_rows on torch's current stream
+    rows.synth(batch, places, tensor, mix=mix_mono(2))                    # ... through a channel matrix (lw_rows_synth_mix)
 
 `pcm` is a torch tensor on `cuda:device`: [B, C, T] for the planar formats, [B, T, C] for the interleaved ones, int16 or
 float32, zero beyond each row's length.  The synthesis kernels write a batch's blocks into a staging buffer as always; one more
 kernel behind them (k_rows, csrc/lw_kernels_rows.hip) moves the samples into their rows, so no sample crosses PCIe.
+channels= / mix= puts a channel matrix [out_ch][in_ch] into that kernel (k_rows_mix): C becomes out_ch, every output channel is
+folded from the stream's channels by the rule of include/lewton_amd.h (lw_rows_synth_mix) -- mono downmix, a selection, WAVE
+channel order -- and files of different channel counts fill one tensor.
 torch is imported inside the functions, never at module import.
 """
 import ctypes as C
@@ -73,6 +77,66 @@ def places_array(places):
     return arr
 
 
+MIX_MAX_OUT = 8  # LW_ROWS_MIX_MAX_OUT
+# Vorbis I channel order (section 4.3.9 of the specification) -> WAVE mask order (FL FR FC LFE BL BR SL SR): source of output o
+_WAV_SOURCES = {1: (0,), 2: (0, 1), 3: (0, 2, 1), 4: (0, 1, 2, 3), 5: (0, 2, 1, 3, 4), 6: (0, 2, 1, 5, 3, 4),
+                7: (0, 2, 1, 6, 5, 3, 4), 8: (0, 2, 1, 7, 5, 6, 3, 4)}
+
+
+def mix_mono(in_ch):
+    """[1][in_ch] float32: the mean of the channels, 1 / in_ch each"""
+    if in_ch < 1:
+        raise ValueError("no channels")
+    return np.full((1, in_ch), np.float32(1) / np.float32(in_ch), np.float32)
+
+
+def mix_select(in_ch, sources):
+    """routing matrix [len(sources)][in_ch] float32: output channel o is a copy of input channel sources[o], silence for None"""
+    sources = list(sources)
+    m = np.zeros((len(sources), in_ch), np.float32)
+    for o, c in enumerate(sources):
+        if c is None:
+            continue
+        if not 0 <= c < in_ch:
+            raise ValueError("source channel %r of %d" % (c, in_ch))
+        m[o, c] = 1
+    return m
+
+
+def mix_wav_order(in_ch):
+    """routing matrix from Vorbis I channel order to WAVE mask order; ValueError for channel counts Vorbis I assigns no order to"""
+    if in_ch not in _WAV_SOURCES:
+        raise ValueError("no WAVE channel order for %d channels" % in_ch)
+    return mix_select(in_ch, _WAV_SOURCES[in_ch])
+
+
+def mix_array(mix, in_ch):
+    """a channel matrix as contiguous float32 [out_ch][in_ch], or ValueError"""
+    m = np.ascontiguousarray(mix, dtype=np.float32)
+    if m.ndim != 2 or m.shape[1] != in_ch or not 1 <= m.shape[0] <= MIX_MAX_OUT:
+        raise ValueError("a channel matrix is [1..%d output channels][%d input channels], not %s" % (MIX_MAX_OUT, in_ch, m.shape))
+    return m
+
+
+def mix_is_routing(m):
+    """every row holds at most one non-zero coefficient, and that one is 1.0 (what the i16 formats accept)"""
+    return bool(((m != 0).sum(1) <= 1).all() and ((m == 0) | (m == 1)).all())
+
+
+def _named_mix(channels, in_ch, fmt):
+    """channels= of decode_streams: "mono" or a matrix -> float32 [out_ch][in_ch], checked against the format"""
+    _host()
+    m = mix_mono(in_ch) if isinstance(channels, str) and channels == "mono" else \
+        mix_wav_order(in_ch) if isinstance(channels, str) and channels == "wav" else None
+    if m is None:
+        if isinstance(channels, str):
+            raise ValueError("channels=%r: \"mono\", \"wav\" or a matrix" % channels)
+        m = mix_array(channels, in_ch)
+    if fmt in (N.FMT_I16_PLANAR, N.FMT_I16_INTERLEAVED) and not mix_is_routing(m):
+        raise ValueError("the i16 formats take routing matrices only (one coefficient 1.0 per row at most), not %s" % m.tolist())
+    return m
+
+
 def torch_dtype(fmt):
     torch = _gpu()
     return torch.float32 if fmt in (N.FMT_F32_PLANAR, N.FMT_F32_INTERLEAVED) else torch.int16
@@ -102,9 +166,10 @@ class Rows:
         if N is not None and getattr(N, "lw_rows_destroy", None) is not None:  # not during interpreter shutdown
             self.close()
 
-    def check_tensor(self, tensor):
-        """(n_rows, row_capacity) of a rows tensor, or ValueError: dtype, device, contiguity and shape against the format"""
-        ch = self.dec.ident.audio_channels
+    def check_tensor(self, tensor, out_ch=None):
+        """(n_rows, row_capacity) of a rows tensor, or ValueError: dtype, device, contiguity and shape against the format;
+        out_ch: the channels of the rows when a matrix is used (None: the decoder's)"""
+        ch = self.dec.ident.audio_channels if out_ch is None else out_ch
         if tensor.dtype != torch_dtype(self.fmt):
             raise ValueError("rows tensor is %s, the format needs %s" % (tensor.dtype, torch_dtype(self.fmt)))
         if tensor.device.type != "cuda" or tensor.device.index != self.dec.device:
@@ -121,21 +186,30 @@ class Rows:
             raise ValueError("planar rows are [rows][%d channels][samples], not %s" % (ch, tuple(tensor.shape)))
         return tensor.shape[0], tensor.shape[2]
 
-    def synth(self, batch, places, tensor, stream=None):
+    def synth(self, batch, places, tensor, stream=None, mix=None):
         """lw_rows_synth: the synthesis kernels of `batch` (entropy stage done, uploaded) and k_rows behind them.  places: one
         (row, skip, keep, t0) per packet of the batch, or an array of PLACE_DTYPE.  stream: a hipStream_t value; None = torch's
-        current stream on the decoder's device.  Asynchronous."""
+        current stream on the decoder's device.  mix: a channel matrix, array-like [out_ch][in_ch] (lw_rows_synth_mix, k_rows_mix
+        in place of k_rows); the tensor then has out_ch channels.  Asynchronous."""
         torch = _gpu()
-        n_rows, cap = self.check_tensor(tensor)
+        if mix is not None:
+            mix = mix_array(mix, self.dec.ident.audio_channels)
+        n_rows, cap = self.check_tensor(tensor, None if mix is None else mix.shape[0])
         arr = places_array(places)
         if stream is None:
             stream = torch.cuda.current_stream(self.dec.device).cuda_stream or None
-        rc = N.lw_rows_synth(self._h, batch._h, arr.ctypes.data_as(C.c_void_p) if arr.size else None, arr.size,
-                             C.c_void_p(tensor.data_ptr()), n_rows, cap, stream)
-        if rc in (N.ERR_NULL_ARG, N.ERR_CAPACITY, N.ERR_STATE_MISMATCH):
-            raise ValueError("lw_rows_synth refused the call (%d)" % rc)
+        pl = arr.ctypes.data_as(C.c_void_p) if arr.size else None
+        if mix is None:
+            name = "lw_rows_synth"
+            rc = N.lw_rows_synth(self._h, batch._h, pl, arr.size, C.c_void_p(tensor.data_ptr()), n_rows, cap, stream)
+        else:
+            name = "lw_rows_synth_mix"
+            m = N.RowMix(mix.shape[0], mix.shape[1], mix.ctypes.data_as(C.c_void_p))      # (the coefficients are copied by the call)
+            rc = N.lw_rows_synth_mix(self._h, batch._h, pl, arr.size, C.byref(m), C.c_void_p(tensor.data_ptr()), n_rows, cap, stream)
+        if rc in (N.ERR_NULL_ARG, N.ERR_CAPACITY, N.ERR_STATE_MISMATCH, N.ERR_UNSUPPORTED):
+            raise ValueError("%s refused the call (%d)" % (name, rc))
         if rc:
-            raise RuntimeError("lw_rows_synth: %d %s" % (rc, N.device_error()))
+            raise RuntimeError("%s: %d %s" % (name, rc, N.device_error()))
 
     @property
     def last_segments(self):
@@ -197,9 +271,9 @@ def plan_places(st_idx, m, decoded, skip, keep, row_of):
     return places
 
 
-def _decode_group(dec, streams, samples, max_packets, run, entropy_on_device, skip, keep, pcm, row_of, packet_keep):
-    """The streams of ONE decoder into the rows `row_of` of pcm, on torch's current stream.  Returns (samples decoded per stream
-    before skip / keep, errors as (stream, packet, code))."""
+def _decode_group(dec, streams, samples, max_packets, run, entropy_on_device, skip, keep, pcm, row_of, packet_keep, mix=None):
+    """The streams of ONE decoder into the rows `row_of` of pcm, on torch's current stream, through the channel matrix `mix` if
+    there is one.  Returns (samples decoded per stream before skip / keep, errors as (stream, packet, code))."""
     torch = _gpu()
     from .batch import Batch
     n_streams = len(streams)
@@ -263,7 +337,7 @@ def _decode_group(dec, streams, samples, max_packets, run, entropy_on_device, sk
                         m[i] = min(m[i], packet_keep[s][t])
             places = plan_places(st_idx, m, decoded, skip_a, keep_a, row_a)
             bt.upload(torch.cuda.current_stream(dec.device).cuda_stream or None)
-            rows.synth(bt, places, pcm)
+            rows.synth(bt, places, pcm, mix=mix)
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream(dec.device))
             slot[1] = ev
@@ -302,7 +376,7 @@ def _per_stream(v, n, what):
 
 
 def decode_streams(ident, setup, streams, samples="f32", device=0, max_packets=16384, run=16, entropy_on_device="auto",
-                   skip=None, keep=None, pad_to=64, out=None):
+                   skip=None, keep=None, pad_to=64, out=None, channels=None):
     """Whole streams of one (ident, setup) pair -> (pcm, lengths, errors).
 
     streams: list of lists of audio-packet bytes (a stream's first packet only primes the window, audio.rs:1140-1152).
@@ -311,11 +385,14 @@ def decode_streams(ident, setup, streams, samples="f32", device=0, max_packets=1
     samples per row) to fill instead; it is zeroed first.  lengths: int64 [B], a host tensor.  errors: (stream, packet, code)
     of the packets whose status is not LW_OK -- they add no samples and decoding goes on (lw_ogg_stream_read_dec_packets).
     skip[s] drops leading samples of stream s, keep[s] caps its length.  Batches of up to max_packets packets take up to `run`
-    consecutive packets of each stream in turn.  entropy_on_device: "auto" = k_entropy where the stream is eligible.  The GPU
+    consecutive packets of each stream in turn.  entropy_on_device: "auto" = k_entropy where the stream is eligible.
+    channels: None = the stream's own channels; "mono" = mix_mono; anything else a channel matrix [out_ch][in_ch] -- C is then
+    out_ch, and out= is checked against it (i16 formats: routing matrices only, ValueError before anything is decoded).  The GPU
     work is queued on torch's current stream; the call returns when it has completed."""
     import torch
     _host()
     fmt = _FMT[samples]
+    mix = None if channels is None else _named_mix(channels, ident.audio_channels, fmt)
     streams = [list(s) for s in streams]
     B = len(streams)
     skip = [0 if v is None else int(v) for v in _per_stream(skip, B, "skip")]
@@ -323,9 +400,9 @@ def decode_streams(ident, setup, streams, samples="f32", device=0, max_packets=1
     bound = [_row_length(_sample_bound(ident, setup, s), skip[i], keep[i]) for i, s in enumerate(streams)]
     T = _round_up(max(bound, default=0), pad_to)
     with torch.cuda.device(device):
-        pcm = _alloc(fmt, B, ident.audio_channels, T, device, out)
+        pcm = _alloc(fmt, B, ident.audio_channels if mix is None else mix.shape[0], T, device, out)
         decoded, errors = _decode_group(decoder_for(ident, setup, device), streams, samples, max_packets, run, entropy_on_device,
-                                        skip, keep, pcm, list(range(B)), None)
+                                        skip, keep, pcm, list(range(B)), None, mix)
     lengths = torch.tensor([_row_length(int(decoded[i]), skip[i], keep[i]) for i in range(B)], dtype=torch.int64)
     return pcm, lengths, errors
 
@@ -379,12 +456,27 @@ def _ogg_keeps(ident, setup, packets, name):
     return keeps
 
 
+def _group_mix(channels, in_ch, fmt):
+    """channels= of decode_ogg_files for a decoder group of in_ch channels"""
+    if isinstance(channels, dict):
+        if in_ch not in channels:
+            raise ValueError("channels= has no matrix for %d channels" % in_ch)
+        channels = channels[in_ch]
+    elif callable(channels):
+        channels = channels(in_ch)
+    return _named_mix(channels, in_ch, fmt)
+
+
 def decode_ogg_files(sources, samples="f32", device=0, **kw):
     """Ogg/Vorbis files (paths or bytes) -> (pcm, lengths, sample_rate); pcm and lengths as decode_streams returns them, row i =
     the first logical stream of sources[i] = the concatenation of what OggStreamReader.read_dec_packet_generic returns for it
     (the last packet truncated to the final granule position, inside_ogg.rs:219-227).  Files whose ident and setup packets are
     byte-identical share one decoder.  ValueError naming the file: a chained or multiplexed file, a packet that does not decode,
-    files that differ in channel count or sample rate.  kw: max_packets, run, entropy_on_device, skip, keep, pad_to, out."""
+    files that differ in channel count or sample rate.  kw: max_packets, run, entropy_on_device, skip, keep, pad_to, out, channels.
+    channels: None = the files' own channels.  Otherwise every decoder group goes through the matrix for ITS channel count, and
+    files of different channel counts fill one tensor as long as every matrix has the same out_ch (ValueError naming the file
+    otherwise; sample rates must still agree): "mono" = mix_mono, "wav" = mix_wav_order, a dict {in_ch: matrix}, or a callable
+    in_ch -> matrix.  i16 formats: routing matrices only, ValueError before anything is decoded."""
     import torch
     _host()
     from . import header as H
@@ -397,6 +489,7 @@ def decode_ogg_files(sources, samples="f32", device=0, **kw):
     pad_to, out = kw.pop("pad_to", 64), kw.pop("out", None)
     max_packets, run = kw.pop("max_packets", 16384), kw.pop("run", 16)
     entropy_on_device = kw.pop("entropy_on_device", "auto")
+    channels = kw.pop("channels", None)
     if kw:
         raise TypeError("unexpected arguments: %s" % ", ".join(sorted(kw)))
     groups = {}   # (ident packet, setup packet) -> [ident, setup, [file index], [packets], [packet keeps]]
@@ -411,9 +504,23 @@ def decode_ogg_files(sources, samples="f32", device=0, **kw):
                 setup = H.read_header_setup(stp, ident.audio_channels, (ident.blocksize_0, ident.blocksize_1))
             except H.HeaderReadError as e:
                 raise ValueError("%s: %s" % (names[i], e))
-            g = groups[(idp, stp)] = [ident, setup, [], [], []]
+            g = groups[(idp, stp)] = [ident, setup, [], [], [], None]
+            if channels is not None:
+                try:
+                    g[5] = _group_mix(channels, ident.audio_channels, fmt)
+                except (ValueError, KeyError) as e:
+                    raise ValueError("%s: %s" % (names[i], e))
         ident, setup = g[0], g[1]
-        if shape is None:
+        if channels is not None:
+            # the channel count that has to agree is the matrices' out_ch; the files' own may differ
+            if shape is None:
+                shape = (g[5].shape[0], ident.audio_sample_rate)
+            elif shape[0] != g[5].shape[0]:
+                raise ValueError("%s: its channel matrix has %d output channels, those of the files before it %d" % (
+                    names[i], g[5].shape[0], shape[0]))
+            elif shape[1] != ident.audio_sample_rate:
+                raise ValueError("%s: %d Hz, the files before it %d Hz" % (names[i], ident.audio_sample_rate, shape[1]))
+        elif shape is None:
             shape = (ident.audio_channels, ident.audio_sample_rate)
         elif shape != (ident.audio_channels, ident.audio_sample_rate):
             raise ValueError("%s: %d channels at %d Hz, the files before it %d at %d Hz" % (
@@ -428,9 +535,9 @@ def decode_ogg_files(sources, samples="f32", device=0, **kw):
     lengths = [0] * B
     with torch.cuda.device(device):
         pcm = _alloc(fmt, B, shape[0], T, device, out)
-        for ident, setup, idx, streams, keeps in groups.values():
+        for ident, setup, idx, streams, keeps, mix in groups.values():
             decoded, errors = _decode_group(decoder_for(ident, setup, device), streams, samples, max_packets, run, entropy_on_device,
-                                            [skip[i] for i in idx], [keep[i] for i in idx], pcm, idx, keeps)
+                                            [skip[i] for i in idx], [keep[i] for i in idx], pcm, idx, keeps, mix)
             if errors:
                 s, t, code = errors[0]
                 raise ValueError("%s: audio packet %d does not decode (%d)" % (names[idx[s]], t, code))
