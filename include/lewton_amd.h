@@ -287,6 +287,62 @@ typedef struct {
 int lw_rows_synth_mix(lw_rows *r, lw_batch *b, const lw_row_place *place, size_t n, const lw_row_mix *mix,
 		void *d_rows, size_t n_rows, size_t row_capacity, void *hip_stream);
 
+/* ---- resampling rows ---------------------------------------------------------------------------------------------------
+ * Finished rows at one sample rate -> rows at another, on the GPU, as a pass of its own (k_resample): the synthesis kernels and
+ * the assemblers above are not involved.  Source and destination are rows buffers of the two f32 formats, `ch` channels each,
+ *   [row][ch][capacity] (LW_FMT_F32_PLANAR) or [row][capacity][ch] (LW_FMT_F32_INTERLEAVED),
+ * with their own capacities.  The filter is a windowed sinc in polyphase form, and it is a contract on BITS:
+ *
+ * A resampler is made from (in_rate, out_rate, zeros, rolloff, window, beta).  g = gcd(in_rate, out_rate), orig = in_rate / g,
+ * new = out_rate / g.
+ *   s = rolloff * min(1, new / orig)      the cut-off as a fraction of the input Nyquist
+ *   W = ceil(zeros / s)                   the half width in input samples
+ *   K = 2 W + 2                           taps per phase; there are `new` phases
+ * Tap k of phase ph, evaluated in double and rounded ONCE to f32:
+ *   t = (k - W) - ph / new,  u = s * t,  h[ph][k] = s * sinc(u) * w(u) for |u| < zeros, else 0
+ *   sinc(u) = sin(pi u) / (pi u), sinc(0) = 1
+ *   w(u) = cos^2(pi u / (2 zeros))                               LW_RESAMPLE_HANN
+ *   w(u) = I0(beta * sqrt(1 - (u / zeros)^2)) / I0(beta)         LW_RESAMPLE_KAISER; I0 by its power series in double until a
+ *                                                                term no longer changes the sum (0 <= beta < 700)
+ * The parameters most users know from other toolkits: hann, zeros 6, rolloff 0.99.  A good-quality choice: kaiser, zeros 16,
+ * beta 14.769656459379492, rolloff 0.99.
+ * A row of len input samples yields out_len = ceil(len * new / orig) output samples.  Output sample n of a row and channel:
+ *   base = floor(n * orig / new), ph = (n * orig) mod new      (64-bit integers)
+ *   y[n] = the fold over k = 0 .. K - 1 in ascending order of h[ph][k] * x[base - W + k]: every term one rounded f32 multiply;
+ *   the first term is the accumulator, every later one is added with one rounded f32 add.  No fused multiply-add, subnormals kept.
+ *   x[i] = +0.0 for i < 0 and for i >= len -- len, not the capacity: what the source holds between len and its capacity never
+ *   reaches the output, and no byte beyond the capacity is read.  Terms with x = +0.0 take part like any other, so the sign of a
+ *   zero result is defined.
+ * Nothing outside [0, out_len) of a destination row and channel is written.  orig == new is a copy of the bits of [0, len).
+ *
+ * lw_resample_rows: source row i (len[i] samples per channel) goes to destination row dst_row[i] (NULL: row i).  len and dst_row
+ * are HOST arrays, copied during the call.  Asynchronous on hip_stream; calls on one object may be queued back to back.
+ * Overlapping source and destination buffers are the caller's error (the result is then unspecified).  Refusals, decided on
+ * the host before anything is queued, so a refused call has written nothing:
+ *   LW_ERR_NULL_ARG     rs NULL, len NULL with rows, d_src / d_dst NULL with samples to read / to write
+ *   LW_ERR_UNSUPPORTED  (create) a rate of 0, zeros == 0, rolloff outside (0, 1], an unknown window, a kaiser beta outside
+ *                       [0, 700), new * K > LW_RESAMPLE_MAX_TAPS;  (rows) an i16 format
+ *   LW_ERR_CAPACITY     len[i] > src_capacity, out_len(len[i]) > dst_capacity, dst_row[i] >= n_dst_rows, two source rows for
+ *                       one destination row, ch == 0 or > 255
+ * (Of the standard rates from 8 to 192 kHz every pair fits LW_RESAMPLE_MAX_TAPS with hann / 6 -- at most 40 960 taps -- and
+ * with kaiser / 16 every pair but 11 025 <-> 192 000 Hz; the pairs of 8, 16, 22.05, 32, 44.1 and 48 kHz need 23 040 at most.) */
+typedef struct lw_resampler lw_resampler;
+enum { LW_RESAMPLE_HANN = 0, LW_RESAMPLE_KAISER = 1 };
+#define LW_RESAMPLE_MAX_TAPS 65536
+lw_resampler *lw_resampler_create(int device, uint32_t in_rate, uint32_t out_rate, uint32_t zeros, double rolloff, int window, double beta,
+		int *err);
+void lw_resampler_destroy(lw_resampler *rs);
+void lw_resampler_geometry(const lw_resampler *rs, uint32_t *orig, uint32_t *new_, uint32_t *half_width, uint32_t *taps_per_phase);
+size_t lw_resampler_taps(const lw_resampler *rs, float *dst); /* [new][K]; returns new * K, dst NULL = size query */
+uint64_t lw_resampler_out_len(const lw_resampler *rs, uint64_t len);
+int lw_resample_rows(lw_resampler *rs, int fmt, uint32_t ch, const void *d_src, size_t n_src_rows, size_t src_capacity,
+		const uint64_t *len, const uint32_t *dst_row, void *d_dst, size_t n_dst_rows, size_t dst_capacity, void *hip_stream);
+/* introspection: where the last queued call read taps and samples from -- 0 = table and input span in LDS, 1 = taps from
+ * global memory (the table does not fit the workgroup's LDS), 2 = both from global memory, 3 = orig == new, the copy; -1 = no
+ * call yet.  lw_resampler_set_taps_in_lds(rs, 0) sends a table that would fit through route 1 (same bits; for tests). */
+int lw_resampler_last_route(const lw_resampler *rs);
+int lw_resampler_set_taps_in_lds(lw_resampler *rs, int on);
+
 /* ---- staging ring (BASELINE north_star: "pinned hipMemcpyAsync staging ring so entropy decode of packet N+1 overlaps
  * GPU synthesis of packet N") ------------------------------------------------------------------------------------------
  * A ring of `slots` staging slots on the decoder's device; a slot = one batch object (pinned records + device mirror), a device

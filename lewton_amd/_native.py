@@ -141,6 +141,15 @@ SYMBOLS = {
     "lw_rows_synth_mix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]),
     "lw_rows_last_segments": (C.c_size_t, [C.c_void_p]),
     "lw_rows_last_copied_elems": (C.c_uint64, [C.c_void_p]),
+    "lw_resampler_create": (C.c_void_p, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_int, C.c_double, intp]),
+    "lw_resampler_destroy": (None, [C.c_void_p]),
+    "lw_resampler_geometry": (None, [C.c_void_p] + [C.POINTER(C.c_uint32)] * 4),
+    "lw_resampler_taps": (C.c_size_t, [C.c_void_p, C.c_void_p]),
+    "lw_resampler_out_len": (C.c_uint64, [C.c_void_p, C.c_uint64]),
+    "lw_resample_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_size_t, C.c_size_t, C.c_void_p]),
+    "lw_resampler_last_route": (C.c_int, [C.c_void_p]),
+    "lw_resampler_set_taps_in_lds": (C.c_int, [C.c_void_p, C.c_int]),
     "lw_ring_create": (C.c_void_p, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, intp]),
     "lw_ring_destroy": (None, [C.c_void_p]),
     "lw_ring_stage": (C.c_int, [C.c_void_p, C.POINTER(Packet), C.c_size_t, C.c_int]),
@@ -220,6 +229,7 @@ ERR_NULL_ARG, ERR_DEVICE, ERR_CAPACITY, ERR_STATE_MISMATCH, ERR_UNSUPPORTED = 32
 OGG_EOF, OGG_NO_CAPTURE_PATTERN, OGG_INVALID_STREAM_STRUCT_VER, OGG_HASH_MISMATCH = 48, 49, 50, 51
 OGG_READ_ERROR, OGG_INVALID_DATA = 52, 53
 FMT_I16_PLANAR, FMT_I16_INTERLEAVED, FMT_F32_PLANAR, FMT_F32_INTERLEAVED = 0, 1, 2, 3
+RESAMPLE_HANN, RESAMPLE_KAISER, RESAMPLE_MAX_TAPS = 0, 1, 65536
 
 
 def fmt_dtype(fmt):

@@ -1,0 +1,272 @@
+// Row resampler (lw_resampler_*, lw_resample_rows; include/lewton_amd.h "resampling rows"): finished rows of f32 PCM
+// ([row][ch][sample] or [row][sample][ch] in device memory) resampled by a rational ratio into another rows buffer, by a windowed-
+// sinc polyphase filter whose taps and fold order are a contract on bits.  The taps are evaluated here in double and rounded once;
+// everything about a call is decided here on the host before anything is queued (the refusals, the output lengths, the launch
+// geometry); k_resample (lw_kernels_resample.hip) does the fold.  The call's per-row records travel through pinned arrays in
+// rotation, each guarded by an event, as lw_rows' descriptors do.  Nothing else in the library calls into this file.
+#include "lw_internal.hpp"
+#include "lw_resample.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <numeric>
+
+#define LW_RS_SLOTS 3 // record arrays in rotation: calls queued back to back do not wait for each other's kernels
+
+struct lw_rs_slot {
+	LwResampleRow *h = nullptr, *d = nullptr; // pinned / device, cap records each
+	size_t cap = 0;
+	hipEvent_t done = nullptr; // recorded behind the last launch that read d
+	bool pending = false;
+};
+
+struct lw_resampler {
+	int device = 0;
+	uint32_t orig = 0, new_ = 0, half_width = 0, k_taps = 0;
+	std::vector<float> taps; // [new][K], the public order
+	float *d_taps = nullptr; // [K][new] by n mod new, the kernel's order (lw_resample.hpp)
+	lw_rs_slot slot[LW_RS_SLOTS];
+	unsigned next = 0;
+	bool taps_in_lds = true;
+	int last_route = -1;
+	std::vector<LwResampleRow> plan;
+	std::vector<uint64_t> taken;
+};
+
+// I0 by its power series, sum of ((x / 2)^m / m!)^2, until a term no longer changes the sum
+static double bessel_i0(double x)
+{
+	const double q = x * x / 4;
+	double sum = 1, term = 1;
+	for (double m = 1;; m += 1) {
+		term *= q / (m * m);
+		const double next = sum + term;
+		if (next == sum)
+			return sum;
+		sum = next;
+	}
+}
+
+static double tap_value(double s, double zeros, int window, double beta, double i0_beta, double t)
+{
+	const double u = s * t;
+	if (!(std::fabs(u) < zeros))
+		return 0;
+	const double pu = M_PI * u;
+	const double sinc = u == 0 ? 1.0 : std::sin(pu) / pu;
+	double w;
+	if (window == LW_RESAMPLE_HANN) {
+		const double c = std::cos(pu / (2 * zeros));
+		w = c * c;
+	} else {
+		const double r = u / zeros;
+		w = bessel_i0(beta * std::sqrt(1 - r * r)) / i0_beta;
+	}
+	return s * sinc * w;
+}
+
+static uint64_t out_len_of(const lw_resampler *rs, uint64_t len)
+{
+	const unsigned __int128 p = (unsigned __int128)len * rs->new_ + (rs->orig - 1);
+	const unsigned __int128 q = p / rs->orig;
+	return q > UINT64_MAX ? UINT64_MAX : (uint64_t)q;
+}
+
+extern "C" {
+
+lw_resampler *lw_resampler_create(int device, uint32_t in_rate, uint32_t out_rate, uint32_t zeros, double rolloff, int window, double beta,
+		int *err)
+{
+	int dummy;
+	if (!err)
+		err = &dummy;
+	*err = LW_OK;
+	if (in_rate == 0 || out_rate == 0 || zeros == 0 || !(rolloff > 0 && rolloff <= 1) ||
+			(window != LW_RESAMPLE_HANN && window != LW_RESAMPLE_KAISER) || (window == LW_RESAMPLE_KAISER && !(beta >= 0 && beta < 700))) {
+		*err = LW_ERR_UNSUPPORTED;
+		return nullptr;
+	}
+	const uint32_t g = std::gcd(in_rate, out_rate), orig = in_rate / g, new_ = out_rate / g;
+	const double s = rolloff * (new_ < orig ? (double)new_ / (double)orig : 1.0);
+	const double wd = std::ceil((double)zeros / s);
+	if (!(wd >= 1) || (2 * wd + 2) * new_ > (double)LW_RESAMPLE_MAX_TAPS) {
+		*err = LW_ERR_UNSUPPORTED;
+		return nullptr;
+	}
+	int ndev = 0;
+	if (!lw_hip_ok(hipGetDeviceCount(&ndev), "hipGetDeviceCount") || device < 0 || device >= ndev || !lw_hip_ok(hipSetDevice(device), "hipSetDevice")) {
+		*err = LW_ERR_DEVICE;
+		return nullptr;
+	}
+	auto rs = std::make_unique<lw_resampler>();
+	rs->device = device;
+	rs->orig = orig, rs->new_ = new_;
+	rs->half_width = (uint32_t)wd;
+	rs->k_taps = 2 * rs->half_width + 2;
+	const uint32_t W = rs->half_width, K = rs->k_taps;
+	const double i0_beta = window == LW_RESAMPLE_KAISER ? bessel_i0(beta) : 1;
+	rs->taps.resize((size_t)new_ * K);
+	for (uint32_t ph = 0; ph < new_; ph++)
+		for (uint32_t k = 0; k < K; k++) {
+			const double t = ((double)k - (double)W) - (double)ph / (double)new_;
+			rs->taps[(size_t)ph * K + k] = (float)tap_value(s, (double)zeros, window, beta, i0_beta, t); // the one rounding
+		}
+	std::vector<float> dev(((size_t)new_ * K + 3) & ~(size_t)3, 0.0f); // (padded: the kernel stages it 16 bytes at a time)
+	for (uint32_t i = 0; i < new_; i++) {
+		const uint32_t ph = (uint32_t)((uint64_t)i * orig % new_);
+		for (uint32_t k = 0; k < K; k++)
+			dev[(size_t)k * new_ + i] = rs->taps[(size_t)ph * K + k];
+	}
+	bool ok = lw_hip_ok(hipMalloc((void **)&rs->d_taps, dev.size() * sizeof(float)), "hipMalloc(resampler taps)") &&
+		lw_hip_ok(hipMemcpy(rs->d_taps, dev.data(), dev.size() * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(resampler taps)");
+	for (auto &sl : rs->slot)
+		ok = ok && lw_hip_ok(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming), "hipEventCreate(resampler rows)");
+	if (!ok) {
+		*err = LW_ERR_DEVICE;
+		lw_resampler_destroy(rs.release());
+		return nullptr;
+	}
+	return rs.release();
+}
+
+void lw_resampler_destroy(lw_resampler *rs)
+{
+	if (!rs)
+		return;
+	(void)hipSetDevice(rs->device);
+	(void)hipDeviceSynchronize();
+	for (auto &s : rs->slot) {
+		if (s.h)
+			(void)hipHostFree(s.h);
+		if (s.d)
+			(void)hipFree(s.d);
+		if (s.done)
+			(void)hipEventDestroy(s.done);
+	}
+	if (rs->d_taps)
+		(void)hipFree(rs->d_taps);
+	delete rs;
+}
+
+void lw_resampler_geometry(const lw_resampler *rs, uint32_t *orig, uint32_t *new_, uint32_t *half_width, uint32_t *taps_per_phase)
+{
+	if (orig)
+		*orig = rs ? rs->orig : 0;
+	if (new_)
+		*new_ = rs ? rs->new_ : 0;
+	if (half_width)
+		*half_width = rs ? rs->half_width : 0;
+	if (taps_per_phase)
+		*taps_per_phase = rs ? rs->k_taps : 0;
+}
+
+size_t lw_resampler_taps(const lw_resampler *rs, float *dst)
+{
+	if (!rs)
+		return 0;
+	if (dst)
+		std::memcpy(dst, rs->taps.data(), rs->taps.size() * sizeof(float));
+	return rs->taps.size();
+}
+
+uint64_t lw_resampler_out_len(const lw_resampler *rs, uint64_t len)
+{
+	return rs ? out_len_of(rs, len) : 0;
+}
+
+int lw_resampler_set_taps_in_lds(lw_resampler *rs, int on)
+{
+	if (!rs)
+		return LW_ERR_NULL_ARG;
+	rs->taps_in_lds = on != 0;
+	return LW_OK;
+}
+
+int lw_resampler_last_route(const lw_resampler *rs)
+{
+	return rs ? rs->last_route : -1;
+}
+
+int lw_resample_rows(lw_resampler *rs, int fmt, uint32_t ch, const void *d_src, size_t n_src_rows, size_t src_capacity, const uint64_t *len,
+		const uint32_t *dst_row, void *d_dst, size_t n_dst_rows, size_t dst_capacity, void *hip_stream)
+{
+	if (!rs || (!len && n_src_rows))
+		return LW_ERR_NULL_ARG;
+	if (fmt != LW_FMT_F32_PLANAR && fmt != LW_FMT_F32_INTERLEAVED)
+		return LW_ERR_UNSUPPORTED;
+	if (ch == 0 || ch > 255 || n_src_rows > UINT32_MAX)
+		return LW_ERR_CAPACITY;
+	// both buffers must be addressable in 64 bits of BYTES
+	uint64_t e = 0;
+	if (__builtin_mul_overflow((uint64_t)ch, (uint64_t)src_capacity, &e) || __builtin_mul_overflow(e, (uint64_t)n_src_rows, &e) || e > UINT64_MAX / 4 ||
+			__builtin_mul_overflow((uint64_t)ch, (uint64_t)dst_capacity, &e) || __builtin_mul_overflow(e, (uint64_t)n_dst_rows, &e) || e > UINT64_MAX / 4)
+		return LW_ERR_CAPACITY;
+	// ---- plan: every row is checked before anything is queued, so a refused call has written nothing
+	rs->plan.clear();
+	rs->taken.clear();
+	uint64_t longest = 0;
+	bool any_in = false;
+	for (size_t i = 0; i < n_src_rows; i++) {
+		const uint64_t row = dst_row ? dst_row[i] : i;
+		if (len[i] > src_capacity || row >= n_dst_rows)
+			return LW_ERR_CAPACITY;
+		const uint64_t out = out_len_of(rs, len[i]);
+		if (out > dst_capacity)
+			return LW_ERR_CAPACITY;
+		rs->plan.push_back(LwResampleRow{len[i], out, row});
+		rs->taken.push_back(row);
+		longest = std::max(longest, out);
+		any_in = any_in || len[i] != 0;
+	}
+	std::sort(rs->taken.begin(), rs->taken.end());
+	if (std::adjacent_find(rs->taken.begin(), rs->taken.end()) != rs->taken.end())
+		return LW_ERR_CAPACITY; // two source rows for one destination row
+	if ((any_in && !d_src) || (longest && !d_dst))
+		return LW_ERR_NULL_ARG;
+	const LwResamplePlan p = lw_resample_plan(rs->orig, rs->new_, rs->k_taps, rs->taps_in_lds);
+	const uint64_t tiles = (longest + p.tile - 1) / p.tile;
+	if (tiles > INT32_MAX)
+		return LW_ERR_CAPACITY;
+	if (longest == 0)
+		return LW_OK;
+	// ---- queue: the records, then one launch per 65535 rows
+	HIP_TRY(hipSetDevice(rs->device));
+	hipStream_t st = (hipStream_t)hip_stream;
+	lw_rs_slot &s = rs->slot[rs->next];
+	if (s.pending) { // an earlier call's copy of these records may still be on its way
+		HIP_TRY(hipEventSynchronize(s.done));
+		s.pending = false;
+	}
+	if (s.cap < n_src_rows) {
+		if (s.h)
+			(void)hipHostFree(s.h);
+		if (s.d)
+			(void)hipFree(s.d);
+		s.h = s.d = nullptr;
+		s.cap = 0;
+		const size_t cap = std::max<size_t>(n_src_rows, 64);
+		HIP_TRY(hipHostMalloc((void **)&s.h, cap * sizeof(LwResampleRow), 0));
+		HIP_TRY(hipMalloc((void **)&s.d, cap * sizeof(LwResampleRow)));
+		s.cap = cap;
+	}
+	std::memcpy(s.h, rs->plan.data(), n_src_rows * sizeof(LwResampleRow));
+	HIP_TRY(hipMemcpyAsync(s.d, s.h, n_src_rows * sizeof(LwResampleRow), hipMemcpyHostToDevice, st));
+	const bool itl = fmt == LW_FMT_F32_INTERLEAVED;
+	LwResampleArgs a{};
+	a.src = (const float *)d_src, a.dst = (float *)d_dst, a.taps = rs->d_taps, a.rows = s.d;
+	a.s = itl ? LwResampleLayout{(uint64_t)src_capacity * ch, 1, ch} : LwResampleLayout{(uint64_t)src_capacity * ch, src_capacity, 1};
+	a.d = itl ? LwResampleLayout{(uint64_t)dst_capacity * ch, 1, ch} : LwResampleLayout{(uint64_t)dst_capacity * ch, dst_capacity, 1};
+	a.orig = rs->orig, a.new_ = rs->new_, a.half_width = rs->half_width, a.k_taps = rs->k_taps, a.blocks = p.blocks;
+	for (size_t r0 = 0; r0 < n_src_rows; r0 += 65535) {
+		a.row0 = (uint32_t)r0;
+		HIP_TRY(lw_launch_resample(a, p, (uint32_t)tiles, ch, (uint32_t)std::min<size_t>(n_src_rows - r0, 65535), st));
+	}
+	HIP_TRY(hipEventRecord(s.done, st));
+	s.pending = true;
+	rs->last_route = p.route;
+	rs->next = (rs->next + 1) % LW_RS_SLOTS;
+	return LW_OK;
+}
+
+} // extern "C"

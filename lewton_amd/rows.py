@@ -17,6 +17,12 @@ kernel behind them (k_rows, csrc/lw_kernels_rows.hip) moves the samples into the
 channels= / mix= puts a channel matrix [out_ch][in_ch] into that kernel (k_rows_mix): C becomes out_ch, every output channel is
 folded from the stream's channels by the rule of include/lewton_amd.h (lw_rows_synth_mix) -- mono downmix, a selection, WAVE
 channel order -- and files of different channel counts fill one tensor.
+sample_rate= resamples the finished rows on the GPU (Resampler, lw_resample_rows, k_resample in csrc/lw_kernels_resample.hip: a
+windowed-sinc polyphase filter specified bit for bit, f32 formats), and files of different sample rates fill one tensor:
+
+    pcm, lengths, rate = decode_ogg_files(paths, channels="mono", sample_rate=16000)
+    rs = Resampler(44100, 16000); out = rs.run(tensor, lengths)             # the same pass over a caller's own rows tensor
+
 torch is imported inside the functions, never at module import.
 """
 import ctypes as C
@@ -220,6 +226,142 @@ class Rows:
         return N.lw_rows_last_copied_elems(self._h)
 
 
+_WINDOWS = {"hann": 0, "kaiser": 1}          # LW_RESAMPLE_HANN, LW_RESAMPLE_KAISER
+KAISER_BETA = 14.769656459379492            # the good-quality choice of include/lewton_amd.h, with zeros=16
+RESAMPLE_MAX_TAPS = 65536                   # LW_RESAMPLE_MAX_TAPS
+
+
+def resample_geometry(in_rate, out_rate, zeros=6, rolloff=0.99):
+    """(orig, new, half width W, taps per phase K) of a resampler, by the rule of include/lewton_amd.h ("resampling rows");
+    ValueError for what lw_resampler_create refuses.  Needs no GPU."""
+    import math
+    for name, v in (("in_rate", in_rate), ("out_rate", out_rate), ("zeros", zeros)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 < v < 1 << 32:
+            raise ValueError("%s=%r: a positive integer" % (name, v))
+    if not 0 < rolloff <= 1:
+        raise ValueError("rolloff=%r: in (0, 1]" % (rolloff,))
+    g = math.gcd(int(in_rate), int(out_rate))
+    orig, new = int(in_rate) // g, int(out_rate) // g
+    s = float(rolloff) * (new / orig if new < orig else 1.0)
+    w = math.ceil(zeros / s)
+    if new * (2 * w + 2) > RESAMPLE_MAX_TAPS:
+        raise ValueError("%d -> %d Hz with zeros=%d needs %d x %d taps, more than %d" % (in_rate, out_rate, zeros, new, 2 * w + 2,
+                                                                                     RESAMPLE_MAX_TAPS))
+    return orig, new, w, 2 * w + 2
+
+
+def _resample_params(resample):
+    """resample= of decode_streams / decode_ogg_files: a dict of Resampler's filter parameters, checked by name"""
+    p = dict(resample or {})
+    extra = set(p) - {"zeros", "rolloff", "window", "beta"}
+    if extra:
+        raise ValueError("resample= takes zeros, rolloff, window and beta, not %s" % ", ".join(sorted(extra)))
+    return p
+
+
+class Resampler:
+    """lw_resampler: rows of f32 PCM at in_rate -> rows at out_rate on the GPU (k_resample), by the windowed-sinc polyphase filter
+    of include/lewton_amd.h ("resampling rows"), a contract on bits.  window: "hann" or "kaiser" (beta: KAISER_BETA when None).
+    Parameter errors are ValueError and need no GPU; the object itself lives on cuda:device."""
+
+    def __init__(self, in_rate, out_rate, zeros=6, rolloff=0.99, window="hann", beta=None, device=0):
+        if window not in _WINDOWS:
+            raise ValueError("window=%r: \"hann\" or \"kaiser\"" % (window,))
+        if beta is None:
+            beta = KAISER_BETA if window == "kaiser" else 0.0
+        if window == "kaiser" and not 0 <= beta < 700:
+            raise ValueError("beta=%r: in [0, 700)" % (beta,))
+        self.orig, self.new, self.half_width, self.taps_per_phase = resample_geometry(in_rate, out_rate, zeros, rolloff)
+        self.in_rate, self.out_rate, self.device = int(in_rate), int(out_rate), device
+        _gpu()
+        err = C.c_int(0)
+        self._h = N.lw_resampler_create(device, int(in_rate), int(out_rate), int(zeros), float(rolloff), _WINDOWS[window], float(beta),
+                                        C.byref(err))
+        if not self._h:
+            if err.value == N.ERR_UNSUPPORTED:
+                raise ValueError("lw_resampler_create refused the parameters")
+            raise RuntimeError("lw_resampler_create failed (%d): %s" % (err.value, N.device_error()))
+        geo = [C.c_uint32() for _ in range(4)]
+        N.lw_resampler_geometry(self._h, *[C.byref(g) for g in geo])
+        assert tuple(g.value for g in geo) == (self.orig, self.new, self.half_width, self.taps_per_phase)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            N.lw_resampler_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        if N is not None and getattr(N, "lw_resampler_destroy", None) is not None:  # not during interpreter shutdown
+            self.close()
+
+    def taps(self):
+        """the filter [new][K], float32"""
+        out = np.empty((self.new, self.taps_per_phase), np.float32)
+        assert N.lw_resampler_taps(self._h, None) == out.size
+        N.lw_resampler_taps(self._h, out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def out_len(self, n):
+        """output samples of a row of n input samples: ceil(n * new / orig)"""
+        return int(N.lw_resampler_out_len(self._h, int(n)))
+
+    @property
+    def last_route(self):
+        """0: taps and samples from LDS, 1: taps from global memory, 2: both from global memory, 3: copy (lw_resampler_last_route)"""
+        return N.lw_resampler_last_route(self._h)
+
+    def check_tensor(self, tensor, samples, what):
+        """(n_rows, channels, row_capacity) of a rows tensor, or ValueError: as Rows.check_tensor, for the two f32 formats"""
+        torch = _gpu()
+        if tensor.dtype != torch.float32:
+            raise ValueError("%s is %s, the resampler works on float32" % (what, tensor.dtype))
+        if tensor.device.type != "cuda" or tensor.device.index != self.device:
+            raise ValueError("%s is on %s, the resampler on cuda:%d" % (what, tensor.device, self.device))
+        if not tensor.is_contiguous():
+            raise ValueError("%s is not contiguous" % what)
+        if tensor.dim() != 3:
+            raise ValueError("%s must have three dimensions, not %d" % (what, tensor.dim()))
+        b, x, y = tensor.shape
+        return (b, y, x) if N.fmt_interleaved(_FMT[samples]) else (b, x, y)
+
+    def run(self, src, lengths, out=None, rows=None, stream=None, samples="f32"):
+        """lw_resample_rows: row i of src ([B, C, T], or [B, T, C] for samples="f32_interleaved"), lengths[i] samples per channel,
+        -> row rows[i] of out (None: row i), out_len(lengths[i]) samples; nothing else of out is written.  out=None: a zeroed
+        tensor of max(rows) + 1 rows and the longest output length.  stream: a hipStream_t value; None = torch's current stream on
+        the resampler's device.  Asynchronous; returns out."""
+        torch = _gpu()
+        fmt = _FMT[samples]
+        if fmt not in (N.FMT_F32_PLANAR, N.FMT_F32_INTERLEAVED):
+            raise ValueError("the resampler works on the f32 formats, not %r" % (samples,))
+        n_src, ch, cap = self.check_tensor(src, samples, "src")
+        lens = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+        if len(lens) != n_src or any(v < 0 for v in lens):
+            raise ValueError("lengths= needs one non-negative entry per row of src")
+        lens = np.asarray(lens, np.uint64)
+        rmap = None
+        if rows is not None:
+            rows = [int(v) for v in (rows.tolist() if hasattr(rows, "tolist") else rows)]
+            if len(rows) != n_src or any(not 0 <= v < 1 << 32 for v in rows):
+                raise ValueError("rows= needs one destination row per row of src")
+            rmap = np.asarray(rows, np.uint32)
+        if out is None:
+            n_dst = max(rows) + 1 if rows else n_src
+            T = max([self.out_len(v) for v in lens.tolist()], default=0)
+            out = torch.zeros((n_dst, T, ch) if N.fmt_interleaved(fmt) else (n_dst, ch, T), dtype=torch.float32, device="cuda:%d" % self.device)
+        n_dst, och, dcap = self.check_tensor(out, samples, "out")
+        if och != ch:
+            raise ValueError("out has %d channels, src %d" % (och, ch))
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream or None
+        rc = N.lw_resample_rows(self._h, fmt, ch, C.c_void_p(src.data_ptr()), n_src, cap, lens.ctypes.data_as(C.c_void_p),
+                                None if rmap is None else rmap.ctypes.data_as(C.c_void_p), C.c_void_p(out.data_ptr()), n_dst, dcap, stream)
+        if rc in (N.ERR_NULL_ARG, N.ERR_CAPACITY, N.ERR_UNSUPPORTED):
+            raise ValueError("lw_resample_rows refused the call (%d)" % rc)
+        if rc:
+            raise RuntimeError("lw_resample_rows: %d %s" % (rc, N.device_error()))
+        return out
+
+
 def _round_up(n, to):
     to = max(1, int(to))
     return (n + to - 1) // to * to
@@ -376,7 +518,7 @@ def _per_stream(v, n, what):
 
 
 def decode_streams(ident, setup, streams, samples="f32", device=0, max_packets=16384, run=16, entropy_on_device="auto",
-                   skip=None, keep=None, pad_to=64, out=None, channels=None):
+                   skip=None, keep=None, pad_to=64, out=None, channels=None, sample_rate=None, resample=None):
     """Whole streams of one (ident, setup) pair -> (pcm, lengths, errors).
 
     streams: list of lists of audio-packet bytes (a stream's first packet only primes the window, audio.rs:1140-1152).
@@ -387,17 +529,40 @@ def decode_streams(ident, setup, streams, samples="f32", device=0, max_packets=1
     skip[s] drops leading samples of stream s, keep[s] caps its length.  Batches of up to max_packets packets take up to `run`
     consecutive packets of each stream in turn.  entropy_on_device: "auto" = k_entropy where the stream is eligible.
     channels: None = the stream's own channels; "mono" = mix_mono; anything else a channel matrix [out_ch][in_ch] -- C is then
-    out_ch, and out= is checked against it (i16 formats: routing matrices only, ValueError before anything is decoded).  The GPU
-    work is queued on torch's current stream; the call returns when it has completed."""
+    out_ch, and out= is checked against it (i16 formats: routing matrices only, ValueError before anything is decoded).
+    sample_rate: None or the stream's own rate = the samples as decoded.  Any other rate (f32 formats only, ValueError before
+    anything is decoded): the streams are decoded as above -- skip, keep and channels= at the stream's rate -- into a temporary
+    tensor, and a Resampler(stream's rate, sample_rate, **resample) fills pcm from it; lengths are then OUTPUT lengths,
+    out_len of the decoded ones, and T is out_len of the longest row's upper bound rounded up to pad_to.  resample: a dict of
+    zeros, rolloff, window, beta.  The GPU work is queued on torch's current stream; the call returns when it has completed."""
     import torch
     _host()
     fmt = _FMT[samples]
     mix = None if channels is None else _named_mix(channels, ident.audio_channels, fmt)
+    params = _resample_params(resample)
     streams = [list(s) for s in streams]
     B = len(streams)
     skip = [0 if v is None else int(v) for v in _per_stream(skip, B, "skip")]
     keep = _per_stream(keep, B, "keep")
     bound = [_row_length(_sample_bound(ident, setup, s), skip[i], keep[i]) for i, s in enumerate(streams)]
+    if sample_rate is not None and sample_rate != ident.audio_sample_rate:
+        if fmt not in (N.FMT_F32_PLANAR, N.FMT_F32_INTERLEAVED):
+            raise ValueError("samples=%r at %d Hz from a %d Hz stream: the resampler works on the f32 formats" % (
+                samples, sample_rate, ident.audio_sample_rate))
+        ch = ident.audio_channels if mix is None else mix.shape[0]
+        rs = Resampler(ident.audio_sample_rate, sample_rate, device=device, **params)
+        try:
+            T = _round_up(max((rs.out_len(b) for b in bound), default=0), pad_to)
+            with torch.cuda.device(device):
+                pcm = _alloc(fmt, B, ch, T, device, out)
+                native, nat_lengths, errors = decode_streams(ident, setup, streams, samples, device, max_packets, run, entropy_on_device,
+                                                             skip, keep, 1, None, channels)
+                rs.run(native, nat_lengths, out=pcm, samples=samples)
+                torch.cuda.current_stream(device).synchronize()
+            lengths = torch.tensor([rs.out_len(n) for n in nat_lengths.tolist()], dtype=torch.int64)
+        finally:
+            rs.close()
+        return pcm, lengths, errors
     T = _round_up(max(bound, default=0), pad_to)
     with torch.cuda.device(device):
         pcm = _alloc(fmt, B, ident.audio_channels if mix is None else mix.shape[0], T, device, out)
@@ -476,7 +641,12 @@ def decode_ogg_files(sources, samples="f32", device=0, **kw):
     channels: None = the files' own channels.  Otherwise every decoder group goes through the matrix for ITS channel count, and
     files of different channel counts fill one tensor as long as every matrix has the same out_ch (ValueError naming the file
     otherwise; sample rates must still agree): "mono" = mix_mono, "wav" = mix_wav_order, a dict {in_ch: matrix}, or a callable
-    in_ch -> matrix.  i16 formats: routing matrices only, ValueError before anything is decoded."""
+    in_ch -> matrix.  i16 formats: routing matrices only, ValueError before anything is decoded.
+    sample_rate (and resample, a dict of Resampler's zeros, rolloff, window, beta): with it files of different sample rates fill
+    one tensor at that rate, which is the rate returned.  Decoder groups already at sample_rate decode straight into their rows;
+    every other group decodes into a temporary tensor (skip, keep and channels= at the file's rate) and a Resampler fills its rows
+    from it (f32 formats only, ValueError before anything is decoded).  lengths are output lengths.  Without sample_rate the
+    rates must agree as before."""
     import torch
     _host()
     from . import header as H
@@ -490,8 +660,11 @@ def decode_ogg_files(sources, samples="f32", device=0, **kw):
     max_packets, run = kw.pop("max_packets", 16384), kw.pop("run", 16)
     entropy_on_device = kw.pop("entropy_on_device", "auto")
     channels = kw.pop("channels", None)
+    sample_rate, params = kw.pop("sample_rate", None), _resample_params(kw.pop("resample", None))
     if kw:
         raise TypeError("unexpected arguments: %s" % ", ".join(sorted(kw)))
+    if sample_rate is not None:
+        resample_geometry(sample_rate, sample_rate)                     # (a rate that is no positive integer: ValueError)
     groups = {}   # (ident packet, setup packet) -> [ident, setup, [file index], [packets], [packet keeps]]
     shape = None
     bound = [0] * B
@@ -511,36 +684,63 @@ def decode_ogg_files(sources, samples="f32", device=0, **kw):
                 except (ValueError, KeyError) as e:
                     raise ValueError("%s: %s" % (names[i], e))
         ident, setup = g[0], g[1]
+        # with sample_rate= the files' own rates may differ: the rate every row ends up with is the one that was asked for
+        rate = ident.audio_sample_rate if sample_rate is None else sample_rate
         if channels is not None:
             # the channel count that has to agree is the matrices' out_ch; the files' own may differ
             if shape is None:
-                shape = (g[5].shape[0], ident.audio_sample_rate)
+                shape = (g[5].shape[0], rate)
             elif shape[0] != g[5].shape[0]:
                 raise ValueError("%s: its channel matrix has %d output channels, those of the files before it %d" % (
                     names[i], g[5].shape[0], shape[0]))
-            elif shape[1] != ident.audio_sample_rate:
+            elif shape[1] != rate:
                 raise ValueError("%s: %d Hz, the files before it %d Hz" % (names[i], ident.audio_sample_rate, shape[1]))
         elif shape is None:
-            shape = (ident.audio_channels, ident.audio_sample_rate)
-        elif shape != (ident.audio_channels, ident.audio_sample_rate):
+            shape = (ident.audio_channels, rate)
+        elif shape != (ident.audio_channels, rate):
             raise ValueError("%s: %d channels at %d Hz, the files before it %d at %d Hz" % (
-                (names[i], ident.audio_channels, ident.audio_sample_rate) + shape))
+                (names[i], ident.audio_channels, rate) + shape))
+        if ident.audio_sample_rate != rate and fmt not in (N.FMT_F32_PLANAR, N.FMT_F32_INTERLEAVED):
+            raise ValueError("%s: samples=%r at %d Hz from a %d Hz file: the resampler works on the f32 formats" % (
+                names[i], samples, rate, ident.audio_sample_rate))
         keeps = _ogg_keeps(ident, setup, packets, names[i])
         data = [p.data for p in packets]
         g[2].append(i), g[3].append(data), g[4].append(keeps)
         bound[i] = _row_length(_sample_bound(ident, setup, data, keeps), skip[i], keep[i])
     if shape is None:
         raise ValueError("no sources")
-    T = _round_up(max(bound), pad_to)
     lengths = [0] * B
-    with torch.cuda.device(device):
-        pcm = _alloc(fmt, B, shape[0], T, device, out)
-        for ident, setup, idx, streams, keeps, mix in groups.values():
-            decoded, errors = _decode_group(decoder_for(ident, setup, device), streams, samples, max_packets, run, entropy_on_device,
-                                            [skip[i] for i in idx], [keep[i] for i in idx], pcm, idx, keeps, mix)
-            if errors:
-                s, t, code = errors[0]
-                raise ValueError("%s: audio packet %d does not decode (%d)" % (names[idx[s]], t, code))
-            for j, i in enumerate(idx):
-                lengths[i] = _row_length(int(decoded[j]), skip[i], keep[i])
+    resamplers = {}   # native rate -> Resampler, for the groups that are not at sample_rate
+    native_bound = list(bound)
+    try:
+        for ident, setup, idx, *_ in groups.values():
+            r = ident.audio_sample_rate
+            if r != shape[1]:
+                if r not in resamplers:
+                    resamplers[r] = Resampler(r, shape[1], device=device, **params)
+                for i in idx:
+                    bound[i] = resamplers[r].out_len(bound[i])
+        T = _round_up(max(bound), pad_to)
+        with torch.cuda.device(device):
+            pcm = _alloc(fmt, B, shape[0], T, device, out)
+            for ident, setup, idx, streams, keeps, mix in groups.values():
+                rs = resamplers.get(ident.audio_sample_rate)
+                dst, rows_of = pcm, idx
+                if rs is not None:
+                    # at the file's rate into a temporary tensor of this group's rows, then the resampler into pcm's
+                    dst, rows_of = _alloc(fmt, len(idx), shape[0], max(native_bound[i] for i in idx), device, None), list(range(len(idx)))
+                decoded, errors = _decode_group(decoder_for(ident, setup, device), streams, samples, max_packets, run, entropy_on_device,
+                                                [skip[i] for i in idx], [keep[i] for i in idx], dst, rows_of, keeps, mix)
+                if errors:
+                    s, t, code = errors[0]
+                    raise ValueError("%s: audio packet %d does not decode (%d)" % (names[idx[s]], t, code))
+                native = [_row_length(int(decoded[j]), skip[i], keep[i]) for j, i in enumerate(idx)]
+                if rs is not None:
+                    rs.run(dst, native, out=pcm, rows=idx, samples=samples)
+                    torch.cuda.current_stream(device).synchronize()
+                for j, i in enumerate(idx):
+                    lengths[i] = native[j] if rs is None else rs.out_len(native[j])
+    finally:
+        for rs in resamplers.values():
+            rs.close()
     return pcm, torch.tensor(lengths, dtype=torch.int64), shape[1]
