@@ -343,6 +343,65 @@ int lw_resample_rows(lw_resampler *rs, int fmt, uint32_t ch, const void *d_src, 
 int lw_resampler_last_route(const lw_resampler *rs);
 int lw_resampler_set_taps_in_lds(lw_resampler *rs, int on);
 
+/* ---- spectral frames of rows ---------------------------------------------------------------------------------------------
+ * Finished rows -> overlapping frames -> power spectrum or mel features, on the GPU, as a pass of its own (k_spec): what a speech
+ * or audio model does first with a [stream][1][samples] tensor.  The source is a rows buffer of either f32 format, `ch` channels,
+ *   [row][ch][capacity] (LW_FMT_F32_PLANAR) or [row][capacity][ch] (LW_FMT_F32_INTERLEAVED);
+ * the destination is f32 [row][ch][F][frame_capacity], F = n_mels when n_mels > 0, else F = B (the power spectrum).  The
+ * transform is a dense windowed DFT, and it is a contract on BITS:
+ *
+ * A lw_spec is made from (n_fft, win_length, hop, window, center, n_mels, fb).  2 <= n_fft <= LW_SPEC_MAX_FFT,
+ * 1 <= win_length <= n_fft, 1 <= hop <= 65535, n_mels <= LW_SPEC_MAX_MELS.  B = n_fft / 2 + 1 bins (integer division).
+ *   window  w[i], 0 <= i < win_length:  0.5 - 0.5 cos(2 pi i / win_length)  LW_SPEC_HANN (periodic);  1  LW_SPEC_RECT.
+ *           Within a frame it sits at offset o = (n_fft - win_length) / 2 (integer division); the SUPPORT is k in
+ *           [o, o + win_length).
+ *   basis   the window folded in, evaluated in double and rounded ONCE to f32, for k in the support and 0 <= j < B:
+ *           a = 2 pi ((k * j) mod n_fft) / n_fft (reduced in integers before the angle is formed),
+ *           C[k][j] = w[k - o] * cos(a),  S[k][j] = -w[k - o] * sin(a)
+ *   frames  pad = center ? n_fft / 2 : 0.  n_frames(len), in 64-bit integers: 0 for len == 0; 1 + len / hop when centred;
+ *           otherwise len < n_fft ? 0 : 1 + (len - n_fft) / hop.  Sample k of frame t is x[t * hop - pad + k] (signed 64-bit
+ *           index); x[i] = +0.0 for i < 0 and for i >= len -- len, not the capacity: what the source holds between len and its
+ *           capacity never reaches the output, and no byte beyond the capacity is read.  Reflect padding is not offered.
+ *   spectrum  re[j]: acc = +0.0; for k ascending over the support acc = fmaf(x_k, C[k][j], acc).  im[j]: the same with S.
+ *           P[j] = fmaf(im, im, re * re), the product re * re one rounded f32 multiply.
+ *   mel     (n_mels > 0) fb is the caller's matrix, n_mels x B host floats, fb[q * B + j], copied at creation.
+ *           m[q]: acc = +0.0; for j = 0 .. B - 1 ascending acc = fmaf(P[j], fb[q][j], acc).  Dense: a weight of 0 takes part
+ *           like any other.
+ *   bits    no reassociation, no chain split over k or over j, subnormals kept.  Two things are NOT part of the contract: the
+ *           sign of a zero result (a zero-padded tail of a matrix tile can turn -0 into +0, and a spectrum is squared anyway)
+ *           and which NaN a NaN result is.  Every other bit is.
+ * Exactly [0, n_frames(len)) of each of the F lines of a destination row and channel is written, nothing else.
+ *
+ * lw_spec_rows: source row i (len[i] samples per channel) goes to destination row dst_row[i] (NULL: row i).  len and dst_row
+ * are HOST arrays, copied during the call.  Asynchronous on hip_stream; calls on one object may be queued back to back.
+ * Refusals, decided on the host before anything is queued, so a refused call has written nothing:
+ *   LW_ERR_NULL_ARG     sp NULL, len NULL with rows, d_src / d_dst NULL with frames to compute; (create) fb NULL with n_mels > 0
+ *   LW_ERR_UNSUPPORTED  (create) a parameter outside the limits above, an unknown window;  (rows) an i16 format
+ *   LW_ERR_DEVICE       (create) no such device, or its LDS per workgroup is below the 67 648 bytes k_spec needs (asked of the
+ *                       device, not assumed)
+ *   LW_ERR_CAPACITY     len[i] > src_capacity, n_frames(len[i]) > frame_capacity, dst_row[i] >= n_dst_rows, two source rows for
+ *                       one destination row, ch == 0 or > 255 */
+typedef struct lw_spec lw_spec;
+enum { LW_SPEC_HANN = 0, LW_SPEC_RECT = 1 };
+#define LW_SPEC_MAX_FFT 2048
+#define LW_SPEC_MAX_MELS 256
+lw_spec *lw_spec_create(int device, uint32_t n_fft, uint32_t win_length, uint32_t hop, int window, int center, uint32_t n_mels,
+		const float *fb, int *err);
+void lw_spec_destroy(lw_spec *sp);
+uint32_t lw_spec_bins(const lw_spec *sp);                /* B */
+uint32_t lw_spec_features(const lw_spec *sp);            /* F */
+uint64_t lw_spec_frames(const lw_spec *sp, uint64_t len); /* n_frames(len) */
+size_t lw_spec_basis(const lw_spec *sp, float *dst);     /* [2][win_length][B], C then S; returns the count, dst NULL = size query */
+uint32_t lw_spec_tile_frames(const lw_spec *sp);         /* the frames one workgroup takes */
+int lw_spec_rows(lw_spec *sp, int fmt, uint32_t ch, const void *d_src, size_t n_src_rows, size_t src_capacity, const uint64_t *len,
+		const uint32_t *dst_row, void *d_dst, size_t n_dst_rows, size_t frame_capacity, void *hip_stream);
+/* routes: 0 = the DFT fold on the matrix cores (v_mfma_f32_32x32x2_f32, whose result is a k-ordered fmaf chain), 1 = the same
+ * kernel body with per-lane fmaf chains -- the fall-back and the second witness for the bits.  Both give the same bits.
+ * lw_spec_last_route: the route of the last queued call, -1 = no call yet.  lw_spec_set_route: LW_ERR_UNSUPPORTED for a route the
+ * build does not have. */
+int lw_spec_last_route(const lw_spec *sp);
+int lw_spec_set_route(lw_spec *sp, int route);
+
 /* ---- staging ring (BASELINE north_star: "pinned hipMemcpyAsync staging ring so entropy decode of packet N+1 overlaps
  * GPU synthesis of packet N") ------------------------------------------------------------------------------------------
  * A ring of `slots` staging slots on the decoder's device; a slot = one batch object (pinned records + device mirror), a device

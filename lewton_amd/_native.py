@@ -150,6 +150,17 @@ SYMBOLS = {
                                    C.c_size_t, C.c_size_t, C.c_void_p]),
     "lw_resampler_last_route": (C.c_int, [C.c_void_p]),
     "lw_resampler_set_taps_in_lds": (C.c_int, [C.c_void_p, C.c_int]),
+    "lw_spec_create": (C.c_void_p, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_uint32, C.c_void_p, intp]),
+    "lw_spec_destroy": (None, [C.c_void_p]),
+    "lw_spec_bins": (C.c_uint32, [C.c_void_p]),
+    "lw_spec_features": (C.c_uint32, [C.c_void_p]),
+    "lw_spec_frames": (C.c_uint64, [C.c_void_p, C.c_uint64]),
+    "lw_spec_basis": (C.c_size_t, [C.c_void_p, C.c_void_p]),
+    "lw_spec_tile_frames": (C.c_uint32, [C.c_void_p]),
+    "lw_spec_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_size_t, C.c_size_t, C.c_void_p]),
+    "lw_spec_last_route": (C.c_int, [C.c_void_p]),
+    "lw_spec_set_route": (C.c_int, [C.c_void_p, C.c_int]),
     "lw_ring_create": (C.c_void_p, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, intp]),
     "lw_ring_destroy": (None, [C.c_void_p]),
     "lw_ring_stage": (C.c_int, [C.c_void_p, C.POINTER(Packet), C.c_size_t, C.c_int]),

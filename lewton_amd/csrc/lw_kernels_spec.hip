@@ -1,0 +1,347 @@
+// Spectral frames of rows (product code, gfx950): k_spec, the kernel of lw_spec_rows.  A pass of its own over finished rows
+// ([row][ch][sample] or [row][sample][ch], f32): overlapping frames of a row and channel -> power spectrum or mel features,
+// [row][ch][F][frame], by the rule of include/lewton_amd.h ("spectral frames of rows"), bit for bit:
+//   re[j] = fold over the window's support, k ascending, of fmaf(x_k, C[k][j], acc) from +0.0;  im[j] likewise with S
+//   P[j]  = fmaf(im, im, re * re);  m[q] = fold over j = 0 .. B - 1 ascending of fmaf(P[j], fb[q][j], acc) from +0.0
+//   x = +0.0 outside [0, len).  No chain is ever split; the unit is compiled with -ffp-contract=off like all others.
+//
+// Work: a tile = LW_SP_TF = 32 consecutive frames of one (row, channel), one workgroup of 256 lanes (four waves) per tile, grid =
+// (tiles, channels, rows).  The framed DFT is a GEMM, D[bin][frame] = sum_k basis[k][bin] * x[frame * hop + k], run on
+// v_mfma_f32_32x32x2_f32, whose result is a k-ordered fmaf chain: M = 32 bins (A operand, from the basis), N = 32 frames (B
+// operand, from the row), so a result's frame is its lane (lane & 31) and stores run over consecutive frames.
+//   pass   256 bins at a time (all of them up to n_fft = 510).  Wave w owns the columns [64 w, 64 w + 64) of the pass as two
+//          32 x 32 tiles, each with a cosine and a sine accumulator -- four independent accumulators per wave, and re and im of one
+//          (bin, frame) in the same lane and register.  Parallelism comes from output tiles only: one output's K loop stays in
+//          one accumulator, ascending.  A tile wholly behind the last bin is skipped (wave-uniform).
+//   stage  per K tile of 16 support samples: the basis tile [16][C | S][256] (one contiguous run of the device table, 16 bytes
+//          per load, eight loads in flight per lane) and the FRAME tile [16][32 frames], laid out per frame in LDS: element
+//          (k, f) = x[(f0 + f) * hop + lead + k], loaded with consecutive lanes on consecutive k (coalesced), clamped index,
+//          the +0.0 selected afterwards.  The frame matrix exists only here, 2 KiB at a time; any hop up to 65535 costs the
+//          same LDS.  Banks: operand reads are 32 consecutive words per half-wave in both tiles (conflict-free, ds_read_b32
+//          serves lanes 0-31 and 32-63 separately); the frame tile's rows are 33 words apart so that the staging stores, which
+//          run down a column, spread over the banks (2-way instead of 16-way).  hop never reaches an LDS address.
+//   tails  k >= win_length: both operands are zeros (fmaf(0, 0, acc) = acc but for the sign of a zero, which is outside the
+//          contract).  Bins >= B and frames >= n_frames of a tile are computed and never stored or read.
+//   power  P of the pass goes to LDS as [bin][frame].  Without a mel matrix it is stored from there; with one, every lane keeps
+//          the accumulators of ONE frame and up to 32 mel bands in registers over all passes and folds P[j] in ascending j, the
+//          matrix slice [32 j][mel_pad] staged where the basis tile was (vector fmaf: a tenth of the arithmetic).
+// Route 1 (LW_SP_ROUTE_FMA) is the same body with the matrix instruction replaced by per-lane fmaf chains over the same LDS
+// tiles and the same register layout: the fall-back, the second witness for the bits, and what tests/san/spec_host.cpp compiles
+// for the host (LW_SPEC_HOST) and runs lane by lane.
+// Addresses: row, channel and sample offsets are 64-bit from the arguments to the load and the store; everything else is
+// 32-bit relative to the tile.  Plain vector loads and stores, no scratch (profiles/rows_spec_resource_usage.txt).
+#include "lw_spec.hpp"
+
+#ifdef LW_SPEC_HOST
+#define LW_SP_FN static inline
+#else
+#include "lw_kernels.hpp"
+#define LW_SP_FN __device__ __forceinline__
+#endif
+
+struct LwSpTile { // what a workgroup works on; the same for all its lanes
+	uint64_t len, n_frames;
+	uint64_t f0;   // first frame of the tile
+	int64_t x0;    // input sample under support sample 0 of frame f0
+	uint64_t s_at; // element of sample 0 of the source row and channel
+	uint64_t d_at; // element of line 0, frame 0 of the destination row and channel
+};
+
+struct LwSpLane { // what a lane keeps in registers between the phases of its workgroup
+	float acc[4][16]; // [2 * tile + sine][register]: bin = LW_SP_ROW(register, lane), frame = lane & 31
+	float mel[8][4];  // band 4 * ((tid >> 5) + 8 * b) + i of frame tid & 31
+};
+
+// C/D layout of the 32x32 matrix instructions: register r of lane l holds row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31
+#define LW_SP_ROW(r, lane) (((r) & 3u) + 8u * ((r) >> 2) + 4u * ((lane) >> 5))
+
+LW_SP_FN bool lw_sp_tile(const LwSpecArgs &a, uint32_t bx, uint32_t by, uint32_t bz, LwSpTile &t)
+{
+	const LwSpecRow r = a.rows[(uint64_t)a.row0 + bz];
+	t.len = r.len, t.n_frames = r.n_frames;
+	t.f0 = (uint64_t)bx * LW_SP_TF;
+	if (t.f0 >= r.n_frames)
+		return false;
+	t.x0 = (int64_t)(t.f0 * a.hop) + a.lead;
+	t.s_at = ((uint64_t)a.row0 + bz) * a.s.row + (uint64_t)by * a.s.ch;
+	t.d_at = r.dst_row * a.d_row + (uint64_t)by * a.d_ch;
+	return true;
+}
+
+// input index of support sample k of the tile's frame f
+LW_SP_FN int64_t lw_sp_index(const LwSpecArgs &a, const LwSpTile &t, uint32_t f, uint32_t k)
+{
+	return t.x0 + (int64_t)((uint64_t)f * a.hop) + (int64_t)k;
+}
+
+// x[i] of the tile's row and channel, +0.0 outside [0, len): the load goes to a clamped index (len >= 1 wherever a tile exists), so
+// it is branch-free, never leaves [0, len), and what lies between len and the capacity is never fetched
+LW_SP_FN float lw_sp_x(const LwSpecArgs &a, const LwSpTile &t, int64_t i)
+{
+	const bool in = i >= 0 && (uint64_t)i < t.len;
+	const uint64_t c = i < 0 ? 0 : (uint64_t)i < t.len ? (uint64_t)i : t.len - 1;
+	const float v = a.src[t.s_at + c * a.s.el];
+	return in ? v : 0.0f;
+}
+
+struct alignas(16) LwSpF4 {
+	float v[4];
+};
+
+LW_SP_FN void lw_sp_zero_acc(LwSpLane &st)
+{
+#pragma unroll
+	for (int i = 0; i < 4; i++)
+#pragma unroll
+		for (int r = 0; r < 16; r++)
+			st.acc[i][r] = 0.0f;
+}
+
+LW_SP_FN void lw_sp_zero_mel(LwSpLane &st)
+{
+#pragma unroll
+	for (int b = 0; b < 8; b++)
+#pragma unroll
+		for (int i = 0; i < 4; i++)
+			st.mel[b][i] = 0.0f;
+}
+
+// ---- stage: K tile kt of pass `pass` into LDS; all of a lane's loads are in flight before its first store
+LW_SP_FN void lw_sp_stage(const LwSpecArgs &a, const LwSpTile &t, uint32_t pass, uint32_t kt, uint32_t tid, float *lds)
+{
+	const uint32_t k0 = kt * LW_SP_KT;
+	const LwSpF4 *g = (const LwSpF4 *)(a.basis + ((size_t)pass * a.k_pad + k0) * (2u * LW_SP_COLS));
+	constexpr uint32_t NA = LW_SP_KT * 2u * LW_SP_COLS / 4u / LW_SP_THREADS; // 8
+	constexpr uint32_t NX = LW_SP_KT * LW_SP_TF / LW_SP_THREADS;             // 2
+	LwSpF4 va[NA];
+	float vx[NX];
+#pragma unroll
+	for (uint32_t q = 0; q < NA; q++)
+		va[q] = g[tid + q * LW_SP_THREADS];
+#pragma unroll
+	for (uint32_t q = 0; q < NX; q++) {
+		const uint32_t e = tid + q * LW_SP_THREADS, kk = e % LW_SP_KT, f = e / LW_SP_KT;
+		const float v = lw_sp_x(a, t, lw_sp_index(a, t, f, k0 + kk));
+		vx[q] = k0 + kk < a.win_length ? v : 0.0f;
+	}
+	LwSpF4 *as = (LwSpF4 *)(lds + LW_SP_LDS_A);
+#pragma unroll
+	for (uint32_t q = 0; q < NA; q++)
+		as[tid + q * LW_SP_THREADS] = va[q];
+#pragma unroll
+	for (uint32_t q = 0; q < NX; q++) {
+		const uint32_t e = tid + q * LW_SP_THREADS, kk = e % LW_SP_KT, f = e / LW_SP_KT;
+		lds[LW_SP_LDS_X + kk * LW_SP_XS + f] = vx[q];
+	}
+}
+
+// which of a wave's two tiles hold a bin at all
+LW_SP_FN bool lw_sp_tile_live(const LwSpecArgs &a, uint32_t pass, uint32_t wave, uint32_t tt)
+{
+	return pass * LW_SP_COLS + wave * 64u + tt * 32u < a.bins;
+}
+
+#ifndef LW_SPEC_HOST
+typedef float lw_sp_f16 __attribute__((ext_vector_type(16)));
+#endif
+
+// ---- fold: the 16 support samples of the staged tile into the lane's accumulators, k ascending
+template <int ROUTE> LW_SP_FN void lw_sp_mma(const LwSpecArgs &a, uint32_t pass, uint32_t tid, const float *lds, LwSpLane &st)
+{
+	const uint32_t lane = tid & 63u, wave = tid >> 6, f = lane & 31u;
+	const float *as = lds + LW_SP_LDS_A + wave * 64u, *xs = lds + LW_SP_LDS_X;
+#ifndef LW_SPEC_HOST
+	if (ROUTE == LW_SP_ROUTE_MFMA) {
+		// A[i = lane & 31][k = lane >> 5] = basis[k][bin i], B[k = lane >> 5][j = lane & 31] = x of frame j: one f32 each
+		const uint32_t h = lane >> 5;
+#pragma unroll
+		for (uint32_t tt = 0; tt < 2u; tt++) {
+			if (!lw_sp_tile_live(a, pass, wave, tt))
+				continue;
+			lw_sp_f16 re, im;
+#pragma unroll
+			for (int r = 0; r < 16; r++)
+				re[r] = st.acc[2 * tt][r], im[r] = st.acc[2 * tt + 1][r];
+#pragma unroll
+			for (uint32_t kk = 0; kk < LW_SP_KT; kk += 2u) {
+				const float b = xs[(kk + h) * LW_SP_XS + f];
+				const float *row = as + (kk + h) * (2u * LW_SP_COLS) + tt * 32u + f;
+				re = __builtin_amdgcn_mfma_f32_32x32x2f32(row[0], b, re, 0, 0, 0);
+				im = __builtin_amdgcn_mfma_f32_32x32x2f32(row[LW_SP_COLS], b, im, 0, 0, 0);
+			}
+#pragma unroll
+			for (int r = 0; r < 16; r++)
+				st.acc[2 * tt][r] = re[r], st.acc[2 * tt + 1][r] = im[r];
+		}
+		return;
+	}
+#endif
+#pragma unroll
+	for (uint32_t tt = 0; tt < 2u; tt++) {
+		if (!lw_sp_tile_live(a, pass, wave, tt))
+			continue;
+		for (uint32_t kk = 0; kk < LW_SP_KT; kk++) {
+			const float b = xs[kk * LW_SP_XS + f];
+			const float *row = as + kk * (2u * LW_SP_COLS) + tt * 32u;
+#pragma unroll
+			for (uint32_t r = 0; r < 16u; r++) {
+				const uint32_t i = LW_SP_ROW(r, lane);
+				st.acc[2 * tt][r] = __builtin_fmaf(b, row[i], st.acc[2 * tt][r]);
+				st.acc[2 * tt + 1][r] = __builtin_fmaf(b, row[LW_SP_COLS + i], st.acc[2 * tt + 1][r]);
+			}
+		}
+	}
+}
+
+// ---- power: P = fmaf(im, im, re * re) of the pass into LDS, [bin of the pass][frame]
+LW_SP_FN void lw_sp_power(const LwSpecArgs &a, uint32_t pass, uint32_t tid, float *lds, const LwSpLane &st)
+{
+	const uint32_t lane = tid & 63u, wave = tid >> 6, f = lane & 31u;
+#pragma unroll
+	for (uint32_t tt = 0; tt < 2u; tt++) {
+		if (!lw_sp_tile_live(a, pass, wave, tt))
+			continue;
+#pragma unroll
+		for (uint32_t r = 0; r < 16u; r++) {
+			const float re = st.acc[2 * tt][r], im = st.acc[2 * tt + 1][r];
+			const float sq = re * re;
+			lds[LW_SP_LDS_P + (wave * 64u + tt * 32u + LW_SP_ROW(r, lane)) * LW_SP_TF + f] = __builtin_fmaf(im, im, sq);
+		}
+	}
+}
+
+// ---- without a mel matrix: the pass's bins from LDS to their lines, consecutive lanes on consecutive frames
+LW_SP_FN void lw_sp_store_power(const LwSpecArgs &a, const LwSpTile &t, uint32_t pass, uint32_t tid, const float *lds)
+{
+	const uint32_t f = tid % LW_SP_TF;
+	if (t.f0 + f >= t.n_frames)
+		return;
+	for (uint32_t c = tid / LW_SP_TF; c < LW_SP_COLS; c += LW_SP_THREADS / LW_SP_TF) {
+		const uint32_t bin = pass * LW_SP_COLS + c;
+		if (bin >= a.bins)
+			break;
+		a.dst[t.d_at + (uint64_t)bin * a.d_line + t.f0 + f] = lds[LW_SP_LDS_P + c * LW_SP_TF + f];
+	}
+}
+
+// ---- mel: slice jc (32 bins) of the pass; the matrix slice [32][mel_pad] into the basis tile's place, then the fold
+LW_SP_FN void lw_sp_stage_fb(const LwSpecArgs &a, uint32_t pass, uint32_t jc, uint32_t tid, float *lds)
+{
+	const uint32_t j0 = pass * LW_SP_COLS + jc * LW_SP_JT, n = LW_SP_JT * a.mel_pad / 4u; // <= 8 per lane
+	const LwSpF4 *g = (const LwSpF4 *)(a.fb + (size_t)j0 * a.mel_pad);
+	LwSpF4 v[8];
+#pragma unroll
+	for (uint32_t q = 0; q < 8u; q++) {
+		const uint32_t i = tid + q * LW_SP_THREADS;
+		v[q] = g[i < n ? i : n - 1u];
+	}
+	LwSpF4 *fs = (LwSpF4 *)(lds + LW_SP_LDS_A);
+#pragma unroll
+	for (uint32_t q = 0; q < 8u; q++) {
+		const uint32_t i = tid + q * LW_SP_THREADS;
+		if (i < n)
+			fs[i] = v[q];
+	}
+}
+
+LW_SP_FN void lw_sp_mel(const LwSpecArgs &a, uint32_t pass, uint32_t jc, uint32_t tid, const float *lds, LwSpLane &st)
+{
+	const uint32_t f = tid % LW_SP_TF, g = tid / LW_SP_TF, nb = a.mel_pad / 32u;
+	const uint32_t j0 = pass * LW_SP_COLS + jc * LW_SP_JT, nj = a.bins - j0 < LW_SP_JT ? a.bins - j0 : LW_SP_JT;
+	const float *ps = lds + LW_SP_LDS_P + jc * LW_SP_JT * LW_SP_TF + f;
+	for (uint32_t jj = 0; jj < nj; jj++) {
+		const float p = ps[jj * LW_SP_TF];
+		const LwSpF4 *w = (const LwSpF4 *)(lds + LW_SP_LDS_A + jj * a.mel_pad) + g;
+#pragma unroll
+		for (uint32_t b = 0; b < 8u; b++)
+			if (b < nb) {
+				const LwSpF4 w4 = w[8u * b];
+#pragma unroll
+				for (int i = 0; i < 4; i++)
+					st.mel[b][i] = __builtin_fmaf(p, w4.v[i], st.mel[b][i]);
+			}
+	}
+}
+
+LW_SP_FN void lw_sp_store_mel(const LwSpecArgs &a, const LwSpTile &t, uint32_t tid, const LwSpLane &st)
+{
+	const uint32_t f = tid % LW_SP_TF, g = tid / LW_SP_TF;
+	if (t.f0 + f >= t.n_frames)
+		return;
+#pragma unroll
+	for (uint32_t b = 0; b < 8u; b++)
+#pragma unroll
+		for (uint32_t i = 0; i < 4u; i++) {
+			const uint32_t q = 4u * (g + 8u * b) + i;
+			if (q < a.n_mels)
+				a.dst[t.d_at + (uint64_t)q * a.d_line + t.f0 + f] = st.mel[b][i];
+		}
+}
+
+// slices of the mel matrix that pass `pass` folds
+LW_SP_FN uint32_t lw_sp_slices(const LwSpecArgs &a, uint32_t pass)
+{
+	const uint32_t left = a.bins - pass * LW_SP_COLS, n = left < LW_SP_COLS ? left : LW_SP_COLS;
+	return (n + LW_SP_JT - 1u) / LW_SP_JT;
+}
+
+#ifndef LW_SPEC_HOST
+
+template <int ROUTE> __global__ void __launch_bounds__(LW_SP_THREADS) k_spec(LwSpecArgs a)
+{
+	extern __shared__ float lw_sp_lds[];
+	LwSpTile t;
+	if (!lw_sp_tile(a, blockIdx.x, blockIdx.y, blockIdx.z, t))
+		return; // (the whole workgroup: the tile is behind its row's last frame)
+	const uint32_t tid = threadIdx.x;
+	LwSpLane st;
+	lw_sp_zero_mel(st);
+	for (uint32_t pass = 0; pass < a.passes; pass++) {
+		lw_sp_zero_acc(st);
+		for (uint32_t kt = 0; kt < a.k_pad / LW_SP_KT; kt++) {
+			lw_sp_stage(a, t, pass, kt, tid, lw_sp_lds);
+			__syncthreads();
+			lw_sp_mma<ROUTE>(a, pass, tid, lw_sp_lds, st);
+			__syncthreads();
+		}
+		lw_sp_power(a, pass, tid, lw_sp_lds, st);
+		__syncthreads();
+		if (a.n_mels == 0) {
+			lw_sp_store_power(a, t, pass, tid, lw_sp_lds);
+			continue; // (the next pass's barriers stand between these reads and its power stores)
+		}
+		for (uint32_t jc = 0; jc < lw_sp_slices(a, pass); jc++) {
+			lw_sp_stage_fb(a, pass, jc, tid, lw_sp_lds);
+			__syncthreads();
+			lw_sp_mel(a, pass, jc, tid, lw_sp_lds, st);
+			__syncthreads();
+		}
+	}
+	if (a.n_mels)
+		lw_sp_store_mel(a, t, tid, st);
+}
+
+template <int ROUTE> static hipError_t lw_sp_launch(const LwSpecArgs &a, dim3 grid, hipStream_t st)
+{
+	static LwPerDeviceOnce once; // above the default limit of dynamic LDS: per device, once
+	const hipError_t e = once.run([] {
+		return hipFuncSetAttribute((const void *)k_spec<ROUTE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LW_SP_LDS_FLOATS * sizeof(float)));
+	});
+	if (e != hipSuccess)
+		return e;
+	return lw_launch_k(k_spec<ROUTE>, grid, dim3(LW_SP_THREADS), (size_t)LW_SP_LDS_FLOATS * sizeof(float), st, a);
+}
+
+hipError_t lw_launch_spec(const LwSpecArgs &a, int route, uint32_t tiles, uint32_t ch, uint32_t n_rows, hipStream_t st)
+{
+	if (tiles == 0 || n_rows == 0)
+		return hipSuccess;
+	if (ch == 0 || ch > 65535u || n_rows > 65535u || a.k_pad == 0 || a.k_pad % LW_SP_KT || a.mel_pad > 256u || a.mel_pad % 32u ||
+			(a.n_mels != 0 && !a.fb))
+		return hipErrorInvalidValue;
+	const dim3 grid(tiles, ch, n_rows);
+	return route == LW_SP_ROUTE_MFMA ? lw_sp_launch<LW_SP_ROUTE_MFMA>(a, grid, st)
+		: route == LW_SP_ROUTE_FMA ? lw_sp_launch<LW_SP_ROUTE_FMA>(a, grid, st) : hipErrorInvalidValue;
+}
+
+#endif // LW_SPEC_HOST

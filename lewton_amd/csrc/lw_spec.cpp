@@ -1,0 +1,249 @@
+// Spectral frames of rows (lw_spec_*, lw_spec_rows; include/lewton_amd.h "spectral frames of rows"): finished rows of f32 PCM
+// ([row][ch][sample] or [row][sample][ch] in device memory) cut into overlapping frames and turned into a power spectrum or mel
+// features, [row][ch][F][frame], by a windowed DFT whose basis and fold order are a contract on bits.  The basis is evaluated
+// here in double and rounded once; everything about a call is decided here on the host before anything is queued (the refusals,
+// the frame counts, the launch geometry); k_spec (lw_kernels_spec.hip) does the folds.  The call's per-row records travel through
+// pinned arrays in rotation, each guarded by an event, as lw_resample_rows' do.  Nothing else in the library calls into this file.
+#include "lw_internal.hpp"
+#include "lw_spec.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#define LW_SP_SLOTS 3 // record arrays in rotation: calls queued back to back do not wait for each other's kernels
+
+struct lw_sp_slot {
+	LwSpecRow *h = nullptr, *d = nullptr; // pinned / device, cap records each
+	size_t cap = 0;
+	hipEvent_t done = nullptr; // recorded behind the last launch that read d
+	bool pending = false;
+};
+
+struct lw_spec {
+	int device = 0;
+	uint32_t n_fft = 0, win_length = 0, hop = 0, n_mels = 0;
+	bool center = false;
+	LwSpecPlan plan{};
+	std::vector<float> basis;                  // [2][win_length][B], the public order
+	float *d_basis = nullptr, *d_fb = nullptr; // the kernel's orders (lw_spec.hpp)
+	lw_sp_slot slot[LW_SP_SLOTS];
+	unsigned next = 0;
+	int route = LW_SP_ROUTE_MFMA, last_route = -1;
+	std::vector<LwSpecRow> rows;
+	std::vector<uint64_t> taken;
+};
+
+extern "C" {
+
+lw_spec *lw_spec_create(int device, uint32_t n_fft, uint32_t win_length, uint32_t hop, int window, int center, uint32_t n_mels, const float *fb,
+		int *err)
+{
+	int dummy;
+	if (!err)
+		err = &dummy;
+	*err = LW_OK;
+	if (n_fft < 2 || n_fft > LW_SPEC_MAX_FFT || win_length < 1 || win_length > n_fft || hop < 1 || hop > 65535 || n_mels > LW_SPEC_MAX_MELS ||
+			(window != LW_SPEC_HANN && window != LW_SPEC_RECT)) {
+		*err = LW_ERR_UNSUPPORTED;
+		return nullptr;
+	}
+	if (n_mels && !fb) {
+		*err = LW_ERR_NULL_ARG;
+		return nullptr;
+	}
+	int ndev = 0, lds_limit = 0;
+	if (!lw_hip_ok(hipGetDeviceCount(&ndev), "hipGetDeviceCount") || device < 0 || device >= ndev || !lw_hip_ok(hipSetDevice(device), "hipSetDevice") ||
+			!lw_hip_ok(hipDeviceGetAttribute(&lds_limit, hipDeviceAttributeMaxSharedMemoryPerBlock, device), "hipDeviceGetAttribute(LDS per workgroup)") ||
+			(size_t)lds_limit < LW_SP_LDS_FLOATS * sizeof(float)) { // k_spec's workgroup does not fit this device
+		*err = LW_ERR_DEVICE;
+		return nullptr;
+	}
+	auto sp = std::make_unique<lw_spec>();
+	sp->device = device;
+	sp->n_fft = n_fft, sp->win_length = win_length, sp->hop = hop, sp->n_mels = n_mels, sp->center = center != 0;
+	const LwSpecPlan p = sp->plan = lw_spec_plan(n_fft, win_length, n_mels);
+	const uint32_t B = p.bins;
+	// ---- the tables, in double, each rounded once
+	sp->basis.resize((size_t)2 * win_length * B);
+	std::vector<float> dev((size_t)p.passes * p.k_pad * 2 * LW_SP_COLS, 0.0f);
+	for (uint32_t i = 0; i < win_length; i++) {
+		const double w = window == LW_SPEC_HANN ? 0.5 - 0.5 * std::cos(2.0 * M_PI * (double)i / (double)win_length) : 1.0;
+		const uint64_t k = (uint64_t)i + p.offset;
+		for (uint32_t j = 0; j < B; j++) {
+			const double ang = 2.0 * M_PI * (double)(k * j % n_fft) / (double)n_fft;
+			const float c = (float)(w * std::cos(ang)), s = (float)(-w * std::sin(ang));
+			sp->basis[(size_t)i * B + j] = c;
+			sp->basis[((size_t)win_length + i) * B + j] = s;
+			dev[lw_spec_basis_at(p, i, 0, j)] = c;
+			dev[lw_spec_basis_at(p, i, 1, j)] = s;
+		}
+	}
+	bool ok = lw_hip_ok(hipMalloc((void **)&sp->d_basis, dev.size() * sizeof(float)), "hipMalloc(spec basis)") &&
+		lw_hip_ok(hipMemcpy(sp->d_basis, dev.data(), dev.size() * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(spec basis)");
+	if (ok && n_mels) {
+		std::vector<float> m((size_t)p.j_pad * p.mel_pad, 0.0f);
+		for (uint32_t q = 0; q < n_mels; q++)
+			for (uint32_t j = 0; j < B; j++)
+				m[(size_t)j * p.mel_pad + q] = fb[(size_t)q * B + j];
+		ok = lw_hip_ok(hipMalloc((void **)&sp->d_fb, m.size() * sizeof(float)), "hipMalloc(spec mel matrix)") &&
+			lw_hip_ok(hipMemcpy(sp->d_fb, m.data(), m.size() * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(spec mel matrix)");
+	}
+	for (auto &sl : sp->slot)
+		ok = ok && lw_hip_ok(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming), "hipEventCreate(spec rows)");
+	if (!ok) {
+		*err = LW_ERR_DEVICE;
+		lw_spec_destroy(sp.release());
+		return nullptr;
+	}
+	return sp.release();
+}
+
+void lw_spec_destroy(lw_spec *sp)
+{
+	if (!sp)
+		return;
+	(void)hipSetDevice(sp->device);
+	(void)hipDeviceSynchronize();
+	for (auto &s : sp->slot) {
+		if (s.h)
+			(void)hipHostFree(s.h);
+		if (s.d)
+			(void)hipFree(s.d);
+		if (s.done)
+			(void)hipEventDestroy(s.done);
+	}
+	if (sp->d_basis)
+		(void)hipFree(sp->d_basis);
+	if (sp->d_fb)
+		(void)hipFree(sp->d_fb);
+	delete sp;
+}
+
+uint32_t lw_spec_bins(const lw_spec *sp)
+{
+	return sp ? sp->plan.bins : 0;
+}
+
+uint32_t lw_spec_features(const lw_spec *sp)
+{
+	return sp ? (sp->n_mels ? sp->n_mels : sp->plan.bins) : 0;
+}
+
+uint64_t lw_spec_frames(const lw_spec *sp, uint64_t len)
+{
+	return sp ? lw_spec_n_frames(len, sp->n_fft, sp->hop, sp->center) : 0;
+}
+
+size_t lw_spec_basis(const lw_spec *sp, float *dst)
+{
+	if (!sp)
+		return 0;
+	if (dst)
+		std::memcpy(dst, sp->basis.data(), sp->basis.size() * sizeof(float));
+	return sp->basis.size();
+}
+
+uint32_t lw_spec_tile_frames(const lw_spec *sp)
+{
+	return sp ? LW_SP_TF : 0;
+}
+
+int lw_spec_last_route(const lw_spec *sp)
+{
+	return sp ? sp->last_route : -1;
+}
+
+int lw_spec_set_route(lw_spec *sp, int route)
+{
+	if (!sp)
+		return LW_ERR_NULL_ARG;
+	if (route != LW_SP_ROUTE_MFMA && route != LW_SP_ROUTE_FMA)
+		return LW_ERR_UNSUPPORTED;
+	sp->route = route;
+	return LW_OK;
+}
+
+int lw_spec_rows(lw_spec *sp, int fmt, uint32_t ch, const void *d_src, size_t n_src_rows, size_t src_capacity, const uint64_t *len,
+		const uint32_t *dst_row, void *d_dst, size_t n_dst_rows, size_t frame_capacity, void *hip_stream)
+{
+	if (!sp || (!len && n_src_rows))
+		return LW_ERR_NULL_ARG;
+	if (fmt != LW_FMT_F32_PLANAR && fmt != LW_FMT_F32_INTERLEAVED)
+		return LW_ERR_UNSUPPORTED;
+	if (ch == 0 || ch > 255 || n_src_rows > UINT32_MAX)
+		return LW_ERR_CAPACITY;
+	const uint64_t F = sp->n_mels ? sp->n_mels : sp->plan.bins;
+	// both buffers must be addressable in 64 bits of BYTES
+	uint64_t e = 0;
+	if (__builtin_mul_overflow((uint64_t)ch, (uint64_t)src_capacity, &e) || __builtin_mul_overflow(e, (uint64_t)n_src_rows, &e) || e > UINT64_MAX / 4 ||
+			__builtin_mul_overflow((uint64_t)ch * F, (uint64_t)frame_capacity, &e) || __builtin_mul_overflow(e, (uint64_t)n_dst_rows, &e) ||
+			e > UINT64_MAX / 4)
+		return LW_ERR_CAPACITY;
+	// ---- plan: every row is checked before anything is queued, so a refused call has written nothing
+	sp->rows.clear();
+	sp->taken.clear();
+	uint64_t most = 0;
+	for (size_t i = 0; i < n_src_rows; i++) {
+		const uint64_t row = dst_row ? dst_row[i] : i;
+		if (len[i] > src_capacity || row >= n_dst_rows)
+			return LW_ERR_CAPACITY;
+		const uint64_t frames = lw_spec_n_frames(len[i], sp->n_fft, sp->hop, sp->center);
+		if (frames > frame_capacity)
+			return LW_ERR_CAPACITY;
+		sp->rows.push_back(LwSpecRow{len[i], frames, row});
+		sp->taken.push_back(row);
+		most = std::max(most, frames);
+	}
+	std::sort(sp->taken.begin(), sp->taken.end());
+	if (std::adjacent_find(sp->taken.begin(), sp->taken.end()) != sp->taken.end())
+		return LW_ERR_CAPACITY; // two source rows for one destination row
+	if (most && (!d_src || !d_dst)) // (a row with a frame has a sample)
+		return LW_ERR_NULL_ARG;
+	const uint64_t tiles = (most + LW_SP_TF - 1) / LW_SP_TF;
+	if (tiles > INT32_MAX)
+		return LW_ERR_CAPACITY;
+	if (most == 0)
+		return LW_OK;
+	// ---- queue: the records, then one launch per 65535 rows
+	HIP_TRY(hipSetDevice(sp->device));
+	hipStream_t st = (hipStream_t)hip_stream;
+	lw_sp_slot &s = sp->slot[sp->next];
+	if (s.pending) { // an earlier call's copy of these records may still be on its way
+		HIP_TRY(hipEventSynchronize(s.done));
+		s.pending = false;
+	}
+	if (s.cap < n_src_rows) {
+		if (s.h)
+			(void)hipHostFree(s.h);
+		if (s.d)
+			(void)hipFree(s.d);
+		s.h = s.d = nullptr;
+		s.cap = 0;
+		const size_t cap = std::max<size_t>(n_src_rows, 64);
+		HIP_TRY(hipHostMalloc((void **)&s.h, cap * sizeof(LwSpecRow), 0));
+		HIP_TRY(hipMalloc((void **)&s.d, cap * sizeof(LwSpecRow)));
+		s.cap = cap;
+	}
+	std::memcpy(s.h, sp->rows.data(), n_src_rows * sizeof(LwSpecRow));
+	HIP_TRY(hipMemcpyAsync(s.d, s.h, n_src_rows * sizeof(LwSpecRow), hipMemcpyHostToDevice, st));
+	const bool itl = fmt == LW_FMT_F32_INTERLEAVED;
+	const LwSpecPlan &p = sp->plan;
+	LwSpecArgs a{};
+	a.src = (const float *)d_src, a.dst = (float *)d_dst, a.basis = sp->d_basis, a.fb = sp->d_fb, a.rows = s.d;
+	a.s = itl ? LwSpecLayout{(uint64_t)src_capacity * ch, 1, ch} : LwSpecLayout{(uint64_t)src_capacity * ch, src_capacity, 1};
+	a.d_line = frame_capacity, a.d_ch = F * frame_capacity, a.d_row = a.d_ch * ch;
+	a.lead = (int64_t)p.offset - (int64_t)(sp->center ? sp->n_fft / 2 : 0);
+	a.hop = sp->hop, a.win_length = sp->win_length, a.k_pad = p.k_pad, a.bins = p.bins, a.passes = p.passes, a.n_mels = sp->n_mels, a.mel_pad = p.mel_pad;
+	for (size_t r0 = 0; r0 < n_src_rows; r0 += 65535) {
+		a.row0 = (uint32_t)r0;
+		HIP_TRY(lw_launch_spec(a, sp->route, (uint32_t)tiles, ch, (uint32_t)std::min<size_t>(n_src_rows - r0, 65535), st));
+	}
+	HIP_TRY(hipEventRecord(s.done, st));
+	s.pending = true;
+	sp->last_route = sp->route;
+	sp->next = (sp->next + 1) % LW_SP_SLOTS;
+	return LW_OK;
+}
+
+} // extern "C"

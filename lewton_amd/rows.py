@@ -23,6 +23,12 @@ windowed-sinc polyphase filter specified bit for bit, f32 formats), and files of
     pcm, lengths, rate = decode_ogg_files(paths, channels="mono", sample_rate=16000)
     rs = Resampler(44100, 16000); out = rs.run(tensor, lengths)             # the same pass over a caller's own rows tensor
 
+Spectrogram turns finished rows into a power spectrum or (log-)mel features on the GPU (lw_spec_rows, k_spec in
+csrc/lw_kernels_spec.hip: a windowed DFT on the f32 matrix instruction, specified bit for bit), the step between the waveform and
+a speech model's input:
+
+    sp = Spectrogram(400, 160, mel=mel_filterbank(16000, 400, 80)); feats, frames = sp.run(pcm, lengths, log="log10")
+
 torch is imported inside the functions, never at module import.
 """
 import ctypes as C
@@ -360,6 +366,202 @@ class Resampler:
         if rc:
             raise RuntimeError("lw_resample_rows: %d %s" % (rc, N.device_error()))
         return out
+
+
+_SPEC_WINDOWS = {"hann": 0, "rect": 1}      # LW_SPEC_HANN, LW_SPEC_RECT
+SPEC_MAX_FFT, SPEC_MAX_MELS = 2048, 256     # LW_SPEC_MAX_FFT, LW_SPEC_MAX_MELS
+
+
+def _mel_scale(f, scale):
+    f = np.asarray(f, np.float64)
+    if scale == "htk":
+        return 2595.0 * np.log10(1.0 + f / 700.0)
+    with np.errstate(divide="ignore"):
+        return np.where(f < 1000.0, f / (200.0 / 3), 15.0 + np.log(np.maximum(f, 1e-300) / 1000.0) / (np.log(6.4) / 27.0))
+
+
+def _mel_inverse(m, scale):
+    m = np.asarray(m, np.float64)
+    if scale == "htk":
+        return 700.0 * (10.0 ** (m / 2595.0) - 1.0)
+    return np.where(m < 15.0, m * (200.0 / 3), 1000.0 * np.exp((m - 15.0) * (np.log(6.4) / 27.0)))
+
+
+def mel_filterbank(sample_rate, n_fft, n_mels, fmin=0.0, fmax=None, scale="htk", norm=None):
+    """[n_mels][n_fft // 2 + 1] float32 triangular filters, computed in float64 and rounded once: n_mels + 2 points p equally
+    spaced on the mel scale from fmin to fmax (sample_rate / 2 when None); the weight of bin frequency f_j = j * sample_rate /
+    n_fft in row q is max(0, min((f_j - p[q]) / (p[q+1] - p[q]), (p[q+2] - f_j) / (p[q+2] - p[q+1]))).  scale: "htk"
+    (2595 log10(1 + f / 700)) or "slaney" (f / (200 / 3) below 1000 Hz, 15 + ln(f / 1000) / (ln(6.4) / 27) above); norm="slaney"
+    multiplies row q by 2 / (p[q+2] - p[q]).  Needs no GPU."""
+    if scale not in ("htk", "slaney"):
+        raise ValueError("scale=%r: \"htk\" or \"slaney\"" % (scale,))
+    if norm not in (None, "slaney"):
+        raise ValueError("norm=%r: None or \"slaney\"" % (norm,))
+    if isinstance(n_mels, bool) or not isinstance(n_mels, (int, np.integer)) or not 1 <= n_mels <= SPEC_MAX_MELS:
+        raise ValueError("n_mels=%r: 1 .. %d" % (n_mels, SPEC_MAX_MELS))
+    if isinstance(n_fft, bool) or not isinstance(n_fft, (int, np.integer)) or not 2 <= n_fft <= SPEC_MAX_FFT:
+        raise ValueError("n_fft=%r: 2 .. %d" % (n_fft, SPEC_MAX_FFT))
+    if fmax is None:
+        fmax = sample_rate / 2.0
+    if not (sample_rate > 0 and 0 <= fmin < fmax):
+        raise ValueError("0 <= fmin < fmax and sample_rate > 0 are required")
+    p = _mel_inverse(np.linspace(_mel_scale(fmin, scale), _mel_scale(fmax, scale), int(n_mels) + 2), scale)
+    f = np.arange(int(n_fft) // 2 + 1, dtype=np.float64) * (float(sample_rate) / int(n_fft))
+    up = (f[None, :] - p[:-2, None]) / (p[1:-1] - p[:-2])[:, None]
+    down = (p[2:, None] - f[None, :]) / (p[2:] - p[1:-1])[:, None]
+    w = np.maximum(0.0, np.minimum(up, down))
+    if norm == "slaney":
+        w = w * (2.0 / (p[2:] - p[:-2]))[:, None]
+    return w.astype(np.float32)
+
+
+def _spec_params(n_fft, hop, win_length, window, mel):
+    """(win_length, the mel matrix as contiguous float32 or None), or ValueError for what lw_spec_create refuses"""
+    for name, v, lo, hi in (("n_fft", n_fft, 2, SPEC_MAX_FFT), ("hop", hop, 1, 65535)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ValueError("%s=%r: an integer in %d .. %d" % (name, v, lo, hi))
+    if win_length is None:
+        win_length = n_fft
+    if isinstance(win_length, bool) or not isinstance(win_length, (int, np.integer)) or not 1 <= win_length <= n_fft:
+        raise ValueError("win_length=%r: an integer in 1 .. n_fft" % (win_length,))
+    if window not in _SPEC_WINDOWS:
+        raise ValueError("window=%r: \"hann\" or \"rect\"" % (window,))
+    if mel is not None:
+        mel = np.ascontiguousarray(mel, np.float32)
+        if mel.ndim != 2 or mel.shape[1] != n_fft // 2 + 1 or not 1 <= mel.shape[0] <= SPEC_MAX_MELS:
+            raise ValueError("mel= must be [n_mels <= %d][n_fft // 2 + 1 = %d], not %r" % (SPEC_MAX_MELS, n_fft // 2 + 1, mel.shape))
+    return int(win_length), mel
+
+
+class Spectrogram:
+    """lw_spec: rows of f32 PCM -> power spectrum or mel features on the GPU (k_spec), by the windowed DFT of
+    include/lewton_amd.h ("spectral frames of rows"), a contract on bits.  window: "hann" (periodic) or "rect"; win_length: n_fft
+    when None; mel: None for the power spectrum [n_fft // 2 + 1 lines], or a matrix [n_mels][n_fft // 2 + 1] (mel_filterbank).
+    Parameter errors are ValueError and need no GPU; the object itself lives on cuda:device."""
+
+    def __init__(self, n_fft=400, hop=160, win_length=None, window="hann", center=True, mel=None, device=0):
+        self.win_length, self._mel = _spec_params(n_fft, hop, win_length, window, mel)
+        self.n_fft, self.hop, self.center, self.device = int(n_fft), int(hop), bool(center), device
+        _gpu()
+        err = C.c_int(0)
+        n_mels = 0 if self._mel is None else self._mel.shape[0]
+        self._h = N.lw_spec_create(device, self.n_fft, self.win_length, self.hop, _SPEC_WINDOWS[window], int(self.center), n_mels,
+                                   None if self._mel is None else self._mel.ctypes.data_as(C.c_void_p), C.byref(err))
+        if not self._h:
+            if err.value in (N.ERR_UNSUPPORTED, N.ERR_NULL_ARG):
+                raise ValueError("lw_spec_create refused the parameters")
+            raise RuntimeError("lw_spec_create failed (%d): %s" % (err.value, N.device_error()))
+        assert self.bins == self.n_fft // 2 + 1 and self.features == (n_mels or self.bins)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            N.lw_spec_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        if N is not None and getattr(N, "lw_spec_destroy", None) is not None:  # not during interpreter shutdown
+            self.close()
+
+    @property
+    def bins(self):
+        return int(N.lw_spec_bins(self._h))
+
+    @property
+    def features(self):
+        """lines per row and channel of the output: n_mels, or bins without a mel matrix"""
+        return int(N.lw_spec_features(self._h))
+
+    @property
+    def tile_frames(self):
+        return int(N.lw_spec_tile_frames(self._h))
+
+    def frames(self, n):
+        """frames of a row of n samples (lw_spec_frames)"""
+        return int(N.lw_spec_frames(self._h, int(n)))
+
+    def basis(self):
+        """[2][win_length][bins] float32: C, then S, the window folded in"""
+        out = np.empty((2, self.win_length, self.bins), np.float32)
+        assert N.lw_spec_basis(self._h, None) == out.size
+        N.lw_spec_basis(self._h, out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def last_route(self):
+        """0: the DFT fold ran on the matrix cores, 1: per-lane fmaf chains, -1: no call yet (lw_spec_last_route)"""
+        return N.lw_spec_last_route(self._h)
+
+    def set_route(self, route):
+        if N.lw_spec_set_route(self._h, int(route)):
+            raise ValueError("lw_spec_set_route refused route %r" % (route,))
+
+    def check_tensor(self, tensor, samples, what):
+        """(n_rows, channels, row_capacity) of a source rows tensor, or ValueError: as Resampler.check_tensor"""
+        torch = _gpu()
+        if tensor.dtype != torch.float32:
+            raise ValueError("%s is %s, the spectrogram works on float32" % (what, tensor.dtype))
+        if tensor.device.type != "cuda" or tensor.device.index != self.device:
+            raise ValueError("%s is on %s, the spectrogram on cuda:%d" % (what, tensor.device, self.device))
+        if not tensor.is_contiguous():
+            raise ValueError("%s is not contiguous" % what)
+        if tensor.dim() != 3:
+            raise ValueError("%s must have three dimensions, not %d" % (what, tensor.dim()))
+        b, x, y = tensor.shape
+        return (b, y, x) if N.fmt_interleaved(_FMT[samples]) else (b, x, y)
+
+    def run(self, src, lengths, out=None, rows=None, stream=None, samples="f32", log=None, floor=1e-10):
+        """lw_spec_rows: row i of src ([B, C, T], or [B, T, C] for samples="f32_interleaved"), lengths[i] samples per channel,
+        -> row rows[i] of out (None: row i), float32 [rows][C][features][frame capacity], frames(lengths[i]) frames of each
+        line; nothing else of out is written.  out=None: a zeroed tensor of max(rows) + 1 rows and the largest frame count.
+        log: None, "ln" or "log10" -- log(max(x, floor)), applied by torch behind the kernel (plumbing: not part of the bit
+        contract).  Only the written positions change, but the step is one torch.where over out[..., :max(frames)] that stores the
+        other positions back unchanged: with log=, nothing else may read or write ANY row of out on another stream meanwhile.  stream: a hipStream_t value; None = torch's current stream on the object's
+        device.  Asynchronous; returns (out, frames), frames an int64 host tensor with one count per row of src."""
+        torch = _gpu()
+        fmt = _FMT[samples]
+        if fmt not in (N.FMT_F32_PLANAR, N.FMT_F32_INTERLEAVED):
+            raise ValueError("the spectrogram works on the f32 formats, not %r" % (samples,))
+        if log not in (None, "ln", "log10"):
+            raise ValueError("log=%r: None, \"ln\" or \"log10\"" % (log,))
+        n_src, ch, cap = self.check_tensor(src, samples, "src")
+        lens = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+        if len(lens) != n_src or any(v < 0 for v in lens):
+            raise ValueError("lengths= needs one non-negative entry per row of src")
+        frames = [self.frames(v) for v in lens]
+        lens = np.asarray(lens, np.uint64)
+        rmap = None
+        if rows is not None:
+            rows = [int(v) for v in (rows.tolist() if hasattr(rows, "tolist") else rows)]
+            if len(rows) != n_src or any(not 0 <= v < 1 << 32 for v in rows):
+                raise ValueError("rows= needs one destination row per row of src")
+            rmap = np.asarray(rows, np.uint32)
+        F = self.features
+        if out is None:
+            n_dst = max(rows) + 1 if rows else n_src
+            out = torch.zeros((n_dst, ch, F, max(frames, default=0)), dtype=torch.float32, device="cuda:%d" % self.device)
+        if out.dtype != torch.float32 or out.device.type != "cuda" or out.device.index != self.device or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32 tensor on cuda:%d" % self.device)
+        if out.dim() != 4 or out.shape[1] != ch or out.shape[2] != F:
+            raise ValueError("out must be [rows][%d channels][%d features][frames], not %r" % (ch, F, tuple(out.shape)))
+        n_dst, fcap = out.shape[0], out.shape[3]
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream or None
+        rc = N.lw_spec_rows(self._h, fmt, ch, C.c_void_p(src.data_ptr()), n_src, cap, lens.ctypes.data_as(C.c_void_p),
+                            None if rmap is None else rmap.ctypes.data_as(C.c_void_p), C.c_void_p(out.data_ptr()), n_dst, fcap, stream)
+        if rc in (N.ERR_NULL_ARG, N.ERR_CAPACITY, N.ERR_UNSUPPORTED):
+            raise ValueError("lw_spec_rows refused the call (%d)" % rc)
+        if rc:
+            raise RuntimeError("lw_spec_rows: %d %s" % (rc, N.device_error()))
+        if log is not None and n_dst and max(frames, default=0):
+            per_row = [0] * n_dst
+            for i, n in enumerate(frames):
+                per_row[rows[i] if rows else i] = n
+            with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=self.device) if stream else torch.cuda.default_stream(self.device)):
+                count = torch.tensor(per_row, dtype=torch.int64).to(out.device)
+                part = out[:, :, :, :max(frames)]                        # no frame of this call lies beyond
+                written = torch.arange(part.shape[3], device=out.device)[None, None, None, :] < count[:, None, None, None]
+                x = torch.clamp(part, min=float(floor))
+                part.copy_(torch.where(written, torch.log(x) if log == "ln" else torch.log10(x), part))
+        return out, torch.tensor(frames, dtype=torch.int64)
 
 
 def _round_up(n, to):
