@@ -361,7 +361,15 @@ int lw_resampler_set_taps_in_lds(lw_resampler *rs, int on);
  *   frames  pad = center ? n_fft / 2 : 0.  n_frames(len), in 64-bit integers: 0 for len == 0; 1 + len / hop when centred;
  *           otherwise len < n_fft ? 0 : 1 + (len - n_fft) / hop.  Sample k of frame t is x[t * hop - pad + k] (signed 64-bit
  *           index); x[i] = +0.0 for i < 0 and for i >= len -- len, not the capacity: what the source holds between len and its
- *           capacity never reaches the output, and no byte beyond the capacity is read.  Reflect padding is not offered.
+ *           capacity never reaches the output, and no byte beyond the capacity is read.
+ *   reflect   With LW_SPEC_PAD_REFLECT (centred objects only; LW_SPEC_PAD_ZERO, the rule above, is what a new object has):
+ *           x[i] = x[-i] for i < 0 and x[i] = x[2 (len - 1) - i] for i >= len, one reflection that does not repeat the edge sample,
+ *           as numpy.pad(mode="reflect"); the indices are 64-bit integers.  Frame counts, basis, chains and what is written are
+ *           unchanged.  One reflection must reach every support sample of every frame, so a row with
+ *           0 < len < n_fft - n_fft / 2 + 1 (integer division) is refused; len == 0 still yields no frames.  For even n_fft that
+ *           is len > n_fft / 2, torch.stft's own condition.  For odd n_fft it is one sample stricter than torch's, and n_frames
+ *           stays 1 + len / hop: torch.stft yields one frame fewer when hop divides len (its padded row is one sample short
+ *           of that frame), the frames both compute are the same.
  *   spectrum  re[j]: acc = +0.0; for k ascending over the support acc = fmaf(x_k, C[k][j], acc).  im[j]: the same with S.
  *           P[j] = fmaf(im, im, re * re), the product re * re one rounded f32 multiply.
  *   mel     (n_mels > 0) fb is the caller's matrix, n_mels x B host floats, fb[q * B + j], copied at creation.
@@ -376,11 +384,12 @@ int lw_resampler_set_taps_in_lds(lw_resampler *rs, int on);
  * are HOST arrays, copied during the call.  Asynchronous on hip_stream; calls on one object may be queued back to back.
  * Refusals, decided on the host before anything is queued, so a refused call has written nothing:
  *   LW_ERR_NULL_ARG     sp NULL, len NULL with rows, d_src / d_dst NULL with frames to compute; (create) fb NULL with n_mels > 0
- *   LW_ERR_UNSUPPORTED  (create) a parameter outside the limits above, an unknown window;  (rows) an i16 format
+ *   LW_ERR_UNSUPPORTED  (create) a parameter outside the limits above, an unknown window;  (rows) an i16 format;
+ *                       (set_pad_mode) an unknown mode, reflect on an object that is not centred
  *   LW_ERR_DEVICE       (create) no such device, or its LDS per workgroup is below the 67 648 bytes k_spec needs (asked of the
  *                       device, not assumed)
  *   LW_ERR_CAPACITY     len[i] > src_capacity, n_frames(len[i]) > frame_capacity, dst_row[i] >= n_dst_rows, two source rows for
- *                       one destination row, ch == 0 or > 255 */
+ *                       one destination row, ch == 0 or > 255, a row too short for one reflection under LW_SPEC_PAD_REFLECT */
 typedef struct lw_spec lw_spec;
 enum { LW_SPEC_HANN = 0, LW_SPEC_RECT = 1 };
 #define LW_SPEC_MAX_FFT 2048
@@ -401,6 +410,63 @@ int lw_spec_rows(lw_spec *sp, int fmt, uint32_t ch, const void *d_src, size_t n_
  * build does not have. */
 int lw_spec_last_route(const lw_spec *sp);
 int lw_spec_set_route(lw_spec *sp, int route);
+/* what x[i] is outside [0, len) for the calls that follow ("reflect" above); lw_spec_pad_mode: the mode, -1 for NULL */
+enum { LW_SPEC_PAD_ZERO = 0, LW_SPEC_PAD_REFLECT = 1 };
+int lw_spec_set_pad_mode(lw_spec *sp, int mode);
+int lw_spec_pad_mode(const lw_spec *sp);
+
+/* ---- finishing feature rows ------------------------------------------------------------------------------------------------
+ * Log compression, dynamic-range clamp, affine map and fill of finished feature rows, on the GPU, as a pass of its own (k_feat):
+ * what stands between lw_spec_rows' output and a speech model's input (Whisper: log10, floor 1e-10, top 8, add 4, mul 0.25, the
+ * scope a row, filled to 3000 frames).  Source and destination are f32 [row][ch][F][frame_capacity], lw_spec_rows' layout;
+ * row i has n_frames[i] frames.  A contract on BITS.  For element x of a line at frame t < n_frames[row]:
+ *   1  v = (x > floor) ? x : floor.  A NaN and everything at or below the floor become the floor; v is never NaN.
+ *   2  l = LOG(v).  LW_FEAT_LOG_NONE: l = v.  Otherwise v = +inf gives +inf, and any other v (positive and finite, see the
+ *      refusals) goes through double arithmetic in which every * + - / is ONE correctly rounded IEEE operation, nothing fused:
+ *        d = (double)v (exact, a subnormal f32 included);  d = m * 2^e with m in [0.5, 1) (frexp);
+ *        if m < RH = 0x1.6a09e667f3bcdp-1 (the double nearest sqrt(1/2)): m = m * 2, e = e - 1
+ *        s = (m - 1) / (m + 1),  z = s * s
+ *        p = c9; for k = 8 .. 0: p = p * z + c_k, with c_k = 1.0 / (2 k + 1) the correctly rounded quotient
+ *        r = (double)e * LN2 + (s + s) * p,  LN2 = 0x1.62e42fefa39efp-1
+ *      LW_FEAT_LOG_LN: r.  LW_FEAT_LOG_LOG10: r * LOG10E, LOG10E = 0x1.bcb7b1526e50ep-2.  LW_FEAT_LOG_DB: (r * LOG10E) * 10.0.
+ *      Then ONE rounding to f32.  (The series' truncation error is about 2e-17 relative, so l is the correctly rounded f32
+ *      logarithm on all but a vanishing share of inputs, and the same bits on every machine with IEEE doubles.)
+ *   3  M = the maximum of l over the scope: LW_FEAT_SCOPE_ROW, all ch * F lines of the row, frames [0, n_frames);
+ *      LW_FEAT_SCOPE_CHANNEL, the F lines of the channel.  l is never NaN, and +0.0 counts as greater than -0.0, so the order
+ *      cannot matter.  An empty scope (n_frames == 0) has M = l0 = LOG(floor) (LW_FEAT_LOG_NONE: l0 = floor).
+ *   4  tt = M - top, one rounded f32 subtraction; top == +inf: tt = -inf whatever M is (no clamp).  y = (l > tt) ? l : tt.
+ *   5  z = (y + add) * mul, two rounded f32 operations.  (Whisper's (x + 4) / 4: add = 4, mul = 0.25, exact.)
+ * Positions [n_frames, max(n_frames, fill_to[row])) of every line receive what x = floor would give (steps 2 - 5 with the
+ * scope's M); they take no part in M.  Nothing else of d_dst is written, and nothing of d_src beyond n_frames of a line is read.
+ * d_max, when given, receives M per scope: f32 [n_rows] (row scope) or [n_rows][ch], rows with nothing written included.  Which
+ * NaN a NaN result is, is outside the contract (z can be one, inf * 0); every other bit is inside it, the sign of a zero included.
+ * d_src == d_dst is allowed (in place); any other overlap is the caller's error.
+ *
+ * lw_feat_rows: n_frames and fill_to (may be NULL: nothing is filled) are HOST arrays, copied during the call.  Asynchronous on
+ * hip_stream; calls on one object may be queued back to back.  Two kernel launches on the stream (the second combines the
+ * tiles' maxima and re-reads the l the first one stored in d_dst); one when top == +inf and d_max is NULL.
+ * lw_feat_last_launches: the kernels the last accepted call queued, -1 = no call yet.  lw_feat_log: step 2 for one value on the
+ * host (NaN for a v that step 1 cannot produce: NaN, or not positive under a log kind).
+ * Refusals, decided on the host before anything is queued:
+ *   LW_ERR_NULL_ARG     ft or p NULL, n_frames NULL with rows, d_src NULL with frames to read, d_dst NULL with elements to write
+ *   LW_ERR_UNSUPPORTED  (create) an unknown log or scope; a log kind with a floor that is not a positive finite f32 (a subnormal
+ *                       is fine); floor NaN; top NaN or negative; add or mul NaN
+ *   LW_ERR_DEVICE       (create) no such device
+ *   LW_ERR_CAPACITY     n_frames[i] or fill_to[i] > frame_capacity, ch == 0 or > 255, F == 0 or > 65535, a buffer that 64 bits of
+ *                       bytes cannot address, more than 2^32 - 1 runs of 256 frames in one channel */
+typedef struct lw_feat lw_feat;
+enum { LW_FEAT_LOG_NONE = 0, LW_FEAT_LOG_LN = 1, LW_FEAT_LOG_LOG10 = 2, LW_FEAT_LOG_DB = 3 };
+enum { LW_FEAT_SCOPE_ROW = 0, LW_FEAT_SCOPE_CHANNEL = 1 };
+typedef struct {
+	int32_t log, scope;
+	float floor, top, add, mul;
+} lw_feat_params;
+lw_feat *lw_feat_create(int device, const lw_feat_params *p, int *err);
+void lw_feat_destroy(lw_feat *ft);
+float lw_feat_log(const lw_feat *ft, float v);
+int lw_feat_rows(lw_feat *ft, uint32_t ch, uint32_t F, const void *d_src, void *d_dst, size_t n_rows, size_t frame_capacity,
+		const uint64_t *n_frames, const uint64_t *fill_to, float *d_max, void *hip_stream);
+int lw_feat_last_launches(const lw_feat *ft);
 
 /* ---- staging ring (BASELINE north_star: "pinned hipMemcpyAsync staging ring so entropy decode of packet N+1 overlaps
  * GPU synthesis of packet N") ------------------------------------------------------------------------------------------

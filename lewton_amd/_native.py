@@ -53,6 +53,10 @@ class RowMix(C.Structure):
     _fields_ = [("out_ch", C.c_uint32), ("in_ch", C.c_uint32), ("coef", C.c_void_p)]
 
 
+class FeatParams(C.Structure):
+    _fields_ = [("log", C.c_int32), ("scope", C.c_int32), ("floor", C.c_float), ("top", C.c_float), ("add", C.c_float), ("mul", C.c_float)]
+
+
 class OggPacket(C.Structure):
     _fields_ = [("data", C.c_void_p), ("len", C.c_size_t), ("stream_serial", C.c_uint32), ("absgp_page", C.c_uint64),
                 ("first_in_stream", C.c_uint8), ("last_in_stream", C.c_uint8), ("first_in_page", C.c_uint8),
@@ -161,6 +165,14 @@ SYMBOLS = {
                                C.c_size_t, C.c_size_t, C.c_void_p]),
     "lw_spec_last_route": (C.c_int, [C.c_void_p]),
     "lw_spec_set_route": (C.c_int, [C.c_void_p, C.c_int]),
+    "lw_spec_set_pad_mode": (C.c_int, [C.c_void_p, C.c_int]),
+    "lw_spec_pad_mode": (C.c_int, [C.c_void_p]),
+    "lw_feat_create": (C.c_void_p, [C.c_int, C.POINTER(FeatParams), intp]),
+    "lw_feat_destroy": (None, [C.c_void_p]),
+    "lw_feat_log": (C.c_float, [C.c_void_p, C.c_float]),
+    "lw_feat_rows": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_void_p]),
+    "lw_feat_last_launches": (C.c_int, [C.c_void_p]),
     "lw_ring_create": (C.c_void_p, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, intp]),
     "lw_ring_destroy": (None, [C.c_void_p]),
     "lw_ring_stage": (C.c_int, [C.c_void_p, C.POINTER(Packet), C.c_size_t, C.c_int]),
@@ -241,6 +253,9 @@ OGG_EOF, OGG_NO_CAPTURE_PATTERN, OGG_INVALID_STREAM_STRUCT_VER, OGG_HASH_MISMATC
 OGG_READ_ERROR, OGG_INVALID_DATA = 52, 53
 FMT_I16_PLANAR, FMT_I16_INTERLEAVED, FMT_F32_PLANAR, FMT_F32_INTERLEAVED = 0, 1, 2, 3
 RESAMPLE_HANN, RESAMPLE_KAISER, RESAMPLE_MAX_TAPS = 0, 1, 65536
+SPEC_PAD_ZERO, SPEC_PAD_REFLECT = 0, 1
+FEAT_LOG_NONE, FEAT_LOG_LN, FEAT_LOG_LOG10, FEAT_LOG_DB = 0, 1, 2, 3
+FEAT_SCOPE_ROW, FEAT_SCOPE_CHANNEL = 0, 1
 
 
 def fmt_dtype(fmt):

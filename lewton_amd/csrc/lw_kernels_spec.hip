@@ -3,7 +3,8 @@
 // [row][ch][F][frame], by the rule of include/lewton_amd.h ("spectral frames of rows"), bit for bit:
 //   re[j] = fold over the window's support, k ascending, of fmaf(x_k, C[k][j], acc) from +0.0;  im[j] likewise with S
 //   P[j]  = fmaf(im, im, re * re);  m[q] = fold over j = 0 .. B - 1 ascending of fmaf(P[j], fb[q][j], acc) from +0.0
-//   x = +0.0 outside [0, len).  No chain is ever split; the unit is compiled with -ffp-contract=off like all others.
+//   x = +0.0 outside [0, len), or the reflected sample (LW_SPEC_PAD_REFLECT, lw_sp_reflect).  No chain is ever split; the unit is
+//   compiled with -ffp-contract=off like all others.
 //
 // Work: a tile = LW_SP_TF = 32 consecutive frames of one (row, channel), one workgroup of 256 lanes (four waves) per tile, grid =
 // (tiles, channels, rows).  The framed DFT is a GEMM, D[bin][frame] = sum_k basis[k][bin] * x[frame * hop + k], run on
@@ -74,10 +75,24 @@ LW_SP_FN int64_t lw_sp_index(const LwSpecArgs &a, const LwSpTile &t, uint32_t f,
 	return t.x0 + (int64_t)((uint64_t)f * a.hop) + (int64_t)k;
 }
 
-// x[i] of the tile's row and channel, +0.0 outside [0, len): the load goes to a clamped index (len >= 1 wherever a tile exists), so
-// it is branch-free, never leaves [0, len), and what lies between len and the capacity is never fetched
-LW_SP_FN float lw_sp_x(const LwSpecArgs &a, const LwSpTile &t, int64_t i)
+// where x[i] is read under reflect padding: i itself inside [0, len), -i below, 2 (len - 1) - i from len on, in 64-bit integers
+// (one reflection: the host has refused rows for which a support sample would need a second one).  Selects, no branch
+LW_SP_FN int64_t lw_sp_reflect(const LwSpTile &t, int64_t i)
 {
+	const int64_t up = i < 0 ? -i : i;
+	return (uint64_t)up >= t.len ? 2 * ((int64_t)t.len - 1) - up : up;
+}
+
+// x[i] of the tile's row and channel; outside [0, len) +0.0, or the reflected sample: the load goes to a clamped index (len >= 1
+// wherever a tile exists), so it is branch-free, never leaves [0, len), and what lies between len and the capacity is never
+// fetched.  PAD is the pad mode as a compile-time constant -- the kernel is instantiated per mode: a test of a.pad_mode here
+// becomes a uniform branch between a lane's loads and ends their overlap -- or LW_SP_PAD_ARGS: as a.pad_mode says
+// (the host programs, which call lw_sp_stage without it)
+#define LW_SP_PAD_ARGS (-1)
+template <int PAD> LW_SP_FN float lw_sp_x(const LwSpecArgs &a, const LwSpTile &t, int64_t i)
+{
+	if (PAD == 1 || (PAD == LW_SP_PAD_ARGS && a.pad_mode))
+		i = lw_sp_reflect(t, i);
 	const bool in = i >= 0 && (uint64_t)i < t.len;
 	const uint64_t c = i < 0 ? 0 : (uint64_t)i < t.len ? (uint64_t)i : t.len - 1;
 	const float v = a.src[t.s_at + c * a.s.el];
@@ -107,7 +122,7 @@ LW_SP_FN void lw_sp_zero_mel(LwSpLane &st)
 }
 
 // ---- stage: K tile kt of pass `pass` into LDS; all of a lane's loads are in flight before its first store
-LW_SP_FN void lw_sp_stage(const LwSpecArgs &a, const LwSpTile &t, uint32_t pass, uint32_t kt, uint32_t tid, float *lds)
+template <int PAD = LW_SP_PAD_ARGS> LW_SP_FN void lw_sp_stage(const LwSpecArgs &a, const LwSpTile &t, uint32_t pass, uint32_t kt, uint32_t tid, float *lds)
 {
 	const uint32_t k0 = kt * LW_SP_KT;
 	const LwSpF4 *g = (const LwSpF4 *)(a.basis + ((size_t)pass * a.k_pad + k0) * (2u * LW_SP_COLS));
@@ -121,7 +136,7 @@ LW_SP_FN void lw_sp_stage(const LwSpecArgs &a, const LwSpTile &t, uint32_t pass,
 #pragma unroll
 	for (uint32_t q = 0; q < NX; q++) {
 		const uint32_t e = tid + q * LW_SP_THREADS, kk = e % LW_SP_KT, f = e / LW_SP_KT;
-		const float v = lw_sp_x(a, t, lw_sp_index(a, t, f, k0 + kk));
+		const float v = lw_sp_x<PAD>(a, t, lw_sp_index(a, t, f, k0 + kk));
 		vx[q] = k0 + kk < a.win_length ? v : 0.0f;
 	}
 	LwSpF4 *as = (LwSpF4 *)(lds + LW_SP_LDS_A);
@@ -287,7 +302,7 @@ LW_SP_FN uint32_t lw_sp_slices(const LwSpecArgs &a, uint32_t pass)
 
 #ifndef LW_SPEC_HOST
 
-template <int ROUTE> __global__ void __launch_bounds__(LW_SP_THREADS) k_spec(LwSpecArgs a)
+template <int ROUTE, int PAD> __global__ void __launch_bounds__(LW_SP_THREADS) k_spec(LwSpecArgs a)
 {
 	extern __shared__ float lw_sp_lds[];
 	LwSpTile t;
@@ -299,7 +314,7 @@ template <int ROUTE> __global__ void __launch_bounds__(LW_SP_THREADS) k_spec(LwS
 	for (uint32_t pass = 0; pass < a.passes; pass++) {
 		lw_sp_zero_acc(st);
 		for (uint32_t kt = 0; kt < a.k_pad / LW_SP_KT; kt++) {
-			lw_sp_stage(a, t, pass, kt, tid, lw_sp_lds);
+			lw_sp_stage<PAD>(a, t, pass, kt, tid, lw_sp_lds);
 			__syncthreads();
 			lw_sp_mma<ROUTE>(a, pass, tid, lw_sp_lds, st);
 			__syncthreads();
@@ -321,15 +336,15 @@ template <int ROUTE> __global__ void __launch_bounds__(LW_SP_THREADS) k_spec(LwS
 		lw_sp_store_mel(a, t, tid, st);
 }
 
-template <int ROUTE> static hipError_t lw_sp_launch(const LwSpecArgs &a, dim3 grid, hipStream_t st)
+template <int ROUTE, int PAD> static hipError_t lw_sp_launch(const LwSpecArgs &a, dim3 grid, hipStream_t st)
 {
 	static LwPerDeviceOnce once; // above the default limit of dynamic LDS: per device, once
 	const hipError_t e = once.run([] {
-		return hipFuncSetAttribute((const void *)k_spec<ROUTE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LW_SP_LDS_FLOATS * sizeof(float)));
+		return hipFuncSetAttribute((const void *)k_spec<ROUTE, PAD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LW_SP_LDS_FLOATS * sizeof(float)));
 	});
 	if (e != hipSuccess)
 		return e;
-	return lw_launch_k(k_spec<ROUTE>, grid, dim3(LW_SP_THREADS), (size_t)LW_SP_LDS_FLOATS * sizeof(float), st, a);
+	return lw_launch_k(k_spec<ROUTE, PAD>, grid, dim3(LW_SP_THREADS), (size_t)LW_SP_LDS_FLOATS * sizeof(float), st, a);
 }
 
 hipError_t lw_launch_spec(const LwSpecArgs &a, int route, uint32_t tiles, uint32_t ch, uint32_t n_rows, hipStream_t st)
@@ -340,8 +355,13 @@ hipError_t lw_launch_spec(const LwSpecArgs &a, int route, uint32_t tiles, uint32
 			(a.n_mels != 0 && !a.fb))
 		return hipErrorInvalidValue;
 	const dim3 grid(tiles, ch, n_rows);
-	return route == LW_SP_ROUTE_MFMA ? lw_sp_launch<LW_SP_ROUTE_MFMA>(a, grid, st)
-		: route == LW_SP_ROUTE_FMA ? lw_sp_launch<LW_SP_ROUTE_FMA>(a, grid, st) : hipErrorInvalidValue;
+	if (route != LW_SP_ROUTE_MFMA && route != LW_SP_ROUTE_FMA)
+		return hipErrorInvalidValue;
+	if (a.pad_mode == 0)
+		return route == LW_SP_ROUTE_MFMA ? lw_sp_launch<LW_SP_ROUTE_MFMA, 0>(a, grid, st) : lw_sp_launch<LW_SP_ROUTE_FMA, 0>(a, grid, st);
+	if (a.pad_mode == 1)
+		return route == LW_SP_ROUTE_MFMA ? lw_sp_launch<LW_SP_ROUTE_MFMA, 1>(a, grid, st) : lw_sp_launch<LW_SP_ROUTE_FMA, 1>(a, grid, st);
+	return hipErrorInvalidValue;
 }
 
 #endif // LW_SPEC_HOST

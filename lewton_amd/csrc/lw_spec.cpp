@@ -24,6 +24,7 @@ struct lw_spec {
 	int device = 0;
 	uint32_t n_fft = 0, win_length = 0, hop = 0, n_mels = 0;
 	bool center = false;
+	int pad_mode = LW_SPEC_PAD_ZERO;
 	LwSpecPlan plan{};
 	std::vector<float> basis;                  // [2][win_length][B], the public order
 	float *d_basis = nullptr, *d_fb = nullptr; // the kernel's orders (lw_spec.hpp)
@@ -164,6 +165,21 @@ int lw_spec_set_route(lw_spec *sp, int route)
 	return LW_OK;
 }
 
+int lw_spec_pad_mode(const lw_spec *sp)
+{
+	return sp ? sp->pad_mode : -1;
+}
+
+int lw_spec_set_pad_mode(lw_spec *sp, int mode)
+{
+	if (!sp)
+		return LW_ERR_NULL_ARG;
+	if ((mode != LW_SPEC_PAD_ZERO && mode != LW_SPEC_PAD_REFLECT) || (mode == LW_SPEC_PAD_REFLECT && !sp->center))
+		return LW_ERR_UNSUPPORTED;
+	sp->pad_mode = mode;
+	return LW_OK;
+}
+
 int lw_spec_rows(lw_spec *sp, int fmt, uint32_t ch, const void *d_src, size_t n_src_rows, size_t src_capacity, const uint64_t *len,
 		const uint32_t *dst_row, void *d_dst, size_t n_dst_rows, size_t frame_capacity, void *hip_stream)
 {
@@ -188,6 +204,8 @@ int lw_spec_rows(lw_spec *sp, int fmt, uint32_t ch, const void *d_src, size_t n_
 		const uint64_t row = dst_row ? dst_row[i] : i;
 		if (len[i] > src_capacity || row >= n_dst_rows)
 			return LW_ERR_CAPACITY;
+		if (sp->pad_mode == LW_SPEC_PAD_REFLECT && len[i] != 0 && len[i] < lw_spec_reflect_min_len(sp->n_fft))
+			return LW_ERR_CAPACITY; // one reflection does not reach every support sample
 		const uint64_t frames = lw_spec_n_frames(len[i], sp->n_fft, sp->hop, sp->center);
 		if (frames > frame_capacity)
 			return LW_ERR_CAPACITY;
@@ -235,6 +253,7 @@ int lw_spec_rows(lw_spec *sp, int fmt, uint32_t ch, const void *d_src, size_t n_
 	a.d_line = frame_capacity, a.d_ch = F * frame_capacity, a.d_row = a.d_ch * ch;
 	a.lead = (int64_t)p.offset - (int64_t)(sp->center ? sp->n_fft / 2 : 0);
 	a.hop = sp->hop, a.win_length = sp->win_length, a.k_pad = p.k_pad, a.bins = p.bins, a.passes = p.passes, a.n_mels = sp->n_mels, a.mel_pad = p.mel_pad;
+	a.pad_mode = (uint32_t)sp->pad_mode;
 	for (size_t r0 = 0; r0 < n_src_rows; r0 += 65535) {
 		a.row0 = (uint32_t)r0;
 		HIP_TRY(lw_launch_spec(a, sp->route, (uint32_t)tiles, ch, (uint32_t)std::min<size_t>(n_src_rows - r0, 65535), st));

@@ -81,6 +81,14 @@ static inline uint64_t lw_spec_n_frames(uint64_t len, uint32_t n_fft, uint32_t h
 	return len < n_fft ? 0 : 1u + (len - n_fft) / hop;
 }
 
+// Reflect padding (LW_SPEC_PAD_REFLECT, centred frames): x[i] = x[-i] below 0, x[2 (len - 1) - i] from len on.  ONE reflection has
+// to reach every support sample of every frame: -(n_fft / 2) from below, and len - n_fft / 2 + n_fft - 1 (the last sample of frame
+// len / hop when hop divides len) from above.  The shortest row that allows it:
+static inline uint64_t lw_spec_reflect_min_len(uint32_t n_fft)
+{
+	return (uint64_t)n_fft - n_fft / 2u + 1u;
+}
+
 struct LwSpecArgs {
 	const float *src;
 	float *dst;
@@ -92,6 +100,7 @@ struct LwSpecArgs {
 	int64_t lead;                 // o - pad: sample 0 of frame t's SUPPORT is x[t * hop + lead]
 	uint32_t hop, win_length, k_pad, bins, passes, n_mels, mel_pad;
 	uint32_t row0; // first source row of this launch (blockIdx.z counts from it)
+	uint32_t pad_mode; // LW_SPEC_PAD_ZERO / LW_SPEC_PAD_REFLECT: what x[i] is outside [0, len)
 };
 
 // grid = (tiles of the row with the most frames, channels, rows of this launch <= 65535); a workgroup whose tile starts at or

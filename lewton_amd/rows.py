@@ -29,6 +29,14 @@ a speech model's input:
 
     sp = Spectrogram(400, 160, mel=mel_filterbank(16000, 400, 80)); feats, frames = sp.run(pcm, lengths, log="log10")
 
+pad_mode="reflect" frames a row as torch.stft's default does, and LogCompress finishes the features on the GPU (lw_feat_rows, k_feat
+in csrc/lw_kernels_feat.hip: a logarithm specified in double arithmetic, the clamp under the row's maximum, an affine map and the
+fill, bit for bit) -- together the input of a Whisper-style model:
+
+    sp = Spectrogram(400, 160, mel=mel_filterbank(16000, 400, 80, scale="slaney", norm="slaney"), pad_mode="reflect")
+    feats, frames = sp.run(pcm, lengths, out=torch.zeros((B, 1, 80, 3000), device="cuda"))
+    LogCompress.whisper().run(feats, frames, fill_to=3000)
+
 torch is imported inside the functions, never at module import.
 """
 import ctypes as C
@@ -369,6 +377,7 @@ class Resampler:
 
 
 _SPEC_WINDOWS = {"hann": 0, "rect": 1}      # LW_SPEC_HANN, LW_SPEC_RECT
+_SPEC_PAD_MODES = {"zero": 0, "reflect": 1}  # LW_SPEC_PAD_ZERO, LW_SPEC_PAD_REFLECT
 SPEC_MAX_FFT, SPEC_MAX_MELS = 2048, 256     # LW_SPEC_MAX_FFT, LW_SPEC_MAX_MELS
 
 
@@ -437,10 +446,15 @@ class Spectrogram:
     """lw_spec: rows of f32 PCM -> power spectrum or mel features on the GPU (k_spec), by the windowed DFT of
     include/lewton_amd.h ("spectral frames of rows"), a contract on bits.  window: "hann" (periodic) or "rect"; win_length: n_fft
     when None; mel: None for the power spectrum [n_fft // 2 + 1 lines], or a matrix [n_mels][n_fft // 2 + 1] (mel_filterbank).
+    pad_mode: what a centred frame sees beyond the row, "zero" (+0.0) or "reflect" (x[-i], x[2 (len - 1) - i]: torch.stft's
+    default; centred objects only, and run() then refuses a row of 0 < len < n_fft - n_fft // 2 + 1 samples).
     Parameter errors are ValueError and need no GPU; the object itself lives on cuda:device."""
 
-    def __init__(self, n_fft=400, hop=160, win_length=None, window="hann", center=True, mel=None, device=0):
+    def __init__(self, n_fft=400, hop=160, win_length=None, window="hann", center=True, mel=None, device=0, pad_mode="zero"):
         self.win_length, self._mel = _spec_params(n_fft, hop, win_length, window, mel)
+        if pad_mode not in _SPEC_PAD_MODES or (pad_mode == "reflect" and not center):
+            raise ValueError("pad_mode=%r: \"zero\", or \"reflect\" with center=True" % (pad_mode,))
+        self.pad_mode = pad_mode
         self.n_fft, self.hop, self.center, self.device = int(n_fft), int(hop), bool(center), device
         _gpu()
         err = C.c_int(0)
@@ -452,6 +466,9 @@ class Spectrogram:
                 raise ValueError("lw_spec_create refused the parameters")
             raise RuntimeError("lw_spec_create failed (%d): %s" % (err.value, N.device_error()))
         assert self.bins == self.n_fft // 2 + 1 and self.features == (n_mels or self.bins)
+        if N.lw_spec_set_pad_mode(self._h, _SPEC_PAD_MODES[pad_mode]):
+            self.close()
+            raise ValueError("lw_spec_set_pad_mode refused pad_mode=%r" % (pad_mode,))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -562,6 +579,115 @@ class Spectrogram:
                 x = torch.clamp(part, min=float(floor))
                 part.copy_(torch.where(written, torch.log(x) if log == "ln" else torch.log10(x), part))
         return out, torch.tensor(frames, dtype=torch.int64)
+
+
+_FEAT_LOGS = {None: 0, "none": 0, "ln": 1, "log10": 2, "db": 3}      # LW_FEAT_LOG_*
+_FEAT_SCOPES = {"row": 0, "channel": 1}                             # LW_FEAT_SCOPE_*
+
+
+def _feat_params(log, floor, top, add, mul, scope):
+    """(log kind, scope, the four numbers as float32), or ValueError for what lw_feat_create refuses"""
+    if log not in _FEAT_LOGS:
+        raise ValueError("log=%r: None, \"ln\", \"log10\" or \"db\"" % (log,))
+    if scope not in _FEAT_SCOPES:
+        raise ValueError("scope=%r: \"row\" or \"channel\"" % (scope,))
+    try:
+        with np.errstate(over="ignore"):
+            floor, top, add, mul = (np.float32(v) for v in (floor, top, add, mul))
+    except (TypeError, ValueError):
+        raise ValueError("floor, top, add and mul must be numbers")
+    if np.isnan(floor) or (_FEAT_LOGS[log] and not (floor > 0 and np.isfinite(floor))):
+        raise ValueError("floor=%r: a positive finite float32 under a logarithm, never NaN" % (floor,))
+    if np.isnan(top) or top < 0:
+        raise ValueError("top=%r: non-negative (inf: no clamp)" % (top,))
+    if np.isnan(add) or np.isnan(mul):
+        raise ValueError("add and mul must not be NaN")
+    return _FEAT_LOGS[log], _FEAT_SCOPES[scope], floor, top, add, mul
+
+
+class LogCompress:
+    """lw_feat: finishes feature rows [rows][C][F][frame capacity] (Spectrogram.run's output) on the GPU (k_feat), by the rule of
+    include/lewton_amd.h ("finishing feature rows"), a contract on bits: v = max(x, floor) (a NaN becomes the floor), l = LOG(v)
+    in specified double arithmetic (log: None, "ln", "log10", "db"), M = the largest l of the scope ("row": all channels and lines
+    of the row; "channel"), y = max(l, M - top) (top=inf: no clamp), z = (y + add) * mul.  The defaults are Whisper's.  Parameter
+    errors are ValueError and need no GPU; the object itself lives on cuda:device."""
+
+    WHISPER = dict(log="log10", floor=1e-10, top=8.0, add=4.0, mul=0.25, scope="row")
+
+    def __init__(self, log="log10", floor=1e-10, top=8.0, add=4.0, mul=0.25, scope="row", device=0):
+        kind, sc, floor, top, add, mul = _feat_params(log, floor, top, add, mul, scope)
+        self.log_kind, self.scope, self.device = log, scope, device
+        self.floor, self.top, self.add, self.mul = float(floor), float(top), float(add), float(mul)
+        _gpu()
+        err = C.c_int(0)
+        p = N.FeatParams(kind, sc, floor, top, add, mul)
+        self._h = N.lw_feat_create(device, C.byref(p), C.byref(err))
+        if not self._h:
+            if err.value in (N.ERR_UNSUPPORTED, N.ERR_NULL_ARG):
+                raise ValueError("lw_feat_create refused the parameters")
+            raise RuntimeError("lw_feat_create failed (%d): %s" % (err.value, N.device_error()))
+
+    @classmethod
+    def whisper(cls, device=0):
+        """log10, floor 1e-10, clamp 8 below the row's maximum, (x + 4) / 4"""
+        return cls(device=device, **cls.WHISPER)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            N.lw_feat_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        if N is not None and getattr(N, "lw_feat_destroy", None) is not None:  # not during interpreter shutdown
+            self.close()
+
+    def log(self, v):
+        """the contract's LOG of one float32 value, evaluated on the host (lw_feat_log)"""
+        return float(N.lw_feat_log(self._h, float(np.float32(v))))
+
+    def last_launches(self):
+        """kernels the last call queued: 2, or 1 when nothing needs the maximum; -1: no call yet (lw_feat_last_launches)"""
+        return N.lw_feat_last_launches(self._h)
+
+    def run(self, feat, frames, out=None, fill_to=None, want_max=False, stream=None):
+        """lw_feat_rows: frames[i] frames of every line of row i of feat (float32 [rows][C][F][frame capacity]) -> the same
+        positions of out (None: feat itself, in place; otherwise a tensor of feat's shape).  fill_to: None, one count for all rows
+        or one per row -- positions [frames[i], fill_to[i]) of every line receive what x = floor gives.  Nothing else of out is
+        written.  want_max: also return M, float32 [rows] (scope "row") or [rows][C].  stream: a hipStream_t value; None = torch's
+        current stream on the object's device.  Asynchronous; returns out, or (out, M)."""
+        torch = _gpu()
+        if out is None:
+            out = feat
+        for t, what in ((feat, "feat"), (out, "out")):
+            if t.dtype != torch.float32 or t.device.type != "cuda" or t.device.index != self.device or not t.is_contiguous() or t.dim() != 4:
+                raise ValueError("%s must be a contiguous float32 tensor [rows][C][F][frames] on cuda:%d" % (what, self.device))
+        if tuple(out.shape) != tuple(feat.shape):
+            raise ValueError("out must have feat's shape %r, not %r" % (tuple(feat.shape), tuple(out.shape)))
+        n_rows, ch, F, cap = feat.shape
+        counts = [int(v) for v in (frames.tolist() if hasattr(frames, "tolist") else frames)]
+        if len(counts) != n_rows or any(v < 0 for v in counts):
+            raise ValueError("frames= needs one non-negative entry per row of feat")
+        fill = None
+        if fill_to is not None:
+            fill = fill_to.tolist() if hasattr(fill_to, "tolist") else fill_to
+            fill = [int(fill)] * n_rows if isinstance(fill, (int, np.integer)) else [int(v) for v in fill]
+            if len(fill) != n_rows or any(v < 0 for v in fill):
+                raise ValueError("fill_to= needs one non-negative count, or one per row of feat")
+            fill = np.asarray(fill, np.uint64)
+        counts = np.asarray(counts, np.uint64)
+        mx = None
+        if want_max:
+            mx = torch.empty((n_rows,) if self.scope == "row" else (n_rows, ch), dtype=torch.float32, device=feat.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream or None
+        rc = N.lw_feat_rows(self._h, ch, F, C.c_void_p(feat.data_ptr()), C.c_void_p(out.data_ptr()), n_rows, cap,
+                            counts.ctypes.data_as(C.c_void_p), None if fill is None else fill.ctypes.data_as(C.c_void_p),
+                            None if mx is None else C.c_void_p(mx.data_ptr()), stream)
+        if rc in (N.ERR_NULL_ARG, N.ERR_CAPACITY, N.ERR_UNSUPPORTED):
+            raise ValueError("lw_feat_rows refused the call (%d)" % rc)
+        if rc:
+            raise RuntimeError("lw_feat_rows: %d %s" % (rc, N.device_error()))
+        return (out, mx) if want_max else out
 
 
 def _round_up(n, to):

@@ -1,0 +1,33 @@
+"""Reflect padding of the spectral frames (include/lewton_amd.h, "spectral frames of rows", reflect) for the CPU and the GPU suite:
+the centred frames of a row under LW_SPEC_PAD_REFLECT are the uncentred frames (tests/spec_model.py) of the row padded by numpy."""
+import numpy as np
+
+import spec_model as M
+
+
+def min_len(n_fft):
+    """the shortest row one reflection serves"""
+    return n_fft - n_fft // 2 + 1
+
+
+def index(i, n):
+    """where x[i] of a row of n samples is read, in Python integers"""
+    if i < 0:
+        i = -i
+    if i >= n:
+        i = 2 * (n - 1) - i
+    assert 0 <= i < n
+    return i
+
+
+def frame_matrix(x, n_fft, win_length, hop):
+    """float32 [1 + len // hop][win_length]: numpy pads n_fft // 2 in front and n_fft - n_fft // 2 behind -- for even n_fft what
+    torch.stft pads, for odd n_fft one sample more, which the frame at len / hop needs when hop divides len"""
+    x = np.asarray(x, np.float32)
+    if len(x) == 0:
+        return np.zeros((0, win_length), np.float32)
+    assert len(x) >= min_len(n_fft)
+    pad = n_fft // 2
+    X = M.frame_matrix(np.pad(x, (pad, n_fft - pad), "reflect"), n_fft, win_length, hop, False)
+    assert len(X) == 1 + len(x) // hop
+    return X
