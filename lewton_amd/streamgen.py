@@ -642,13 +642,16 @@ def floor0_setup(bs0: int = 7, bs1: int = 10, sample_rate: int = 22050, mixed: b
 
 class PacketWriter:
     def __init__(self, setup: StreamSetup, seed: int = 0, y01_range=(45, 95), p_floor_unused: float = 0.0,
-                 p_zero_y: float = 0.7, class_probs=(0.35, 0.3, 0.2, 0.15), vq_scale: float = 1.0):
+                 p_zero_y: float = 0.7, class_probs=(0.35, 0.3, 0.2, 0.15), vq_scale: float = 1.0, class_probs_by_channel=None):
+        """class_probs_by_channel: one class_probs tuple per channel of a submap (residue types 0 and 1, whose vectors have their
+        own class words), e.g. to keep one class out of the magnitude channel of a coupled pair"""
         self.s = setup
         self.rng = np.random.default_rng(seed)
         self.y01_range = y01_range
         self.p_unused = p_floor_unused
         self.p_zero_y = p_zero_y
         self.class_probs = np.asarray(class_probs, np.float64)
+        self.class_probs_by_channel = None if class_probs_by_channel is None else np.asarray(class_probs_by_channel, np.float64)
         self.vq_scale = vq_scale
         self._vq_cdf = {}
 
@@ -740,7 +743,8 @@ class PacketWriter:
                     for j in range(ch):
                         if dnd[j]:
                             continue
-                        cw = self.rng.choice(ncls, size=cpc, p=self.class_probs[:ncls] / self.class_probs[:ncls].sum())
+                        cp = self.class_probs if self.class_probs_by_channel is None or rs.type == 2 else self.class_probs_by_channel[j]
+                        cw = self.rng.choice(ncls, size=cpc, p=cp[:ncls] / cp[:ncls].sum())
                         sym = 0
                         for c in cw:
                             sym = sym * ncls + int(c)
