@@ -468,6 +468,70 @@ int lw_feat_rows(lw_feat *ft, uint32_t ch, uint32_t F, const void *d_src, void *
 		const uint64_t *n_frames, const uint64_t *fill_to, float *d_max, void *hip_stream);
 int lw_feat_last_launches(const lw_feat *ft);
 
+/* ---- normalising rows ----------------------------------------------------------------------------------------------------
+ * Mean removal and scaling of rows by a statistic of their own, on the GPU, as a pass of its own (k_norm): per-utterance
+ * (x - mean) / sqrt(var + 1e-7) for the waveform models (wav2vec 2.0, HuBERT, WavLM), utterance CMVN for the feature models (every
+ * mel band over time), peak and RMS level.  Source and destination are f32 [row][ch][F][capacity], lw_spec_rows' and lw_feat_rows'
+ * layout; a planar waveform rows buffer [row][ch][capacity] is F = 1.  Row i has n[i] valid elements per line.  A SCOPE is what one
+ * statistic is taken over: LW_NORM_SCOPE_ROW, all ch * F lines of a row; LW_NORM_SCOPE_CHANNEL, the F lines of a channel;
+ * LW_NORM_SCOPE_LINE, one line.  A scope of L lines has N = L * n elements.  A contract on BITS, and the first in this library whose
+ * result depends on the ORDER of a summation -- so the order is part of it.  All arithmetic of steps 1 - 4 is double; every + - * /
+ * and sqrt is ONE correctly rounded IEEE operation, nothing fused.
+ *   1  Chunk sums.  A line is cut into chunks of 256 consecutive elements counted from the line's element 0 (by index, not by
+ *      address); C = ceil(n / 256).  Elements of a chunk at or beyond n are +0.0 and take part like any other.  With elements
+ *      4i .. 4i + 3 of the chunk as doubles d0 .. d3 (i = 0 .. 63; the squares are exact in double):
+ *        a_i = ((d0 + d1) + d2) + d3,   b_i = ((d0*d0 + d1*d1) + d2*d2) + d3*d3
+ *      The 64 values are folded by the adjacent-pair tree t[j] = t[2j] + t[2j + 1], six levels, a and b each.  The chunk's peak is
+ *      the largest |x| of its elements below n, compared as the unsigned bit patterns of |x| (a NaN therefore wins, and the order
+ *      cannot matter).  A chunk so yields a triple (sum, sum of squares, peak).
+ *   2  Scope sums.  The chunk triples of a scope are listed line-major: channel, then feature line, then chunk, all ascending.  A
+ *      list of more than one entry is folded 64 entries at a time by the same six-level tree, a short last group padded with +0.0
+ *      (sums) or 0 (peak); the resulting list is folded the same way, until one triple (S1, S2, P) is left.  A list of one entry is
+ *      that entry.
+ *   3  Scalars.  mu = S1 / (double)N;  q = S2 / (double)N;  v = q - mu * mu, and v = 0 if !(v > 0);  m = center ? mu : +0.0;
+ *        LW_NORM_SCALE_NONE  g = 1.0                          LW_NORM_SCALE_STD   g = 1.0 / sqrt(v + eps)
+ *        LW_NORM_SCALE_RMS   g = target / sqrt(q + eps)       LW_NORM_SCALE_PEAK  g = (P == 0) ? 1.0 : target / (double)P
+ *      An empty scope (n == 0) has m = +0.0, g = 1.0.
+ *   4  z = (float)(((double)x - m) * g): one subtraction, one multiplication, one rounding to f32.  With center = 0 and no scale
+ *      this is a bit copy of every value that is not a NaN.
+ * Positions [n, max(n, fill_to[row])) of every line receive +0.0.  Nothing else of d_dst is written, and nothing of d_src at or
+ * beyond n of a line is read.  d_stats, when given, receives (m, g) as two doubles per scope in row / channel / line order --
+ * [n_rows][2], [n_rows][ch][2] or [n_rows][ch][F][2] -- rows with n == 0 included.  Which NaN a NaN result is, is outside the
+ * contract; every other bit is inside it, the sign of a zero included.  d_src == d_dst is allowed (in place); any other overlap is
+ * the caller's error.
+ * Accuracy: S1 and S2 carry an error of at most about 26 * 2^-53 of the sum of the magnitudes up to 2^18 chunks in a scope (2 + 6
+ * additions deep in a chunk, 6 per list level, three levels), six more per further level.  v = q - mu * mu cancels: its relative error is about 2^-50 * (1 + mu^2 / v) -- ample for audio, where a DC offset is a
+ * fraction of the deviation, and poor only for an offset thousands of times the deviation (at 512 deviations z is still within
+ * one f32 ulp of the exactly centred value; at 10 000 it is not).
+ *
+ * lw_norm_rows: n and fill_to (may be NULL: nothing is filled) are HOST arrays, copied during the call.  Asynchronous on
+ * hip_stream; calls on one object may be queued back to back.  No float atomics: the bits depend neither on the grid nor on the
+ * number of launches.  Three kernel launches on the stream (chunk sums into a list the object owns; the fold of each scope's list
+ * to (m, g); apply and fill); without center and scale one (apply and fill; the fold before it only when d_stats is given); the sums
+ * are left out when no row has an element, the apply pass when nothing is to be written.
+ * lw_norm_last_launches: the kernels the last accepted call queued, -1 = no call yet.  lw_norm_scalars: step 3 on the host, from
+ * the same source as the kernel's (P is the peak as an f32, N the scope's element count).
+ * Refusals, decided on the host before anything is queued:
+ *   LW_ERR_NULL_ARG     nm, p, m or g NULL, n NULL with rows, d_src NULL with elements to read, d_dst NULL with elements to write
+ *   LW_ERR_UNSUPPORTED  (create) an unknown scale or scope; center not 0 or 1; reserved != 0; eps NaN, negative or infinite; target
+ *                       not positive and finite under LW_NORM_SCALE_RMS or LW_NORM_SCALE_PEAK
+ *   LW_ERR_DEVICE       (create) no such device
+ *   LW_ERR_CAPACITY     n[i] or fill_to[i] > capacity, ch == 0 or > 255, F == 0 or > 65535, a buffer that 64 bits of bytes cannot
+ *                       address, more than 2^32 - 1 chunks in one row (its longest possible list) */
+typedef struct lw_norm lw_norm;
+enum { LW_NORM_SCALE_NONE = 0, LW_NORM_SCALE_STD = 1, LW_NORM_SCALE_RMS = 2, LW_NORM_SCALE_PEAK = 3 };
+enum { LW_NORM_SCOPE_ROW = 0, LW_NORM_SCOPE_CHANNEL = 1, LW_NORM_SCOPE_LINE = 2 };
+typedef struct {
+	int32_t center, scale, scope, reserved;
+	double eps, target;
+} lw_norm_params;
+lw_norm *lw_norm_create(int device, const lw_norm_params *p, int *err);
+void lw_norm_destroy(lw_norm *nm);
+int lw_norm_rows(lw_norm *nm, uint32_t ch, uint32_t F, const void *d_src, void *d_dst, size_t n_rows, size_t capacity, const uint64_t *n,
+		const uint64_t *fill_to, double *d_stats, void *hip_stream);
+int lw_norm_scalars(const lw_norm *nm, double S1, double S2, float P, uint64_t N, double *m, double *g);
+int lw_norm_last_launches(const lw_norm *nm);
+
 /* ---- staging ring (BASELINE north_star: "pinned hipMemcpyAsync staging ring so entropy decode of packet N+1 overlaps
  * GPU synthesis of packet N") ------------------------------------------------------------------------------------------
  * A ring of `slots` staging slots on the decoder's device; a slot = one batch object (pinned records + device mirror), a device

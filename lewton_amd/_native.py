@@ -57,6 +57,11 @@ class FeatParams(C.Structure):
     _fields_ = [("log", C.c_int32), ("scope", C.c_int32), ("floor", C.c_float), ("top", C.c_float), ("add", C.c_float), ("mul", C.c_float)]
 
 
+class NormParams(C.Structure):
+    _fields_ = [("center", C.c_int32), ("scale", C.c_int32), ("scope", C.c_int32), ("reserved", C.c_int32), ("eps", C.c_double),
+                ("target", C.c_double)]
+
+
 class OggPacket(C.Structure):
     _fields_ = [("data", C.c_void_p), ("len", C.c_size_t), ("stream_serial", C.c_uint32), ("absgp_page", C.c_uint64),
                 ("first_in_stream", C.c_uint8), ("last_in_stream", C.c_uint8), ("first_in_page", C.c_uint8),
@@ -173,6 +178,12 @@ SYMBOLS = {
     "lw_feat_rows": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_void_p]),
     "lw_feat_last_launches": (C.c_int, [C.c_void_p]),
+    "lw_norm_create": (C.c_void_p, [C.c_int, C.POINTER(NormParams), intp]),
+    "lw_norm_destroy": (None, [C.c_void_p]),
+    "lw_norm_rows": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_void_p]),
+    "lw_norm_scalars": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_float, C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "lw_norm_last_launches": (C.c_int, [C.c_void_p]),
     "lw_ring_create": (C.c_void_p, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, intp]),
     "lw_ring_destroy": (None, [C.c_void_p]),
     "lw_ring_stage": (C.c_int, [C.c_void_p, C.POINTER(Packet), C.c_size_t, C.c_int]),
@@ -256,6 +267,8 @@ RESAMPLE_HANN, RESAMPLE_KAISER, RESAMPLE_MAX_TAPS = 0, 1, 65536
 SPEC_PAD_ZERO, SPEC_PAD_REFLECT = 0, 1
 FEAT_LOG_NONE, FEAT_LOG_LN, FEAT_LOG_LOG10, FEAT_LOG_DB = 0, 1, 2, 3
 FEAT_SCOPE_ROW, FEAT_SCOPE_CHANNEL = 0, 1
+NORM_SCALE_NONE, NORM_SCALE_STD, NORM_SCALE_RMS, NORM_SCALE_PEAK = 0, 1, 2, 3
+NORM_SCOPE_ROW, NORM_SCOPE_CHANNEL, NORM_SCOPE_LINE = 0, 1, 2
 
 
 def fmt_dtype(fmt):

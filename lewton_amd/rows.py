@@ -37,6 +37,13 @@ fill, bit for bit) -- together the input of a Whisper-style model:
     feats, frames = sp.run(pcm, lengths, out=torch.zeros((B, 1, 80, 3000), device="cuda"))
     LogCompress.whisper().run(feats, frames, fill_to=3000)
 
+Normalize is the step the waveform models (wav2vec 2.0, HuBERT, WavLM) and utterance CMVN need (lw_norm_rows, k_norm in
+csrc/lw_kernels_norm.hip: mean and deviation, RMS or peak of a row, a channel or a line from double sums in a fixed order, bit for
+bit), over a waveform tensor [B, C, T] or a feature tensor [B, C, F, frames]:
+
+    Normalize.wav2vec2().run(pcm, lengths)                                  # in place; or decode_ogg_files(..., normalize="wav2vec2")
+    Normalize.cmvn().run(feats, frames, fill_to=3000)
+
 torch is imported inside the functions, never at module import.
 """
 import ctypes as C
@@ -690,6 +697,164 @@ class LogCompress:
         return (out, mx) if want_max else out
 
 
+_NORM_SCALES = {None: 0, "none": 0, "std": 1, "rms": 2, "peak": 3}       # LW_NORM_SCALE_*
+_NORM_SCOPES = {"row": 0, "channel": 1, "line": 2}                    # LW_NORM_SCOPE_*
+
+
+def _norm_params(center, scale, eps, target, scope):
+    """(center, scale kind, scope, eps, target), or ValueError for what lw_norm_create refuses"""
+    if scale not in _NORM_SCALES:
+        raise ValueError("scale=%r: None, \"std\", \"rms\" or \"peak\"" % (scale,))
+    if scope not in _NORM_SCOPES:
+        raise ValueError("scope=%r: \"row\", \"channel\" or \"line\"" % (scope,))
+    if center not in (True, False, 0, 1):
+        raise ValueError("center=%r: True or False" % (center,))
+    try:
+        eps, target = float(eps), float(target)
+    except (TypeError, ValueError):
+        raise ValueError("eps and target must be numbers")
+    if not (eps >= 0.0 and np.isfinite(eps)):
+        raise ValueError("eps=%r: non-negative and finite" % (eps,))
+    if _NORM_SCALES[scale] >= 2 and not (target > 0.0 and np.isfinite(target)):
+        raise ValueError("target=%r: positive and finite under \"rms\" and \"peak\"" % (target,))
+    return int(bool(center)), _NORM_SCALES[scale], _NORM_SCOPES[scope], eps, target
+
+
+class Normalize:
+    """lw_norm: normalises rows [rows][C][capacity] (waveforms) or [rows][C][F][capacity] (features) on the GPU (k_norm), by the
+    rule of include/lewton_amd.h ("normalising rows"), a contract on bits with a fixed summation order: z = (x - m) * g in double,
+    rounded once, with m the scope's mean (center) and g from its standard deviation ("std": 1 / sqrt(var + eps)), its RMS
+    ("rms": target / sqrt(mean square + eps)) or its peak ("peak": target / max |x|); scale None: g = 1.  scope: "row" (all channels
+    and lines of a row), "channel" or "line".  Parameter errors are ValueError and need no GPU; the object itself lives on
+    cuda:device."""
+
+    def __init__(self, center=True, scale="std", eps=1e-7, target=1.0, scope="row", device=0):
+        c, kind, sc, eps, target = _norm_params(center, scale, eps, target, scope)
+        self.center, self.scale, self.scope, self.eps, self.target, self.device = bool(c), scale, scope, eps, target, device
+        _gpu()
+        err = C.c_int(0)
+        p = N.NormParams(c, kind, sc, 0, eps, target)
+        self._h = N.lw_norm_create(device, C.byref(p), C.byref(err))
+        if not self._h:
+            if err.value in (N.ERR_UNSUPPORTED, N.ERR_NULL_ARG):
+                raise ValueError("lw_norm_create refused the parameters")
+            raise RuntimeError("lw_norm_create failed (%d): %s" % (err.value, N.device_error()))
+
+    @classmethod
+    def wav2vec2(cls, device=0):
+        """(x - mean) / sqrt(var + 1e-7) over each channel of an utterance: wav2vec 2.0, HuBERT, WavLM, data2vec"""
+        return cls(True, "std", 1e-7, 1.0, "channel", device)
+
+    @classmethod
+    def cmvn(cls, variance=True, eps=1e-20, device=0):
+        """utterance CMVN: every feature line has its mean over time removed, and (variance) its deviation scaled to 1"""
+        return cls(True, "std" if variance else None, eps, 1.0, "line", device)
+
+    @classmethod
+    def peak(cls, target=1.0, device=0):
+        """the row's largest |x| becomes target; nothing is centred"""
+        return cls(False, "peak", 0.0, target, "row", device)
+
+    @classmethod
+    def rms(cls, target, device=0):
+        """the row's RMS becomes target; nothing is centred"""
+        return cls(False, "rms", 0.0, target, "row", device)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            N.lw_norm_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        if N is not None and getattr(N, "lw_norm_destroy", None) is not None:  # not during interpreter shutdown
+            self.close()
+
+    def scalars(self, S1, S2, P, N_):
+        """step 3 of the contract on the host (lw_norm_scalars): (m, g) of a scope with sums S1, S2, peak P and N_ elements"""
+        m, g = C.c_double(0), C.c_double(0)
+        N.lw_norm_scalars(self._h, float(S1), float(S2), float(np.float32(P)), int(N_), C.byref(m), C.byref(g))
+        return m.value, g.value
+
+    def last_launches(self):
+        """kernels the last call queued: 3, or 1 without center and scale; -1: no call yet (lw_norm_last_launches)"""
+        return N.lw_norm_last_launches(self._h)
+
+    def run(self, x, lengths, out=None, fill_to=None, want_stats=False, stream=None):
+        """lw_norm_rows: lengths[i] elements of every line of row i of x (float32 [rows][C][capacity] or [rows][C][F][capacity])
+        -> the same positions of out (None: x itself, in place; otherwise a tensor of x's shape).  fill_to: None, one count for all
+        rows or one per row -- positions [lengths[i], fill_to[i]) of every line receive 0.  Nothing else of out is written.
+        want_stats: also return (m, g) per scope, float64 [rows][2] ("row"), [rows][C][2] or [rows][C][F][2] (without the F of a
+        3-D x).  stream: a hipStream_t value; None = torch's current stream on the object's device.  Asynchronous; returns out, or
+        (out, stats)."""
+        torch = _gpu()
+        if out is None:
+            out = x
+        for t, what in ((x, "x"), (out, "out")):
+            if (t.dtype != torch.float32 or t.device.type != "cuda" or t.device.index != self.device or not t.is_contiguous() or
+                    t.dim() not in (3, 4)):
+                raise ValueError("%s must be a contiguous float32 tensor [rows][C][capacity] or [rows][C][F][capacity] on cuda:%d" % (
+                    what, self.device))
+        if tuple(out.shape) != tuple(x.shape):
+            raise ValueError("out must have x's shape %r, not %r" % (tuple(x.shape), tuple(out.shape)))
+        n_rows, ch, cap = x.shape[0], x.shape[1], x.shape[-1]
+        F = x.shape[2] if x.dim() == 4 else 1
+        counts = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+        if len(counts) != n_rows or any(v < 0 for v in counts):
+            raise ValueError("lengths= needs one non-negative entry per row of x")
+        fill = None
+        if fill_to is not None:
+            fill = fill_to.tolist() if hasattr(fill_to, "tolist") else fill_to
+            fill = [int(fill)] * n_rows if isinstance(fill, (int, np.integer)) else [int(v) for v in fill]
+            if len(fill) != n_rows or any(v < 0 for v in fill):
+                raise ValueError("fill_to= needs one non-negative count, or one per row of x")
+            fill = np.asarray(fill, np.uint64)
+        counts = np.asarray(counts, np.uint64)
+        stats = None
+        if want_stats:
+            shape = {"row": (n_rows, 2), "channel": (n_rows, ch, 2), "line": (n_rows, ch, F, 2) if x.dim() == 4 else (n_rows, ch, 2)}[self.scope]
+            stats = torch.empty(shape, dtype=torch.float64, device=x.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream or None
+        rc = N.lw_norm_rows(self._h, ch, F, C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), n_rows, cap,
+                            counts.ctypes.data_as(C.c_void_p), None if fill is None else fill.ctypes.data_as(C.c_void_p),
+                            None if stats is None else C.c_void_p(stats.data_ptr()), stream)
+        if rc in (N.ERR_NULL_ARG, N.ERR_CAPACITY, N.ERR_UNSUPPORTED):
+            raise ValueError("lw_norm_rows refused the call (%d)" % rc)
+        if rc:
+            raise RuntimeError("lw_norm_rows: %d %s" % (rc, N.device_error()))
+        return (out, stats) if want_stats else out
+
+
+def _normalizer(normalize, samples, device):
+    """normalize= of decode_streams / decode_ogg_files -> (a Normalize or None, whether it is this call's own to close); ValueError
+    before anything is decoded"""
+    if normalize is None:
+        return None, False
+    if samples != "f32":
+        raise ValueError("normalize= works on the planar f32 format, not samples=%r" % (samples,))
+    if isinstance(normalize, Normalize):
+        if normalize.device != device:
+            raise ValueError("normalize= lives on cuda:%d, the rows on cuda:%d" % (normalize.device, device))
+        return normalize, False
+    if normalize == "wav2vec2":
+        return Normalize.wav2vec2(device), True
+    if normalize == "peak":
+        return Normalize.peak(device=device), True
+    raise ValueError("normalize=%r: a Normalize, \"wav2vec2\" or \"peak\"" % (normalize,))
+
+
+def _normalize_rows(nm, own, pcm, lengths, device):
+    """the finished rows in place, on torch's current stream; returns when it has completed"""
+    import torch
+    try:
+        with torch.cuda.device(device):
+            nm.run(pcm, lengths)
+            torch.cuda.current_stream(device).synchronize()
+    finally:
+        if own:
+            nm.close()
+
+
 def _round_up(n, to):
     to = max(1, int(to))
     return (n + to - 1) // to * to
@@ -846,7 +1011,7 @@ def _per_stream(v, n, what):
 
 
 def decode_streams(ident, setup, streams, samples="f32", device=0, max_packets=16384, run=16, entropy_on_device="auto",
-                   skip=None, keep=None, pad_to=64, out=None, channels=None, sample_rate=None, resample=None):
+                   skip=None, keep=None, pad_to=64, out=None, channels=None, sample_rate=None, resample=None, normalize=None):
     """Whole streams of one (ident, setup) pair -> (pcm, lengths, errors).
 
     streams: list of lists of audio-packet bytes (a stream's first packet only primes the window, audio.rs:1140-1152).
@@ -862,12 +1027,26 @@ def decode_streams(ident, setup, streams, samples="f32", device=0, max_packets=1
     anything is decoded): the streams are decoded as above -- skip, keep and channels= at the stream's rate -- into a temporary
     tensor, and a Resampler(stream's rate, sample_rate, **resample) fills pcm from it; lengths are then OUTPUT lengths,
     out_len of the decoded ones, and T is out_len of the longest row's upper bound rounded up to pad_to.  resample: a dict of
-    zeros, rolloff, window, beta.  The GPU work is queued on torch's current stream; the call returns when it has completed."""
+    zeros, rolloff, window, beta.  normalize: None, a Normalize or one of the names "wav2vec2", "peak" -- applied in place to the
+    finished rows (their lengths; what lies beyond stays zero), after the resampler if there is one; samples="f32" only,
+    ValueError before anything is decoded.  The GPU work is queued on torch's current stream; the call returns when it has
+    completed."""
     import torch
     _host()
     fmt = _FMT[samples]
     mix = None if channels is None else _named_mix(channels, ident.audio_channels, fmt)
     params = _resample_params(resample)
+    if normalize is not None:
+        nm, own = _normalizer(normalize, samples, device)
+        try:
+            pcm, lengths, errors = decode_streams(ident, setup, streams, samples, device, max_packets, run, entropy_on_device, skip, keep,
+                                                  pad_to, out, channels, sample_rate, resample)
+        except BaseException:
+            if own:
+                nm.close()
+            raise
+        _normalize_rows(nm, own, pcm, lengths, device)
+        return pcm, lengths, errors
     streams = [list(s) for s in streams]
     B = len(streams)
     skip = [0 if v is None else int(v) for v in _per_stream(skip, B, "skip")]
@@ -974,11 +1153,24 @@ def decode_ogg_files(sources, samples="f32", device=0, **kw):
     one tensor at that rate, which is the rate returned.  Decoder groups already at sample_rate decode straight into their rows;
     every other group decodes into a temporary tensor (skip, keep and channels= at the file's rate) and a Resampler fills its rows
     from it (f32 formats only, ValueError before anything is decoded).  lengths are output lengths.  Without sample_rate the
-    rates must agree as before."""
+    rates must agree as before.
+    normalize: as decode_streams' -- a Normalize, "wav2vec2" or "peak", applied in place to the finished rows, after the resampler
+    if there is one (samples="f32" only, ValueError before anything is decoded)."""
     import torch
     _host()
     from . import header as H
     fmt = _FMT[samples]
+    if kw.get("normalize") is not None:
+        nm, own = _normalizer(kw.pop("normalize"), samples, device)
+        try:
+            pcm, lengths, rate = decode_ogg_files(sources, samples, device, **kw)
+        except BaseException:
+            if own:
+                nm.close()
+            raise
+        _normalize_rows(nm, own, pcm, lengths, device)
+        return pcm, lengths, rate
+    kw.pop("normalize", None)
     sources = list(sources)
     B = len(sources)
     names = [s if isinstance(s, str) else "source %d" % i for i, s in enumerate(sources)]
