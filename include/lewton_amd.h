@@ -105,6 +105,12 @@ void lw_pwr_reset(lw_pwr *p);              /* `pwr = PreviousWindowRight::new()`
 void lw_pwr_free(lw_pwr *p);
 size_t lw_pwr_len(const lw_pwr *p);        /* per-channel length of the stored right part */
 int lw_pwr_copy_to_host(const lw_pwr *p, float *dst /* [ch][len] */);
+/* Grows the decoder's state pool to exactly `n` stream slots in ONE allocation (lw_pwr_new doubles the pool when it runs
+ * out: a device synchronisation and a device-to-device copy of the whole pool each time).  A no-op when the pool already
+ * holds `n` slots; LW_ERR_CAPACITY past the slot limit (see "Limits" below), LW_ERR_DEVICE when the device has no room.
+ * From a fresh pool lw_pwr_new hands the slots out in ascending order. */
+int lw_decoder_reserve_streams(lw_decoder *d, size_t n);
+int lw_debug_pwr_slot(const lw_pwr *p);    /* the state-pool slot of a handle (tests) */
 
 /* ---- one packet (drop-in for audio.rs) ---------------------------------------------------- */
 /* get_decoded_sample_count, src/audio.rs:874-909 (header bits only, host only) */
@@ -150,6 +156,30 @@ typedef struct {
 enum { LW_TAP_RESIDUE_PRE_INVERSE = 0, LW_TAP_RESIDUE_POST_INVERSE = 1, LW_TAP_PRE_MDCT = 2, LW_TAP_POST_MDCT = 3 };
 
 lw_batch *lw_batch_create(lw_decoder *d, size_t max_packets, int fmt, int *err);
+/* The largest max_packets lw_batch_create (and with it lw_ring_create, lw_sharder_create per shard, lw_rows_create and the Ogg
+ * stream's read-ahead) accepts for this decoder; a larger one is refused with LW_ERR_CAPACITY before anything is allocated.
+ * See "Limits" below. */
+size_t lw_batch_max_packets(const lw_decoder *d);
+/* ---- Limits ---------------------------------------------------------------------------------
+ * Two sizes are bounded by 32-bit fields of the records the kernels read; both are refused with LW_ERR_CAPACITY before
+ * anything is allocated, never truncated ("every failure is a status, never wrong samples").
+ *
+ * Packets per batch.  The records carry per-batch offsets in 32 bits.  With ch channels, block sizes n0 <= n1 and a floor
+ * stride of lw_setup_floor_stride() entries, a batch of n packets needs (every packet a long block, the worst case)
+ *     n * ch * n1                   floats of time-domain scratch      (2 res_off + c n1 + i; the tightest)
+ *     n * ch * (3 n1 - n0) / 4      output elements                    (lw_decoder_max_block_elems per packet)
+ *     n * ch * floor stride         floor entries
+ *     n * 2 * ch * n0 / 4           raw edge values                    (n0 = 256 or 512: the block sizes with an edge form)
+ *     n * 3                         padding words of the device entropy stage's packet pool
+ * to be at most 2^32 each, so lw_batch_max_packets = 2^32 / (ch * n1) for every setup in use: 1 048 576 packets for stereo
+ * 256/2048, 349 525 for 5.1.  With the entropy stage on the device the packets' own bytes count as well: a batch whose
+ * packets, each rounded up to 32-bit words plus three, exceed 2^32 words fails in lw_batch_entropy / lw_ring_stage with
+ * LW_ERR_CAPACITY.
+ *
+ * Streams per decoder.  A state-pool slot travels as int and as int32_t prev = -(slot + 2): slots are 0 .. 2^31 - 2, so
+ * lw_decoder_reserve_streams(d, n) and the growth behind lw_pwr_new refuse n > 2^31 - 1 (lw_pwr_new then returns NULL, as on
+ * any failed growth).  The pool itself is addressed in size_t by every kernel: its size, 2 * ch * n1 / 2 floats per slot, is
+ * bounded by device memory only (2^20 stereo 256/2048 streams are 16 GiB). */
 void lw_batch_destroy(lw_batch *b);
 /* Host entropy stage for `n` packets on `n_threads` host threads (0 = lw_default_host_threads()): fills the
  * pinned staging buffers with GPU-stage records and decides sample counts, window geometry and error

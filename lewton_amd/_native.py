@@ -108,6 +108,8 @@ SYMBOLS = {
     "lw_pwr_free": (None, [C.c_void_p]),
     "lw_pwr_len": (C.c_size_t, [C.c_void_p]),
     "lw_pwr_copy_to_host": (C.c_int, [C.c_void_p, f32p]),
+    "lw_decoder_reserve_streams": (C.c_int, [C.c_void_p, C.c_size_t]),
+    "lw_debug_pwr_slot": (C.c_int, [C.c_void_p]),
     "lw_get_decoded_sample_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t, szp]),
     "lw_read_audio_packet": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p,
                                        C.c_size_t, szp]),
@@ -121,6 +123,7 @@ SYMBOLS = {
     "lw_debug_plan_census": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]),
     "lw_debug_short_image": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_int, u8p, C.c_size_t, u8p, szp, C.POINTER(C.c_uint32)]),
     "lw_batch_create": (C.c_void_p, [C.c_void_p, C.c_size_t, C.c_int, intp]),
+    "lw_batch_max_packets": (C.c_size_t, [C.c_void_p]),
     "lw_batch_destroy": (None, [C.c_void_p]),
     "lw_batch_entropy": (C.c_int, [C.c_void_p, C.POINTER(Packet), C.c_size_t, C.c_int]),
     "lw_batch_upload": (C.c_int, [C.c_void_p, C.c_void_p]),

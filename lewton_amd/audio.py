@@ -52,6 +52,10 @@ class Decoder:
             raise ValueError("lw_decoder_set_cu_share(%d, %d): %d" % (part, parts, rc))
         return N.lw_decoder_cu_count(self._h)
 
+    def reserve_streams(self, n):
+        """grow the state pool to exactly `n` stream slots in one allocation (lw_decoder_reserve_streams); returns the status"""
+        return N.lw_decoder_reserve_streams(self._h, n)
+
     def close(self):
         if getattr(self, "_h", None):
             N.lw_decoder_destroy(self._h)

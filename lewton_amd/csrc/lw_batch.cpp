@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <thread>
@@ -19,9 +20,49 @@ static inline size_t lw_edge_values(const lw_decoder *d)
 	return d->blkp[0].eligible && d->blkp[0].lanes <= 16 ? 8u * d->blkp[0].lanes : LW_EDGE_VALUES;
 }
 
+// Every narrowing of a per-batch offset to a 32-bit record field goes through here.  lw_batch_max_packets bounds them all, so
+// no bit is ever lost; -DLW_CHECK_NARROW (the sanitizer harnesses under tests/san) turns a lost bit into an abort.
+static inline uint32_t lw_u32(size_t v)
+{
+#ifdef LW_CHECK_NARROW
+	if (v > 0xffffffffu) {
+		std::fprintf(stderr, "lw_u32: %zu does not fit 32 bits\n", v);
+		std::abort();
+	}
+#endif
+	return (uint32_t)v;
+}
+
+// (the bound of lw_batch_max_packets from the headers alone: lw_sharder_create refuses before it makes its decoders)
+size_t lw_max_packets_of(uint32_t ch_, uint32_t bs0, uint32_t bs1, uint32_t fstride)
+{
+	const uint64_t lim = (uint64_t)1 << 32, ch = ch_, n0 = (uint64_t)1 << bs0, n1 = (uint64_t)1 << bs1;
+	uint64_t m = lim / (ch * n1);                          // time-domain scratch
+	m = std::min<uint64_t>(m, lim / (ch * ((3 * n1 - n0) / 4))); // output elements (lw_decoder_max_block_elems)
+	m = std::min<uint64_t>(m, lim / (ch * fstride));       // floor records
+	if (bs0 == 8 || bs0 == 9)                              // raw edges: blocksize_0 / 4 values each (the block sizes with an edge form)
+		m = std::min<uint64_t>(m, lim / (2 * ch * (n0 / 4)));
+	m = std::min<uint64_t>(m, lim / 3);                    // packet pool: three padding words per packet
+	return (size_t)m;
+}
+
 extern "C" {
 
 // ---- batches ----------------------------------------------------------------------------------
+/* The largest batch whose LAST packet's offsets still fit the 32-bit fields of the records (LwPacketRec, LwFastItem, LwShortSlot,
+ * LwOlaDesc; include/lewton_amd.h, "Limits").  Worst case per packet: a long block.  With n packets,
+ *   time-domain scratch [n][ch][n1] floats   2 res_off + c n1 + rs + i: the block of packet n - 1 ends at n ch n1      (tightest)
+ *   output elements                          out_off + c m + i: ends at n * lw_decoder_max_block_elems at the most
+ *   floor records [n][ch][fstride] u16       floor_off + c fstride + i: ends at n ch fstride
+ *   raw edges [n][2][ch][edge values]        ((2 pkt + side) ch + c) edge values + i: ends at 2 n ch edge values (edge form only)
+ *   device-entropy packet pool               word_off: at least the three padding words per packet (the packets' bytes
+ *                                            themselves are checked when a batch is staged: lw_batch_entropy)
+ * must all be <= 2^32, so that the largest offset formed is 2^32 - 1. */
+size_t lw_batch_max_packets(const lw_decoder *d)
+{
+	return d ? lw_max_packets_of(d->T.ch, d->id->bs0, d->id->bs1, d->T.fstride) : 0;
+}
+
 lw_batch *lw_batch_create(lw_decoder *d, size_t max_packets, int fmt, int *err)
 {
 	int dummy;
@@ -30,6 +71,11 @@ lw_batch *lw_batch_create(lw_decoder *d, size_t max_packets, int fmt, int *err)
 	*err = LW_OK;
 	if (!d || max_packets == 0 || !lw_fmt_valid(fmt)) {
 		*err = LW_ERR_NULL_ARG;
+		return nullptr;
+	}
+	if (max_packets > lw_batch_max_packets(d)) { // (before anything is allocated or the device is touched)
+		lw_set_device_error("lw_batch_create: more packets than the records' 32-bit offsets address (lw_batch_max_packets)");
+		*err = LW_ERR_CAPACITY;
 		return nullptr;
 	}
 	if (lw_decoder_set_device(d)) {
@@ -282,8 +328,8 @@ int lw_batch_entropy(lw_batch *b, const lw_packet *pkts, size_t n, int n_threads
 		std::memset(&r, 0, sizeof(r));
 		r.prev = -1;
 		r.state_out = -1;
-		r.floor_off = (uint32_t)(i * ch * fstride);
-		r.res_off = (uint32_t)res_off;
+		r.floor_off = lw_u32(i * ch * fstride);
+		r.res_off = lw_u32(res_off);
 		if ((!pkts[i].data && pkts[i].len) || !pkts[i].pwr) {
 			b->status[i] = LW_ERR_NULL_ARG;
 			continue;
@@ -310,9 +356,16 @@ int lw_batch_entropy(lw_batch *b, const lw_packet *pkts, size_t n, int n_threads
 		for (size_t i = 0; i < n; i++) {
 			if (b->status[i] != LW_OK)
 				continue;
-			b->h_pk[i].word_off = (uint32_t)words;
-			b->h_pk[i].len = (uint32_t)pkts[i].len;
-			words += (pkts[i].len + 3) / 4 + 3;
+			// word_off is 32 bits: a batch whose packets (with their padding) do not fit 2^32 words is refused as a whole
+			const size_t w = (pkts[i].len + 3) / 4 + 3;
+			if (pkts[i].len > 0xffffffffu || words + w > ((size_t)1 << 32)) {
+				lw_set_device_error("device entropy stage: the batch's packets exceed the 32-bit word offsets of its packet pool");
+				b->n = 0;
+				return LW_ERR_CAPACITY;
+			}
+			b->h_pk[i].word_off = lw_u32(words);
+			b->h_pk[i].len = lw_u32(pkts[i].len);
+			words += w;
 		}
 		if (words > b->pool_cap_words) {
 			const size_t cap = words + words / 2 + 1024;
@@ -429,7 +482,7 @@ int lw_batch_entropy(lw_batch *b, const lw_packet *pkts, size_t n, int n_threads
 		res.status = b->status[i];
 		res.n_samples = 0;
 		res.out_offset = out_off;
-		r.out_off = (uint32_t)out_off;
+		r.out_off = lw_u32(out_off);
 		if (b->status[i] != LW_OK) {
 			r.flags = LW_RF_SKIP;
 			continue;
@@ -688,7 +741,7 @@ int lw_batch_entropy(lw_batch *b, const lw_packet *pkts, size_t n, int n_threads
 						sl.prev_arg = (uint32_t)r.prev;
 					} else { // generic kernels, or k_long<TD>: the whole time-domain block is in td
 						sl.prev_kind = LW_SP_TD;
-						sl.prev_arg = 2u * pr.res_off + pr.rs;
+						sl.prev_arg = lw_u32((size_t)2 * pr.res_off + pr.rs);
 						sl.prev_stride = (uint16_t)(1u << pr.bs);
 					}
 				}
@@ -777,7 +830,7 @@ int lw_batch_entropy(lw_batch *b, const lw_packet *pkts, size_t n, int n_threads
 	for (uint32_t t = 0; t < b->n_gen_ola; t++) {
 		const LwPacketRec &r = b->h_recs[b->h_gen[2 * b->max_packets + t]];
 		LwOlaDesc &o = b->h_ola[t];
-		o.cur_off = 2u * r.res_off;
+		o.cur_off = lw_u32((size_t)2 * r.res_off);
 		o.out_off = r.out_off;
 		o.state_out = r.state_out;
 		o.n = (uint16_t)(1u << r.bs); // (8192-point blocks: 0x2000 fits)
@@ -794,12 +847,12 @@ int lw_batch_entropy(lw_batch *b, const lw_packet *pkts, size_t n, int n_threads
 		} else if (r.prev >= 0) {
 			const LwPacketRec &pr = b->h_recs[r.prev];
 			o.prev_kind = 1;
-			o.prev_off = 2u * pr.res_off + pr.rs;
+			o.prev_off = lw_u32((size_t)2 * pr.res_off + pr.rs);
 			o.prev_stride = (uint16_t)(1u << pr.bs);
 		} else {
 			const uint32_t slot = (uint32_t)(-(r.prev + 2)), par = (r.flags & LW_RF_PARITY_IN) ? 1u : 0u;
 			o.prev_kind = 2;
-			o.prev_off = (uint32_t)(((size_t)slot * 2 + par) * d->T.state_stride);
+			o.prev_off = lw_u32((size_t)slot * 2 + par); // (scaled by the pool's stride in the kernel, in size_t)
 			o.prev_stride = (uint16_t)d->T.state_chan_stride;
 		}
 	}
@@ -925,7 +978,7 @@ int lw_batch_entropy(lw_batch *b, const lw_packet *pkts, size_t n, int n_threads
 			}
 			LwFastItem &it = b->h_items[pos];
 			fill(it, idx);
-			if (it.res_off != (uint32_t)(pos * ch * n1h) || it.floor_off != (uint32_t)(pos * ch * fstride))
+			if (it.res_off != pos * ch * n1h || it.floor_off != pos * ch * fstride)
 				b->fast_dense = 0;
 			if (r.prev == -1 || (r.flags & LW_RF_TDONLY) || (r.xflags & LW_XF_EDGE_L)) {
 				it.src_kind = LW_SRC_NONE; // (a TD-only packet is overlapped later, by k_ola_generic; a short left slope by k_short)
@@ -946,7 +999,7 @@ int lw_batch_entropy(lw_batch *b, const lw_packet *pkts, size_t n, int n_threads
 				}
 			} else {
 				it.src_kind = LW_SRC_TD;
-				it.src_arg = 2u * b->h_recs[r.prev].res_off;
+				it.src_arg = lw_u32((size_t)2 * b->h_recs[r.prev].res_off);
 			}
 			pos++;
 		}

@@ -189,5 +189,9 @@ inline int lw_kernel_fmt(int fmt, uint32_t ch)
 	return -1;
 }
 int lw_decoder_set_device(const lw_decoder *d);
-// grow the state pool to at least `slots` (caller holds d->mu)
+// slots of a decoder's state pool: slot numbers 0 .. 2^31 - 2 (lw_runtime.cpp: grow_state_to)
+#define LW_STATE_MAX_SLOTS ((size_t)0x7fffffffu)
+// lw_batch_max_packets from the stream's shape alone (lw_batch.cpp)
+size_t lw_max_packets_of(uint32_t ch, uint32_t bs0, uint32_t bs1, uint32_t fstride);
+// grow the state pool to at least `slots` (caller holds d->mu); LW_ERR_CAPACITY past LW_STATE_MAX_SLOTS
 int lw_grow_state(lw_decoder *d, size_t slots);

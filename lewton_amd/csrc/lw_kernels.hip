@@ -794,11 +794,13 @@ __global__ void __launch_bounds__(LW_BLOCK) k_ola_generic(LwDevTables T, LwBatch
 		if (o.prev_kind != 0 && rs > ls) {
 			const uint32_t m = rs - ls;
 			const float *slope = T.bs[(o.flags & LW_RF_SLOPE_BS1) ? 1 : 0].window;
-			const float *prev0 = (o.prev_kind == 1 ? B.td : B.state) + o.prev_off;
+			// kind 2: prev_off = 2 slot + parity, scaled here in size_t (the pool may hold more than 2^32 floats)
+			const float *prev0 = o.prev_kind == 1 ? B.td + o.prev_off : B.state + (size_t)o.prev_off * T.state_stride;
+			const uint32_t prev_align = o.prev_kind == 1 ? o.prev_off : T.state_stride; // (what decides prev0's alignment)
 			const uint32_t prev_stride = o.prev_stride;
 			// four samples per thread and step (16-byte loads, one 8- or 16-byte store) when everything is a multiple of four
 			// -- it always is for block sizes >= 64; the long blocks next to short ones move 40 KB each through here
-			const bool quads = !lw_out_itl(FMT) && ((ls | m | plen | n | prev_stride | o.prev_off | o.cur_off | o.out_off) & 3u) == 0 &&
+			const bool quads = !lw_out_itl(FMT) && ((ls | m | plen | n | prev_stride | prev_align | o.cur_off | o.out_off) & 3u) == 0 &&
 				((uintptr_t)out_v & 15u) == 0;
 			if (quads) {
 				const uint32_t mq = m >> 2;

@@ -67,7 +67,8 @@ static_assert(sizeof(LwPacketRec) == 32, "LwPacketRec must stay 32 bytes");
 // first sample).  32 bytes.
 struct LwOlaDesc {
 	uint32_t cur_off;   // this packet's time-domain block [ch][n] in B.td (float offset)
-	uint32_t prev_off;  // previous right part: float offset of channel 0 in B.td (kind 1) or in the state pool (kind 2)
+	uint32_t prev_off;  // previous right part: float offset of channel 0 in B.td (kind 1); 2 * state slot + parity (kind 2: the
+	                    // kernel multiplies by the pool's stride in size_t -- a pool holds more than 2^32 floats)
 	uint32_t out_off;   // first output element
 	int32_t state_out;  // state slot the raw right part goes to, or -1
 	uint16_t n, ls, rs, re, plen, prev_stride;

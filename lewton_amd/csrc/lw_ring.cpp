@@ -227,6 +227,10 @@ lw_ring *lw_ring_create(lw_decoder *d, size_t n_slots, size_t max_packets, int f
 		*err = LW_ERR_NULL_ARG;
 		return nullptr;
 	}
+	if (max_packets > lw_batch_max_packets(d)) { // (what lw_batch_create would say for every slot, before anything is allocated)
+		*err = LW_ERR_CAPACITY;
+		return nullptr;
+	}
 	auto *r = new lw_ring();
 	r->dec = d;
 	r->device = lw_decoder_device(d);
@@ -259,6 +263,11 @@ lw_ring *lw_ring_create(lw_decoder *d, size_t n_slots, size_t max_packets, int f
 			break;
 		int e = 0;
 		s.batch = lw_batch_create(d, max_packets, fmt, &e);
+		if (!s.batch && e == LW_ERR_CAPACITY) { // (a batch's refusal is passed on as it is)
+			*err = e;
+			lw_ring_destroy(r);
+			return nullptr;
+		}
 		good = s.batch && ok(hipMalloc(&s.d_out, r->cap_elems * r->esz)) && ok(hipHostMalloc(&s.h_out, r->cap_elems * r->esz)) &&
 			ok(lw_decoder_stream_create(d, &s.stream)) &&
 			ok(hipEventCreateWithFlags(&s.kernels_done, hipEventDisableTiming)) &&

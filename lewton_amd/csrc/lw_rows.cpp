@@ -30,6 +30,10 @@ lw_rows *lw_rows_create(lw_decoder *d, size_t max_packets, int fmt, int *err)
 		*err = LW_ERR_NULL_ARG;
 		return nullptr;
 	}
+	if (max_packets > lw_batch_max_packets(d)) { // no batch of the decoder is that large (before anything is allocated)
+		*err = LW_ERR_CAPACITY;
+		return nullptr;
+	}
 	if (lw_decoder_set_device(d)) {
 		*err = LW_ERR_DEVICE;
 		return nullptr;

@@ -50,11 +50,14 @@ int lw_decoder_set_device(const lw_decoder *d)
 	return LW_OK;
 }
 
-int lw_grow_state(lw_decoder *d, size_t slots)
+// Slots travel as `int` (the free list, lw_pwr::slot), as int32_t state_out and as int32_t prev = -(slot + 2) in the packet
+// records: the largest slot all of them carry is 2^31 - 2 (include/lewton_amd.h, "Limits").
+static int grow_state_to(lw_decoder *d, size_t cap)
 {
-	if (slots <= d->state_cap)
-		return LW_OK;
-	size_t cap = std::max<size_t>(slots, d->state_cap ? d->state_cap * 2 : 64);
+	if (cap > LW_STATE_MAX_SLOTS) {
+		lw_set_device_error("state pool: more streams than a packet record's slot field carries");
+		return LW_ERR_CAPACITY;
+	}
 	const size_t per = (size_t)2 * d->T.state_stride;
 	float *nb = nullptr;
 	HIP_TRY(hipDeviceSynchronize());
@@ -68,6 +71,15 @@ int lw_grow_state(lw_decoder *d, size_t slots)
 	d->d_state = nb;
 	d->state_cap = cap;
 	return LW_OK;
+}
+
+int lw_grow_state(lw_decoder *d, size_t slots)
+{
+	if (slots <= d->state_cap)
+		return LW_OK;
+	if (slots > LW_STATE_MAX_SLOTS)
+		return grow_state_to(d, slots); // (refused there)
+	return grow_state_to(d, std::min<size_t>(LW_STATE_MAX_SLOTS, std::max<size_t>(slots, d->state_cap ? d->state_cap * 2 : 64)));
 }
 
 
@@ -836,6 +848,25 @@ lw_pwr *lw_pwr_new(lw_decoder *d)
 	p->slot = d->free_slots.back();
 	d->free_slots.pop_back();
 	return p;
+}
+
+int lw_decoder_reserve_streams(lw_decoder *d, size_t n)
+{
+	if (!d)
+		return LW_ERR_NULL_ARG;
+	std::lock_guard<std::mutex> g(d->mu);
+	if (n <= d->state_cap)
+		return LW_OK;
+	if (n > LW_STATE_MAX_SLOTS) // (before anything touches the device)
+		return grow_state_to(d, n);
+	if (int rc = lw_decoder_set_device(d))
+		return rc;
+	return grow_state_to(d, n);
+}
+
+int lw_debug_pwr_slot(const lw_pwr *p)
+{
+	return p ? p->slot : -1;
 }
 
 int lw_pwr_is_empty(const lw_pwr *p)

@@ -311,6 +311,8 @@ struct lw_sharder {
 
 static std::atomic<int> g_share_cus{0};
 
+size_t lw_max_packets_of(uint32_t ch, uint32_t bs0, uint32_t bs1, uint32_t fstride); // lw_batch.cpp: lw_batch_max_packets from the headers
+
 extern "C" {
 
 // measurement hook: 1 = logical shards of one device get their own CUs of every XCD each (tools/probe/sharder_probe.py)
@@ -328,6 +330,13 @@ lw_sharder *lw_sharder_create(const lw_ident *id, const lw_setup *setup, const i
 	*err = LW_OK;
 	if (!id || !setup || !devices || n_shards == 0 || n_shards > 1024 || max_packets_per_shard == 0 || !lw_fmt_valid(fmt)) {
 		*err = LW_ERR_NULL_ARG;
+		return nullptr;
+	}
+	// a shard's batches cannot be larger than lw_batch_max_packets: refused before any decoder is made
+	lw_ident_info info;
+	if (lw_ident_get_info(id, &info) == LW_OK &&
+			max_packets_per_shard > lw_max_packets_of(info.audio_channels, info.blocksize_0, info.blocksize_1, lw_setup_floor_stride(setup))) {
+		*err = LW_ERR_CAPACITY;
 		return nullptr;
 	}
 	auto sh = std::make_unique<lw_sharder>();

@@ -71,10 +71,13 @@
 #pragma unroll
 		for (int x = 0; x < 4; x++)
 			r[c][x] = need_res && has_block ? __builtin_nontemporal_load(&s[L * x + l]) : float4_t{0.0f, 0.0f, 0.0f, 0.0f};
+		// the state pool is addressed in size_t like the store below (a stream's slot lies anywhere in a pool of up to 2^31 - 1
+		// slots); the edge and time-domain offsets are per-batch and stay 32-bit: lw_batch_create refuses a batch whose last
+		// packet's offsets do not fit (lw_batch_max_packets)
 		const float *pbase = F.state;
-		uint32_t poff = 0;
+		size_t poff = 0;
 		if (prev_kind == LW_SP_STATE) {
-			poff = (prev_arg * 2u + ((flags & LW_RF_PARITY_IN) ? 1u : 0u)) * F.state_stride + chn[c] * F.state_chan_stride;
+			poff = ((size_t)prev_arg * 2u + ((flags & LW_RF_PARITY_IN) ? 1u : 0u)) * F.state_stride + chn[c] * F.state_chan_stride;
 		} else if (prev_kind == LW_SP_EDGE) {
 			pbase = F.edge;
 			poff = ((prev_arg * 2u + 1u) * F.ch + chn[c]) * (8u * L);

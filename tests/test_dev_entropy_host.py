@@ -20,7 +20,7 @@ SRC = [os.path.join(ROOT, "tests", "san", "dev_entropy_host.cpp")] + [
 def harness(tmp_path_factory):
     exe = str(tmp_path_factory.mktemp("deventropy") / "dev_entropy_host")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-ffp-contract=off"] + SRC + ["-o", exe])
+                           "-ffp-contract=off", "-DLW_CHECK_NARROW"] + SRC + ["-o", exe])
     return exe
 
 

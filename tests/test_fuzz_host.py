@@ -51,7 +51,7 @@ def test_host_stage_under_sanitizers(tmp_path):
     exe = tmp_path / "host_fuzz"
     src = os.path.join(ROOT, "tests", "san", "host_fuzz.cpp")
     csrc = os.path.join(ROOT, "lewton_amd", "csrc")
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off",
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off", "-DLW_CHECK_NARROW",
            src, os.path.join(csrc, "lw_headers.cpp"), os.path.join(csrc, "lw_entropy.cpp"), "-o", str(exe)]
     subprocess.check_call(cmd)
     cases = _cases(5, n_setup_mut=12, n_packet_mut=6)
@@ -136,7 +136,7 @@ def test_ogg_demultiplexer_under_sanitizers(tmp_path):
     from lewton_amd import ogg
     exe = tmp_path / "ogg_fuzz"
     src = os.path.join(ROOT, "tests", "san", "ogg_fuzz.cpp")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", src,
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DLW_CHECK_NARROW", src,
                            "-o", str(exe)])
     rng = np.random.default_rng(31)
     a, b = ogg.PageWriter(21, 9), ogg.PageWriter(22, 2)
@@ -266,7 +266,7 @@ def test_degenerate_setups_under_sanitizers(tmp_path):
     src = os.path.join(ROOT, "tests", "san", "host_fuzz.cpp")
     csrc = os.path.join(ROOT, "lewton_amd", "csrc")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-ffp-contract=off", src, os.path.join(csrc, "lw_headers.cpp"), os.path.join(csrc, "lw_entropy.cpp"),
+                           "-ffp-contract=off", "-DLW_CHECK_NARROW", src, os.path.join(csrc, "lw_headers.cpp"), os.path.join(csrc, "lw_entropy.cpp"),
                            "-o", str(exe)])
     cases = []
     for name, setup in sorted(_degenerate_setups().items()):

@@ -32,7 +32,7 @@ def harness(tmp_path_factory):
     if not os.path.isdir(os.path.join(HIP_INC, "hip")):
         pytest.skip("HIP headers not installed")
     exe = str(tmp_path_factory.mktemp("hostbatch") / "batch_host_bench_tsan")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=thread", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__",
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=thread", "-ffp-contract=off", "-DLW_CHECK_NARROW", "-D__HIP_PLATFORM_AMD__",
                            "-I" + HIP_INC] + SRC + ["-lpthread", "-o", exe])
     return exe
 
@@ -164,7 +164,7 @@ def random_setup_case(harness, seed, case, blocksizes=None, n_streams=6, per=14)
 
 def build_harness_asan(exe):
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off",
-                           "-D__HIP_PLATFORM_AMD__", "-I" + HIP_INC] + SRC + ["-lpthread", "-o", exe])
+                           "-DLW_CHECK_NARROW", "-D__HIP_PLATFORM_AMD__", "-I" + HIP_INC] + SRC + ["-lpthread", "-o", exe])
     return exe
 
 

@@ -25,7 +25,7 @@ def harness(tmp_path_factory):
         pytest.skip("HIP headers not installed")
     exe = str(tmp_path_factory.mktemp("hostogg") / "ogg_stream_host")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I" + HIP_INC] + SRC + ["-lpthread", "-o", exe])
+                           "-ffp-contract=off", "-DLW_CHECK_NARROW", "-D__HIP_PLATFORM_AMD__", "-I" + HIP_INC] + SRC + ["-lpthread", "-o", exe])
     return exe
 
 
@@ -442,7 +442,7 @@ def harness_tsan(tmp_path_factory):
     if not os.path.isdir(os.path.join(HIP_INC, "hip")):
         pytest.skip("HIP headers not installed")
     exe = str(tmp_path_factory.mktemp("hostogg_tsan") / "ogg_stream_host_tsan")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=thread", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__",
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=thread", "-ffp-contract=off", "-DLW_CHECK_NARROW", "-D__HIP_PLATFORM_AMD__",
                            "-I" + HIP_INC] + SRC + ["-lpthread", "-o", exe])
     return exe
 

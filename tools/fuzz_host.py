@@ -84,7 +84,7 @@ def fix_crcs(d):
 with tempfile.TemporaryDirectory() as tmp:
     exe, path = os.path.join(tmp, "ogg_stream_host"), os.path.join(tmp, "in.ogg")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I" + HIP_INC] + SRC + ["-lpthread", "-o", exe])
+                           "-ffp-contract=off", "-DLW_CHECK_NARROW", "-D__HIP_PLATFORM_AMD__", "-I" + HIP_INC] + SRC + ["-lpthread", "-o", exe])
     files = _files()
     names = sorted(files)
     agree = opened = comment_rejects = 0
