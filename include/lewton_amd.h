@@ -562,6 +562,65 @@ int lw_norm_rows(lw_norm *nm, uint32_t ch, uint32_t F, const void *d_src, void *
 int lw_norm_scalars(const lw_norm *nm, double S1, double S2, float P, uint64_t N, double *m, double *g);
 int lw_norm_last_launches(const lw_norm *nm);
 
+/* ---- cepstra and deltas of feature rows ----------------------------------------------------------------------------------
+ * A matrix ACROSS the feature lines of finished feature rows and a regression filter ALONG their frames, on the GPU, as a pass
+ * of its own (k_cep): MFCC (a DCT of the log-mel lines, optionally liftered) and the delta / delta-delta features taken of
+ * cepstra or of filterbanks (HuBERT's 39-dimensional k-means targets, HTK / Kaldi "fbank + deltas").  Source: f32
+ * [row][ch][n_in][frame_capacity], the layout of lw_spec_rows, lw_feat_rows and lw_norm_rows.  Destination: f32
+ * [row][ch][n_out * (1 + order)][frame_capacity], the same frame_capacity: lines 0 .. n_out - 1 are the static features, the
+ * next n_out their deltas, the next n_out the delta-deltas (HTK / Kaldi order).  Row i has n_frames[i] frames.  An object is made
+ * from (n_in, n_out, matrix, order, width): 1 <= n_in <= LW_CEP_MAX_IN, 1 <= n_out <= LW_CEP_MAX_OUT, order 0, 1 or 2, width N
+ * in 1 .. LW_CEP_MAX_WIDTH when order > 0 and 0 when order == 0.  A contract on BITS.  For frame t < n_frames[row]:
+ *   1  Static line q.  matrix is the caller's n_out x n_in HOST floats, matrix[q * n_in + f], copied at creation.  With x[f][t]
+ *      element t of source line f:  acc = +0.0;  for f = 0 .. n_in - 1 ascending: acc = fmaf(x[f][t], matrix[q][f], acc).  The
+ *      fold is dense: a weight of 0 takes part like any other.  matrix == NULL is the identity and needs n_out == n_in: the
+ *      static lines are then a BIT COPY of the source lines (deltas of filterbanks with no arithmetic on the static part).
+ *   2  Delta weights.  D = 2 * (1*1 + 2*2 + .. + N*N) as an integer;  w_n = (float)((double)n / (double)D) for n = 1 .. N: one
+ *      double division, one rounding, on the host.  The kernel divides nothing.
+ *   3  Delta of a line s.  With c(i) = min(max(i, 0), n_frames - 1) in signed 64-bit integers (the edge frames are replicated):
+ *        acc = +0.0;  for n = 1 .. N ascending:  d = s[c(t + n)] - s[c(t - n)] (ONE rounded f32 subtraction);  acc = fmaf(w_n, d, acc)
+ *      The delta lines are this of the static lines.  The delta-delta lines are this OF THE DELTA LINES, with the same clamp --
+ *      what torchaudio.functional.compute_deltas applied twice gives, and python_speech_features.delta.  (Kaldi's add-deltas
+ *      convolves the two windows and clamps once, so it differs within 2 N frames of either end; librosa's Savitzky-Golay deltas
+ *      differ at the edges.)
+ * No reassociation, no chain split over f or over n, subnormals kept.  The sign of a zero is inside the contract; which NaN a
+ * NaN result is, is outside it.  Positions [n_frames, max(n_frames, fill_to[row])) of every destination line receive +0.0.
+ * Nothing else of d_dst is written, and nothing of d_src at or beyond n_frames of a line is read.  Any overlap of d_src and d_dst
+ * is the caller's error: the shapes differ, so there is no in-place form.
+ * Accuracy of a static line against the exact sum: |acc - exact| <= (n_in + 1) * 2^-24 * sum_f |x[f][t]| |matrix[q][f]| (n_in
+ * roundings of partial sums that are at most the sum of the magnitudes, and the rounding of the weights).
+ *
+ * lw_cep_rows: n_frames and fill_to (may be NULL: nothing is filled) are HOST arrays, copied during the call.  Asynchronous on
+ * hip_stream; calls on one object may be queued back to back.  ONE kernel launch per 65535 rows on the stream, none when nothing
+ * is to be written: the source is read once and every destination line written once.  A workgroup produces lw_cep_tile_frames
+ * consecutive frames of a row and channel (256 - 2 * order * width) and recomputes the order * width frames either side of them
+ * at their clamped indices; no atomics, and the bits depend neither on the tile nor on the grid.
+ * lw_cep_features: n_out * (1 + order).  lw_cep_matrix: the matrix as the kernel reads it, [n_out][n_in] floats into dst; returns
+ * their count (dst NULL: the count alone), 0 for the identity.  lw_cep_delta_weights: w_1 .. w_N into dst (may be NULL); returns
+ * N.  lw_cep_last_launches: the kernels the last accepted call queued, -1 = no call yet.
+ * Refusals, decided on the host before anything is queued:
+ *   LW_ERR_NULL_ARG     cp NULL, n_frames NULL with rows, d_src NULL with frames to read, d_dst NULL with elements to write;
+ *                       (create) matrix NULL with n_out != n_in
+ *   LW_ERR_UNSUPPORTED  (create) n_in or n_out outside its limits, order > 2, width outside 1 .. LW_CEP_MAX_WIDTH under an order,
+ *                       width != 0 without one
+ *   LW_ERR_DEVICE       (create) no such device, or one whose workgroups have less LDS than the kernel needs (order * 256 *
+ *                       min(32, n_out rounded up to 8) floats; the device is asked)
+ *   LW_ERR_CAPACITY     n_frames[i] or fill_to[i] > frame_capacity, ch == 0 or > 255, a buffer that 64 bits of bytes cannot address,
+ *                       more than 2^24 - 1 tiles in a line (a grid dimension holds fewer than 2^32 lanes, a tile has 256) */
+#define LW_CEP_MAX_IN 256
+#define LW_CEP_MAX_OUT 256
+#define LW_CEP_MAX_WIDTH 16
+typedef struct lw_cep lw_cep;
+lw_cep *lw_cep_create(int device, uint32_t n_in, uint32_t n_out, const float *matrix, uint32_t order, uint32_t width, int *err);
+void lw_cep_destroy(lw_cep *cp);
+uint32_t lw_cep_features(const lw_cep *cp);
+size_t lw_cep_matrix(const lw_cep *cp, float *dst);
+uint32_t lw_cep_delta_weights(const lw_cep *cp, float *dst);
+uint32_t lw_cep_tile_frames(const lw_cep *cp);
+int lw_cep_rows(lw_cep *cp, uint32_t ch, const void *d_src, void *d_dst, size_t n_rows, size_t frame_capacity, const uint64_t *n_frames,
+		const uint64_t *fill_to, void *hip_stream);
+int lw_cep_last_launches(const lw_cep *cp);
+
 /* ---- staging ring (BASELINE north_star: "pinned hipMemcpyAsync staging ring so entropy decode of packet N+1 overlaps
  * GPU synthesis of packet N") ------------------------------------------------------------------------------------------
  * A ring of `slots` staging slots on the decoder's device; a slot = one batch object (pinned records + device mirror), a device

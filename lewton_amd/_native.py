@@ -187,6 +187,14 @@ SYMBOLS = {
                                C.c_void_p, C.c_void_p]),
     "lw_norm_scalars": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_float, C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "lw_norm_last_launches": (C.c_int, [C.c_void_p]),
+    "lw_cep_create": (C.c_void_p, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, intp]),
+    "lw_cep_destroy": (None, [C.c_void_p]),
+    "lw_cep_features": (C.c_uint32, [C.c_void_p]),
+    "lw_cep_matrix": (C.c_size_t, [C.c_void_p, C.c_void_p]),
+    "lw_cep_delta_weights": (C.c_uint32, [C.c_void_p, C.c_void_p]),
+    "lw_cep_tile_frames": (C.c_uint32, [C.c_void_p]),
+    "lw_cep_rows": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lw_cep_last_launches": (C.c_int, [C.c_void_p]),
     "lw_ring_create": (C.c_void_p, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, intp]),
     "lw_ring_destroy": (None, [C.c_void_p]),
     "lw_ring_stage": (C.c_int, [C.c_void_p, C.POINTER(Packet), C.c_size_t, C.c_int]),

@@ -825,6 +825,170 @@ class Normalize:
         return (out, stats) if want_stats else out
 
 
+CEP_MAX_IN, CEP_MAX_OUT, CEP_MAX_WIDTH = 256, 256, 16     # LW_CEP_MAX_IN, LW_CEP_MAX_OUT, LW_CEP_MAX_WIDTH
+
+
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+def dct_matrix(n_out, n_in, norm="ortho", lifter=0):
+    """[n_out][n_in] float32 DCT-II rows cos(pi q (2 f + 1) / (2 n_in)), computed in float64 and rounded once.  norm="ortho": scaled
+    by sqrt(2 / n_in), row 0 by sqrt(1 / n_in); norm=None: by 2, as scipy and torchaudio.  lifter L > 0 folds the HTK lifter
+    1 + (L / 2) sin(pi q / L) into row q.  Needs no GPU."""
+    if not _is_int(n_in) or not 1 <= n_in <= CEP_MAX_IN:
+        raise ValueError("n_in=%r: 1 .. %d" % (n_in, CEP_MAX_IN))
+    if not _is_int(n_out) or not 1 <= n_out <= CEP_MAX_OUT:
+        raise ValueError("n_out=%r: 1 .. %d" % (n_out, CEP_MAX_OUT))
+    if norm not in (None, "ortho"):
+        raise ValueError("norm=%r: None or \"ortho\"" % (norm,))
+    try:
+        lifter = float(lifter)
+    except (TypeError, ValueError):
+        raise ValueError("lifter must be a number")
+    if not (lifter >= 0.0 and np.isfinite(lifter)):
+        raise ValueError("lifter=%r: non-negative and finite (0: none)" % (lifter,))
+    q = np.arange(int(n_out), dtype=np.float64)[:, None]
+    f = np.arange(int(n_in), dtype=np.float64)[None, :]
+    m = np.cos(np.pi * q * (2.0 * f + 1.0) / (2.0 * int(n_in)))
+    if norm == "ortho":
+        m = m * np.where(q == 0, np.sqrt(1.0 / int(n_in)), np.sqrt(2.0 / int(n_in)))
+    else:
+        m = m * 2.0
+    if lifter:
+        m = m * (1.0 + (lifter / 2.0) * np.sin(np.pi * q / lifter))
+    return m.astype(np.float32)
+
+
+def _cep_params(n_in, matrix, delta_order, delta_width):
+    """(n_in, n_out, the matrix as contiguous float32 or None, order, width), or ValueError for what lw_cep_create refuses"""
+    if not _is_int(n_in) or not 1 <= n_in <= CEP_MAX_IN:
+        raise ValueError("n_in=%r: an integer in 1 .. %d" % (n_in, CEP_MAX_IN))
+    if not _is_int(delta_order) or not 0 <= delta_order <= 2:
+        raise ValueError("delta_order=%r: 0, 1 or 2" % (delta_order,))
+    if delta_order and (not _is_int(delta_width) or not 1 <= delta_width <= CEP_MAX_WIDTH):
+        raise ValueError("delta_width=%r: an integer in 1 .. %d" % (delta_width, CEP_MAX_WIDTH))
+    n_out = int(n_in)
+    if matrix is not None:
+        try:
+            matrix = np.ascontiguousarray(matrix, np.float32)
+        except (TypeError, ValueError):
+            raise ValueError("matrix= must be an array of numbers")
+        if matrix.ndim != 2 or matrix.shape[1] != n_in or not 1 <= matrix.shape[0] <= CEP_MAX_OUT:
+            raise ValueError("matrix= must be [n_out <= %d][n_in = %d], not %r" % (CEP_MAX_OUT, n_in, matrix.shape))
+        n_out = matrix.shape[0]
+    return int(n_in), n_out, matrix, int(delta_order), int(delta_width) if delta_order else 0
+
+
+class Cepstrum:
+    """lw_cep: feature rows [rows][C][n_in][frame capacity] -> [rows][C][n_out * (1 + delta_order)][frame capacity] on the GPU
+    (k_cep), by the rule of include/lewton_amd.h ("cepstra and deltas of feature rows"), a contract on bits: static line q is the
+    fmaf chain over the input lines with row q of matrix ([n_out][n_in]; None: the identity, a bit copy), the next n_out lines
+    are the regression deltas over +-delta_width frames with the edge frames replicated, the next n_out the deltas of those (HTK /
+    Kaldi order; what torchaudio's compute_deltas applied twice gives).  Parameter errors are ValueError and need no GPU; the
+    object itself lives on cuda:device."""
+
+    def __init__(self, n_in, matrix=None, delta_order=0, delta_width=2, device=0):
+        self.n_in, self.n_out, self._matrix, self.delta_order, self.delta_width = _cep_params(n_in, matrix, delta_order, delta_width)
+        self.device = device
+        _gpu()
+        err = C.c_int(0)
+        self._h = N.lw_cep_create(device, self.n_in, self.n_out, None if self._matrix is None else self._matrix.ctypes.data_as(C.c_void_p),
+                                  self.delta_order, self.delta_width, C.byref(err))
+        if not self._h:
+            if err.value in (N.ERR_UNSUPPORTED, N.ERR_NULL_ARG):
+                raise ValueError("lw_cep_create refused the parameters")
+            raise RuntimeError("lw_cep_create failed (%d): %s" % (err.value, N.device_error()))
+        assert self.features == self.n_out * (1 + self.delta_order)
+
+    @classmethod
+    def mfcc(cls, n_mels, n_mfcc=13, norm="ortho", lifter=0, delta_order=0, delta_width=2, device=0):
+        """the first n_mfcc DCT-II coefficients of n_mels log-mel lines (dct_matrix), with deltas on request"""
+        return cls(n_mels, dct_matrix(n_mfcc, n_mels, norm, lifter), delta_order, delta_width, device)
+
+    @classmethod
+    def deltas(cls, n_in, order=2, width=2, device=0):
+        """the lines themselves, bit for bit, then their deltas ("fbank + deltas")"""
+        return cls(n_in, None, order, width, device)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            N.lw_cep_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        if N is not None and getattr(N, "lw_cep_destroy", None) is not None:  # not during interpreter shutdown
+            self.close()
+
+    @property
+    def features(self):
+        """lines per row and channel of the output: n_out * (1 + delta_order)"""
+        return int(N.lw_cep_features(self._h))
+
+    @property
+    def tile_frames(self):
+        """the frames one workgroup produces (lw_cep_tile_frames)"""
+        return int(N.lw_cep_tile_frames(self._h))
+
+    def matrix(self):
+        """[n_out][n_in] float32 as the kernel reads it; None for the identity"""
+        n = int(N.lw_cep_matrix(self._h, None))
+        if n == 0:
+            return None
+        out = np.empty((self.n_out, self.n_in), np.float32)
+        assert n == out.size
+        N.lw_cep_matrix(self._h, out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def delta_weights(self):
+        """w_1 .. w_N float32 (empty without deltas)"""
+        out = np.empty(int(N.lw_cep_delta_weights(self._h, None)), np.float32)
+        N.lw_cep_delta_weights(self._h, out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def last_launches(self):
+        """kernels the last call queued: 1 per 65535 rows, 0 when nothing was to be written; -1: no call yet"""
+        return N.lw_cep_last_launches(self._h)
+
+    def run(self, feat, frames, out=None, fill_to=None, stream=None):
+        """lw_cep_rows: frames[i] frames of every line of row i of feat (float32 [rows][C][n_in][frame capacity]) -> the same
+        frames of the features lines of out (None: a zeroed tensor [rows][C][features][frame capacity]; it must not overlap feat).
+        fill_to: None, one count for all rows or one per row -- positions [frames[i], fill_to[i]) of every line of out receive 0.
+        Nothing else of out is written.  stream: a hipStream_t value; None = torch's current stream on the object's device.
+        Asynchronous; returns out."""
+        torch = _gpu()
+        if (feat.dtype != torch.float32 or feat.device.type != "cuda" or feat.device.index != self.device or not feat.is_contiguous() or
+                feat.dim() != 4 or feat.shape[2] != self.n_in):
+            raise ValueError("feat must be a contiguous float32 tensor [rows][C][%d][frames] on cuda:%d" % (self.n_in, self.device))
+        n_rows, ch, _, cap = feat.shape
+        if out is None:
+            out = torch.zeros((n_rows, ch, self.features, cap), dtype=torch.float32, device=feat.device)
+        if out.dtype != torch.float32 or out.device.type != "cuda" or out.device.index != self.device or not out.is_contiguous() or out.dim() != 4:
+            raise ValueError("out must be a contiguous float32 tensor [rows][C][features][frames] on cuda:%d" % self.device)
+        if tuple(out.shape) != (n_rows, ch, self.features, cap):
+            raise ValueError("out must be %r, not %r" % ((n_rows, ch, self.features, cap), tuple(out.shape)))
+        counts = [int(v) for v in (frames.tolist() if hasattr(frames, "tolist") else frames)]
+        if len(counts) != n_rows or any(v < 0 for v in counts):
+            raise ValueError("frames= needs one non-negative entry per row of feat")
+        fill = None
+        if fill_to is not None:
+            fill = fill_to.tolist() if hasattr(fill_to, "tolist") else fill_to
+            fill = [int(fill)] * n_rows if isinstance(fill, (int, np.integer)) else [int(v) for v in fill]
+            if len(fill) != n_rows or any(v < 0 for v in fill):
+                raise ValueError("fill_to= needs one non-negative count, or one per row of feat")
+            fill = np.asarray(fill, np.uint64)
+        counts = np.asarray(counts, np.uint64)
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream or None
+        rc = N.lw_cep_rows(self._h, ch, C.c_void_p(feat.data_ptr()), C.c_void_p(out.data_ptr()), n_rows, cap,
+                           counts.ctypes.data_as(C.c_void_p), None if fill is None else fill.ctypes.data_as(C.c_void_p), stream)
+        if rc in (N.ERR_NULL_ARG, N.ERR_CAPACITY, N.ERR_UNSUPPORTED):
+            raise ValueError("lw_cep_rows refused the call (%d)" % rc)
+        if rc:
+            raise RuntimeError("lw_cep_rows: %d %s" % (rc, N.device_error()))
+        return out
+
+
 def _normalizer(normalize, samples, device):
     """normalize= of decode_streams / decode_ogg_files -> (a Normalize or None, whether it is this call's own to close); ValueError
     before anything is decoded"""
