@@ -410,22 +410,69 @@ int lw_resampler_set_taps_in_lds(lw_resampler *rs, int on);
  *           and which NaN a NaN result is.  Every other bit is.
  * Exactly [0, n_frames(len)) of each of the F lines of a destination row and channel is written, nothing else.
  *
+ * lw_spec_create_ex takes a lw_spec_params and adds what a Kaldi-compatible front end (torchaudio.compliance.kaldi.fbank,
+ * kaldi-native-fbank) needs; lw_spec_create is lw_spec_create_ex with framing = LW_SPEC_FRAMES_STFT, remove_dc = energy = 0,
+ * preemphasis = 0.0, scale = 1.0, and its tables and results keep every bit; it takes LW_SPEC_HANN and LW_SPEC_RECT only, as
+ * before.  All options are orthogonal to each other.
+ *   windows   with a = 2 pi i / (win_length - 1), symmetric (these four need win_length >= 2):
+ *           LW_SPEC_HAMMING 0.54 - 0.46 cos a;  LW_SPEC_HANN_SYM 0.5 - 0.5 cos a;  LW_SPEC_POVEY pow(0.5 - 0.5 cos a, 0.85);
+ *           LW_SPEC_BLACKMAN 0.42 - 0.5 cos a + 0.08 cos 2a.
+ *   framing   LW_SPEC_FRAMES_STFT: the rule above; `center` applies only here.  The Kaldi framings count frames by the WINDOW,
+ *           which starts at sample 0 of the frame: o = 0, the support is k in [0, win_length) of an n_fft-point transform.
+ *           LW_SPEC_FRAMES_KALDI_SNIP (snip_edges): n_frames = len < win_length ? 0 : 1 + (len - win_length) / hop; frame t
+ *           starts at t * hop; nothing is padded.
+ *           LW_SPEC_FRAMES_KALDI_EDGES: n_frames = (len + hop / 2) / hop; frame t starts at t * hop + hop / 2 - win_length / 2
+ *           (integer divisions of the positive quantities, a signed 64-bit result).  x[i] = x[-i - 1] for i < 0 and
+ *           x[2 len - 1 - i] for i >= len: one reflection that repeats the edge sample, LW_SPEC_PAD_SYMMETRIC, the pad mode such
+ *           an object is in.  A row is refused (LW_ERR_CAPACITY) when the first index any of its frames touches is < -len or
+ *           the last is > 2 len - 1: a second reflection is not offered.  lw_spec_set_pad_mode on a Kaldi-framed object is
+ *           LW_ERR_UNSUPPORTED.  lw_spec_frames answers by the object's framing.
+ *   folded    pre-emphasis (coefficient c = preemphasis in [0, 1]), window and scale (finite, > 0; Kaldi callers pass 32768) are
+ *           linear in the frame and live in the table.  With g_k = w[k] * cos(2 pi (((k + o) * j) mod n_fft) / n_fft) in double
+ *           and g_W = 0:  C[k][j] = (float)(scale * ((k == 0 ? 1.0 - c : 1.0) * g_k - c * g_{k+1})), S the same with -sin --
+ *           Kaldi's y_0 = x_0 - c x_0, y_k = x_k - c x_{k-1}, then the window.  c = 0 and scale = 1 give g_k itself.
+ *           lw_spec_basis returns this table.
+ *   per frame (remove_dc, energy) over a frame's W = win_length support samples x_k, after padding:
+ *           S1 = the fold of (double)x_k for k ascending from +0.0, sequential; S2 = the same fold of (double)x_k * (double)x_k
+ *           (exact in double).  mu = (float)(S1 / (double)W).  x'_k = x_k - mu with remove_dc (one rounded f32 subtraction),
+ *           else x_k; the spectrum chains run over x'_k.  Ed = remove_dc ? S2 - (S1 * S1) / (double)W : S2, every operation
+ *           one rounding; Ed = 0 if !(Ed > 0);  E = (float)(Ed * (scale * scale)).  With energy, E is line 0 of the
+ *           destination and the spectrum or mel lines follow from line 1: F = lw_spec_features counts it.  (Kaldi's
+ *           raw_energy = true and column order without htk_compat; the logarithm is lw_feat_rows' business.)
+ *
  * lw_spec_rows: source row i (len[i] samples per channel) goes to destination row dst_row[i] (NULL: row i).  len and dst_row
  * are HOST arrays, copied during the call.  Asynchronous on hip_stream; calls on one object may be queued back to back.
  * Refusals, decided on the host before anything is queued, so a refused call has written nothing:
  *   LW_ERR_NULL_ARG     sp NULL, len NULL with rows, d_src / d_dst NULL with frames to compute; (create) fb NULL with n_mels > 0
- *   LW_ERR_UNSUPPORTED  (create) a parameter outside the limits above, an unknown window;  (rows) an i16 format;
- *                       (set_pad_mode) an unknown mode, reflect on an object that is not centred
+ *   LW_ERR_UNSUPPORTED  (create) a parameter outside the limits above, an unknown window or framing, center with a Kaldi framing,
+ *                       a symmetric window with win_length < 2, preemphasis outside [0, 1] or NaN, scale not finite or <= 0,
+ *                       remove_dc or energy other than 0 or 1, reserved != 0;  (rows) an i16 format;
+ *                       (set_pad_mode) an unknown mode, reflect on an object that is not centred, any mode on a Kaldi-framed object
  *   LW_ERR_DEVICE       (create) no such device, or its LDS per workgroup is below the 67 648 bytes k_spec needs (asked of the
  *                       device, not assumed)
  *   LW_ERR_CAPACITY     len[i] > src_capacity, n_frames(len[i]) > frame_capacity, dst_row[i] >= n_dst_rows, two source rows for
- *                       one destination row, ch == 0 or > 255, a row too short for one reflection under LW_SPEC_PAD_REFLECT */
+ *                       one destination row, ch == 0 or > 255, a row too short for one reflection under LW_SPEC_PAD_REFLECT or
+ *                       LW_SPEC_PAD_SYMMETRIC */
 typedef struct lw_spec lw_spec;
-enum { LW_SPEC_HANN = 0, LW_SPEC_RECT = 1 };
+enum { LW_SPEC_HANN = 0, LW_SPEC_RECT = 1, LW_SPEC_POVEY = 2, LW_SPEC_HAMMING = 3, LW_SPEC_HANN_SYM = 4, LW_SPEC_BLACKMAN = 5 };
+enum { LW_SPEC_FRAMES_STFT = 0, LW_SPEC_FRAMES_KALDI_SNIP = 1, LW_SPEC_FRAMES_KALDI_EDGES = 2 };
 #define LW_SPEC_MAX_FFT 2048
 #define LW_SPEC_MAX_MELS 256
+typedef struct lw_spec_params {
+	uint32_t n_fft, win_length, hop, n_mels;
+	const float *fb;    /* n_mels x B host floats, copied at creation; NULL with n_mels == 0 */
+	int32_t window;     /* LW_SPEC_HANN ... LW_SPEC_BLACKMAN */
+	int32_t center;     /* LW_SPEC_FRAMES_STFT only */
+	int32_t framing;    /* LW_SPEC_FRAMES_* */
+	int32_t remove_dc;  /* 0 or 1 */
+	int32_t energy;     /* 0 or 1 */
+	uint32_t reserved;  /* must be 0 */
+	double preemphasis; /* in [0, 1] */
+	double scale;       /* finite, > 0 */
+} lw_spec_params;
 lw_spec *lw_spec_create(int device, uint32_t n_fft, uint32_t win_length, uint32_t hop, int window, int center, uint32_t n_mels,
 		const float *fb, int *err);
+lw_spec *lw_spec_create_ex(int device, const lw_spec_params *p, int *err);
 void lw_spec_destroy(lw_spec *sp);
 uint32_t lw_spec_bins(const lw_spec *sp);                /* B */
 uint32_t lw_spec_features(const lw_spec *sp);            /* F */
@@ -441,7 +488,7 @@ int lw_spec_rows(lw_spec *sp, int fmt, uint32_t ch, const void *d_src, size_t n_
 int lw_spec_last_route(const lw_spec *sp);
 int lw_spec_set_route(lw_spec *sp, int route);
 /* what x[i] is outside [0, len) for the calls that follow ("reflect" above); lw_spec_pad_mode: the mode, -1 for NULL */
-enum { LW_SPEC_PAD_ZERO = 0, LW_SPEC_PAD_REFLECT = 1 };
+enum { LW_SPEC_PAD_ZERO = 0, LW_SPEC_PAD_REFLECT = 1, LW_SPEC_PAD_SYMMETRIC = 2 /* LW_SPEC_FRAMES_KALDI_EDGES' own, never set */ };
 int lw_spec_set_pad_mode(lw_spec *sp, int mode);
 int lw_spec_pad_mode(const lw_spec *sp);
 

@@ -57,6 +57,12 @@ class FeatParams(C.Structure):
     _fields_ = [("log", C.c_int32), ("scope", C.c_int32), ("floor", C.c_float), ("top", C.c_float), ("add", C.c_float), ("mul", C.c_float)]
 
 
+class SpecParams(C.Structure):
+    _fields_ = [("n_fft", C.c_uint32), ("win_length", C.c_uint32), ("hop", C.c_uint32), ("n_mels", C.c_uint32), ("fb", C.c_void_p),
+                ("window", C.c_int32), ("center", C.c_int32), ("framing", C.c_int32), ("remove_dc", C.c_int32), ("energy", C.c_int32),
+                ("reserved", C.c_uint32), ("preemphasis", C.c_double), ("scale", C.c_double)]
+
+
 class NormParams(C.Structure):
     _fields_ = [("center", C.c_int32), ("scale", C.c_int32), ("scope", C.c_int32), ("reserved", C.c_int32), ("eps", C.c_double),
                 ("target", C.c_double)]
@@ -163,6 +169,7 @@ SYMBOLS = {
     "lw_resampler_last_route": (C.c_int, [C.c_void_p]),
     "lw_resampler_set_taps_in_lds": (C.c_int, [C.c_void_p, C.c_int]),
     "lw_spec_create": (C.c_void_p, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_uint32, C.c_void_p, intp]),
+    "lw_spec_create_ex": (C.c_void_p, [C.c_int, C.POINTER(SpecParams), intp]),
     "lw_spec_destroy": (None, [C.c_void_p]),
     "lw_spec_bins": (C.c_uint32, [C.c_void_p]),
     "lw_spec_features": (C.c_uint32, [C.c_void_p]),

@@ -3,8 +3,10 @@
 // [row][ch][F][frame], by the rule of include/lewton_amd.h ("spectral frames of rows"), bit for bit:
 //   re[j] = fold over the window's support, k ascending, of fmaf(x_k, C[k][j], acc) from +0.0;  im[j] likewise with S
 //   P[j]  = fmaf(im, im, re * re);  m[q] = fold over j = 0 .. B - 1 ascending of fmaf(P[j], fb[q][j], acc) from +0.0
-//   x = +0.0 outside [0, len), or the reflected sample (LW_SPEC_PAD_REFLECT, lw_sp_reflect).  No chain is ever split; the unit is
-//   compiled with -ffp-contract=off like all others.
+//   x = +0.0 outside [0, len), or the reflected sample (LW_SPEC_PAD_REFLECT, lw_sp_reflect; LW_SPEC_PAD_SYMMETRIC, lw_sp_symmetric).
+//   No chain is ever split; the unit is compiled with -ffp-contract=off like all others.
+//   With remove_dc or energy (lw_spec_create_ex) a per-frame prologue runs first (lw_sp_pro_*, k_spec<.., .., 1>): x_k - mu
+//   takes x_k's place in the chains, and the frame's energy goes to line 0.  Pre-emphasis, window and scale live in the table.
 //
 // Work: a tile = LW_SP_TF = 32 consecutive frames of one (row, channel), one workgroup of 256 lanes (four waves) per tile, grid =
 // (tiles, channels, rows).  The framed DFT is a GEMM, D[bin][frame] = sum_k basis[k][bin] * x[frame * hop + k], run on
@@ -89,10 +91,20 @@ LW_SP_FN int64_t lw_sp_reflect(const LwSpTile &t, int64_t i)
 // becomes a uniform branch between a lane's loads and ends their overlap -- or LW_SP_PAD_ARGS: as a.pad_mode says
 // (the host programs, which call lw_sp_stage without it)
 #define LW_SP_PAD_ARGS (-1)
+// where x[i] is read under symmetric padding (LW_SPEC_PAD_SYMMETRIC, Kaldi's frames without snip_edges): the edge sample is
+// repeated, -i - 1 below 0 and 2 len - 1 - i from len on (one reflection, as above)
+LW_SP_FN int64_t lw_sp_symmetric(const LwSpTile &t, int64_t i)
+{
+	const int64_t up = i < 0 ? -i - 1 : i;
+	return (uint64_t)up >= t.len ? 2 * (int64_t)t.len - 1 - up : up;
+}
+
 template <int PAD> LW_SP_FN float lw_sp_x(const LwSpecArgs &a, const LwSpTile &t, int64_t i)
 {
-	if (PAD == 1 || (PAD == LW_SP_PAD_ARGS && a.pad_mode))
+	if (PAD == 1 || (PAD == LW_SP_PAD_ARGS && a.pad_mode == 1))
 		i = lw_sp_reflect(t, i);
+	if (PAD == 2 || (PAD == LW_SP_PAD_ARGS && a.pad_mode == 2))
+		i = lw_sp_symmetric(t, i);
 	const bool in = i >= 0 && (uint64_t)i < t.len;
 	const uint64_t c = i < 0 ? 0 : (uint64_t)i < t.len ? (uint64_t)i : t.len - 1;
 	const float v = a.src[t.s_at + c * a.s.el];
@@ -122,7 +134,10 @@ LW_SP_FN void lw_sp_zero_mel(LwSpLane &st)
 }
 
 // ---- stage: K tile kt of pass `pass` into LDS; all of a lane's loads are in flight before its first store
-template <int PAD = LW_SP_PAD_ARGS> LW_SP_FN void lw_sp_stage(const LwSpecArgs &a, const LwSpTile &t, uint32_t pass, uint32_t kt, uint32_t tid, float *lds)
+// PRO (the per-frame prologue ran): x'_k = x_k - mu, one rounded subtraction, of the padded sample and before the tail's zeros;
+// mu0 / mu1 are the means of the lane's two frames (lw_sp_pro_mu), +0.0 without remove_dc, which leaves every x as it is
+template <int PAD = LW_SP_PAD_ARGS, int PRO = 0>
+LW_SP_FN void lw_sp_stage(const LwSpecArgs &a, const LwSpTile &t, uint32_t pass, uint32_t kt, uint32_t tid, float *lds, float mu0 = 0.0f, float mu1 = 0.0f)
 {
 	const uint32_t k0 = kt * LW_SP_KT;
 	const LwSpF4 *g = (const LwSpF4 *)(a.basis + ((size_t)pass * a.k_pad + k0) * (2u * LW_SP_COLS));
@@ -136,7 +151,9 @@ template <int PAD = LW_SP_PAD_ARGS> LW_SP_FN void lw_sp_stage(const LwSpecArgs &
 #pragma unroll
 	for (uint32_t q = 0; q < NX; q++) {
 		const uint32_t e = tid + q * LW_SP_THREADS, kk = e % LW_SP_KT, f = e / LW_SP_KT;
-		const float v = lw_sp_x<PAD>(a, t, lw_sp_index(a, t, f, k0 + kk));
+		float v = lw_sp_x<PAD>(a, t, lw_sp_index(a, t, f, k0 + kk));
+		if (PRO)
+			v = v - (q ? mu1 : mu0);
 		vx[q] = k0 + kk < a.win_length ? v : 0.0f;
 	}
 	LwSpF4 *as = (LwSpF4 *)(lds + LW_SP_LDS_A);
@@ -226,16 +243,17 @@ LW_SP_FN void lw_sp_power(const LwSpecArgs &a, uint32_t pass, uint32_t tid, floa
 }
 
 // ---- without a mel matrix: the pass's bins from LDS to their lines, consecutive lanes on consecutive frames
-LW_SP_FN void lw_sp_store_power(const LwSpecArgs &a, const LwSpTile &t, uint32_t pass, uint32_t tid, const float *lds)
+// (PRO: the lines follow the energy line when there is one)
+template <int PRO = 0> LW_SP_FN void lw_sp_store_power(const LwSpecArgs &a, const LwSpTile &t, uint32_t pass, uint32_t tid, const float *lds)
 {
-	const uint32_t f = tid % LW_SP_TF;
+	const uint32_t f = tid % LW_SP_TF, line0 = PRO ? a.energy : 0u;
 	if (t.f0 + f >= t.n_frames)
 		return;
 	for (uint32_t c = tid / LW_SP_TF; c < LW_SP_COLS; c += LW_SP_THREADS / LW_SP_TF) {
 		const uint32_t bin = pass * LW_SP_COLS + c;
 		if (bin >= a.bins)
 			break;
-		a.dst[t.d_at + (uint64_t)bin * a.d_line + t.f0 + f] = lds[LW_SP_LDS_P + c * LW_SP_TF + f];
+		a.dst[t.d_at + (uint64_t)(bin + line0) * a.d_line + t.f0 + f] = lds[LW_SP_LDS_P + c * LW_SP_TF + f];
 	}
 }
 
@@ -278,9 +296,9 @@ LW_SP_FN void lw_sp_mel(const LwSpecArgs &a, uint32_t pass, uint32_t jc, uint32_
 	}
 }
 
-LW_SP_FN void lw_sp_store_mel(const LwSpecArgs &a, const LwSpTile &t, uint32_t tid, const LwSpLane &st)
+template <int PRO = 0> LW_SP_FN void lw_sp_store_mel(const LwSpecArgs &a, const LwSpTile &t, uint32_t tid, const LwSpLane &st)
 {
-	const uint32_t f = tid % LW_SP_TF, g = tid / LW_SP_TF;
+	const uint32_t f = tid % LW_SP_TF, g = tid / LW_SP_TF, line0 = PRO ? a.energy : 0u;
 	if (t.f0 + f >= t.n_frames)
 		return;
 #pragma unroll
@@ -289,7 +307,7 @@ LW_SP_FN void lw_sp_store_mel(const LwSpecArgs &a, const LwSpTile &t, uint32_t t
 		for (uint32_t i = 0; i < 4u; i++) {
 			const uint32_t q = 4u * (g + 8u * b) + i;
 			if (q < a.n_mels)
-				a.dst[t.d_at + (uint64_t)q * a.d_line + t.f0 + f] = st.mel[b][i];
+				a.dst[t.d_at + (uint64_t)(q + line0) * a.d_line + t.f0 + f] = st.mel[b][i];
 		}
 }
 
@@ -300,9 +318,109 @@ LW_SP_FN uint32_t lw_sp_slices(const LwSpecArgs &a, uint32_t pass)
 	return (n + LW_SP_JT - 1u) / LW_SP_JT;
 }
 
+// ---- the per-frame prologue (remove_dc || energy; include/lewton_amd.h "DC removal and energy"): of each of the tile's 32 frames
+//   S1 = the fold of (double)x_k, k ascending from +0.0, sequential;  S2 = the same fold of (double)x_k * (double)x_k (exact)
+// over the W support samples after padding; mu = (float)(S1 / W) goes to the staging step, E to line 0 of the destination.  Four
+// phases with a barrier behind each, all before the first stage of the K loop, in LDS that is free until then: the tile's span
+// of samples in the P region (LW_SP_SPAN_AT; a.span = 0: it does not fit, and the chains read the row), the sums and mu where
+// the frame tile will be.  The 64 chains of W dependent f64 additions are what the prologue costs: 32 lanes of wave 0 fold S1, 32
+// lanes of wave 1 fold S2, side by side on two SIMDs.
+#define LW_SP_PRO_S1 LW_SP_LDS_X                    // [32] doubles
+#define LW_SP_PRO_S2 (LW_SP_LDS_X + 2u * LW_SP_TF)  // [32] doubles
+#define LW_SP_PRO_MU (LW_SP_LDS_X + 4u * LW_SP_TF)  // [32] floats
+static_assert(5u * LW_SP_TF <= LW_SP_KT * LW_SP_XS && LW_SP_LDS_X % 2u == 0, "the prologue's sums fit the frame tile's place, 8-byte aligned");
+
+LW_SP_FN void lw_sp_put_d(float *at, double v)
+{
+	__builtin_memcpy(at, &v, sizeof v);
+}
+
+LW_SP_FN double lw_sp_get_d(const float *at)
+{
+	double v;
+	__builtin_memcpy(&v, at, sizeof v);
+	return v;
+}
+
+template <int PAD = LW_SP_PAD_ARGS> LW_SP_FN void lw_sp_pro_span(const LwSpecArgs &a, const LwSpTile &t, uint32_t tid, float *lds)
+{
+	// eight loads of a lane in flight before its first store (a load beyond the span goes to a clamped index like any other)
+	for (uint32_t s0 = tid; s0 < a.span; s0 += 8u * LW_SP_THREADS) {
+		float v[8];
+#pragma unroll
+		for (uint32_t q = 0; q < 8u; q++)
+			v[q] = lw_sp_x<PAD>(a, t, t.x0 + (int64_t)(s0 + q * LW_SP_THREADS));
+#pragma unroll
+		for (uint32_t q = 0; q < 8u; q++) {
+			const uint32_t s = s0 + q * LW_SP_THREADS;
+			if (s < a.span)
+				lds[LW_SP_LDS_P + LW_SP_SPAN_AT(s)] = v[q];
+		}
+	}
+}
+
+template <int PAD = LW_SP_PAD_ARGS> LW_SP_FN void lw_sp_pro_sums(const LwSpecArgs &a, const LwSpTile &t, uint32_t tid, float *lds)
+{
+	const uint32_t wave = tid >> 6, f = tid & 63u;
+	if (wave > 1u || f >= LW_SP_TF)
+		return;
+	double s = 0.0;
+	if (a.span) {
+		const uint32_t s0 = f * a.hop;
+		const float *p = lds + LW_SP_LDS_P;
+		if (wave == 0) { // (a loop per wave: no select, and no multiply in the S1 chain)
+#pragma unroll 8
+			for (uint32_t k = 0; k < a.win_length; k++)
+				s = s + (double)p[LW_SP_SPAN_AT(s0 + k)];
+		} else {
+#pragma unroll 8
+			for (uint32_t k = 0; k < a.win_length; k++) {
+				const double d = (double)p[LW_SP_SPAN_AT(s0 + k)];
+				s = s + d * d;
+			}
+		}
+	} else {
+#pragma unroll 8
+		for (uint32_t k = 0; k < a.win_length; k++) {
+			const double d = (double)lw_sp_x<PAD>(a, t, lw_sp_index(a, t, f, k));
+			s = s + (wave ? d * d : d);
+		}
+	}
+	lw_sp_put_d(lds + (wave ? LW_SP_PRO_S2 : LW_SP_PRO_S1) + 2u * f, s);
+}
+
+// mu of the tile's frames into LDS (+0.0 without remove_dc), and E of the frames that exist to line 0: every operation one
+// rounding (the unit is compiled with -ffp-contract=off), Ed = 0 unless Ed > 0 (a NaN too)
+LW_SP_FN void lw_sp_pro_finish(const LwSpecArgs &a, const LwSpTile &t, uint32_t tid, float *lds)
+{
+	if (tid >= LW_SP_TF)
+		return;
+	const double S1 = lw_sp_get_d(lds + LW_SP_PRO_S1 + 2u * tid), S2 = lw_sp_get_d(lds + LW_SP_PRO_S2 + 2u * tid), W = (double)a.win_length;
+	const float mu = (float)(S1 / W);
+	lds[LW_SP_PRO_MU + tid] = a.remove_dc ? mu : 0.0f;
+	if (!a.energy || t.f0 + tid >= t.n_frames)
+		return;
+	double Ed = S2;
+	if (a.remove_dc) {
+		const double sq = S1 * S1, part = sq / W;
+		Ed = S2 - part;
+	}
+	if (!(Ed > 0.0))
+		Ed = 0.0;
+	a.dst[t.d_at + t.f0 + tid] = (float)(Ed * a.escale);
+}
+
+// the means of the two frames a lane stages in every K tile (frame e / LW_SP_KT of e = tid + q * 256)
+LW_SP_FN void lw_sp_pro_mu(uint32_t tid, const float *lds, float &mu0, float &mu1)
+{
+	mu0 = lds[LW_SP_PRO_MU + tid / LW_SP_KT];
+	mu1 = lds[LW_SP_PRO_MU + tid / LW_SP_KT + LW_SP_THREADS / LW_SP_KT];
+}
+
 #ifndef LW_SPEC_HOST
 
-template <int ROUTE, int PAD> __global__ void __launch_bounds__(LW_SP_THREADS) k_spec(LwSpecArgs a)
+// PRO = 0 is the kernel without the prologue, to the instruction: what every object without remove_dc and energy runs
+template <int ROUTE, int PAD, int PRO> __global__ void __launch_bounds__(LW_SP_THREADS) k_spec(LwSpecArgs a)
 {
 	extern __shared__ float lw_sp_lds[];
 	LwSpTile t;
@@ -311,10 +429,21 @@ template <int ROUTE, int PAD> __global__ void __launch_bounds__(LW_SP_THREADS) k
 	const uint32_t tid = threadIdx.x;
 	LwSpLane st;
 	lw_sp_zero_mel(st);
+	float mu0 = 0.0f, mu1 = 0.0f;
+	if (PRO) {
+		lw_sp_pro_span<PAD>(a, t, tid, lw_sp_lds);
+		__syncthreads();
+		lw_sp_pro_sums<PAD>(a, t, tid, lw_sp_lds);
+		__syncthreads();
+		lw_sp_pro_finish(a, t, tid, lw_sp_lds);
+		__syncthreads();
+		lw_sp_pro_mu(tid, lw_sp_lds, mu0, mu1);
+		__syncthreads();
+	}
 	for (uint32_t pass = 0; pass < a.passes; pass++) {
 		lw_sp_zero_acc(st);
 		for (uint32_t kt = 0; kt < a.k_pad / LW_SP_KT; kt++) {
-			lw_sp_stage<PAD>(a, t, pass, kt, tid, lw_sp_lds);
+			lw_sp_stage<PAD, PRO>(a, t, pass, kt, tid, lw_sp_lds, mu0, mu1);
 			__syncthreads();
 			lw_sp_mma<ROUTE>(a, pass, tid, lw_sp_lds, st);
 			__syncthreads();
@@ -322,7 +451,7 @@ template <int ROUTE, int PAD> __global__ void __launch_bounds__(LW_SP_THREADS) k
 		lw_sp_power(a, pass, tid, lw_sp_lds, st);
 		__syncthreads();
 		if (a.n_mels == 0) {
-			lw_sp_store_power(a, t, pass, tid, lw_sp_lds);
+			lw_sp_store_power<PRO>(a, t, pass, tid, lw_sp_lds);
 			continue; // (the next pass's barriers stand between these reads and its power stores)
 		}
 		for (uint32_t jc = 0; jc < lw_sp_slices(a, pass); jc++) {
@@ -333,18 +462,23 @@ template <int ROUTE, int PAD> __global__ void __launch_bounds__(LW_SP_THREADS) k
 		}
 	}
 	if (a.n_mels)
-		lw_sp_store_mel(a, t, tid, st);
+		lw_sp_store_mel<PRO>(a, t, tid, st);
 }
 
-template <int ROUTE, int PAD> static hipError_t lw_sp_launch(const LwSpecArgs &a, dim3 grid, hipStream_t st)
+template <int ROUTE, int PAD, int PRO> static hipError_t lw_sp_launch(const LwSpecArgs &a, dim3 grid, hipStream_t st)
 {
 	static LwPerDeviceOnce once; // above the default limit of dynamic LDS: per device, once
 	const hipError_t e = once.run([] {
-		return hipFuncSetAttribute((const void *)k_spec<ROUTE, PAD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LW_SP_LDS_FLOATS * sizeof(float)));
+		return hipFuncSetAttribute((const void *)k_spec<ROUTE, PAD, PRO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LW_SP_LDS_FLOATS * sizeof(float)));
 	});
 	if (e != hipSuccess)
 		return e;
-	return lw_launch_k(k_spec<ROUTE, PAD>, grid, dim3(LW_SP_THREADS), (size_t)LW_SP_LDS_FLOATS * sizeof(float), st, a);
+	return lw_launch_k(k_spec<ROUTE, PAD, PRO>, grid, dim3(LW_SP_THREADS), (size_t)LW_SP_LDS_FLOATS * sizeof(float), st, a);
+}
+
+template <int ROUTE, int PAD> static hipError_t lw_sp_launch_pro(const LwSpecArgs &a, dim3 grid, hipStream_t st)
+{
+	return a.remove_dc || a.energy ? lw_sp_launch<ROUTE, PAD, 1>(a, grid, st) : lw_sp_launch<ROUTE, PAD, 0>(a, grid, st);
 }
 
 hipError_t lw_launch_spec(const LwSpecArgs &a, int route, uint32_t tiles, uint32_t ch, uint32_t n_rows, hipStream_t st)
@@ -357,10 +491,14 @@ hipError_t lw_launch_spec(const LwSpecArgs &a, int route, uint32_t tiles, uint32
 	const dim3 grid(tiles, ch, n_rows);
 	if (route != LW_SP_ROUTE_MFMA && route != LW_SP_ROUTE_FMA)
 		return hipErrorInvalidValue;
+	if (a.span && (a.span != (LW_SP_TF - 1u) * a.hop + a.win_length || !lw_spec_span_fits(a.hop, a.win_length))) // (it indexes LDS)
+		return hipErrorInvalidValue;
 	if (a.pad_mode == 0)
-		return route == LW_SP_ROUTE_MFMA ? lw_sp_launch<LW_SP_ROUTE_MFMA, 0>(a, grid, st) : lw_sp_launch<LW_SP_ROUTE_FMA, 0>(a, grid, st);
+		return route == LW_SP_ROUTE_MFMA ? lw_sp_launch_pro<LW_SP_ROUTE_MFMA, 0>(a, grid, st) : lw_sp_launch_pro<LW_SP_ROUTE_FMA, 0>(a, grid, st);
 	if (a.pad_mode == 1)
-		return route == LW_SP_ROUTE_MFMA ? lw_sp_launch<LW_SP_ROUTE_MFMA, 1>(a, grid, st) : lw_sp_launch<LW_SP_ROUTE_FMA, 1>(a, grid, st);
+		return route == LW_SP_ROUTE_MFMA ? lw_sp_launch_pro<LW_SP_ROUTE_MFMA, 1>(a, grid, st) : lw_sp_launch_pro<LW_SP_ROUTE_FMA, 1>(a, grid, st);
+	if (a.pad_mode == 2)
+		return route == LW_SP_ROUTE_MFMA ? lw_sp_launch_pro<LW_SP_ROUTE_MFMA, 2>(a, grid, st) : lw_sp_launch_pro<LW_SP_ROUTE_FMA, 2>(a, grid, st);
 	return hipErrorInvalidValue;
 }
 

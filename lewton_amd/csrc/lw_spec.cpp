@@ -25,6 +25,9 @@ struct lw_spec {
 	uint32_t n_fft = 0, win_length = 0, hop = 0, n_mels = 0;
 	bool center = false;
 	int pad_mode = LW_SPEC_PAD_ZERO;
+	int framing = LW_SPEC_FRAMES_STFT;
+	bool remove_dc = false, energy = false;
+	double scale = 1.0;
 	LwSpecPlan plan{};
 	std::vector<float> basis;                  // [2][win_length][B], the public order
 	float *d_basis = nullptr, *d_fb = nullptr; // the kernel's orders (lw_spec.hpp)
@@ -40,12 +43,55 @@ extern "C" {
 lw_spec *lw_spec_create(int device, uint32_t n_fft, uint32_t win_length, uint32_t hop, int window, int center, uint32_t n_mels, const float *fb,
 		int *err)
 {
+	if (window != LW_SPEC_HANN && window != LW_SPEC_RECT) { // this entry point keeps its two windows; the others come with lw_spec_create_ex
+		if (err)
+			*err = LW_ERR_UNSUPPORTED;
+		return nullptr;
+	}
+	lw_spec_params p{};
+	p.n_fft = n_fft, p.win_length = win_length, p.hop = hop, p.n_mels = n_mels, p.fb = fb;
+	p.window = window, p.center = center, p.framing = LW_SPEC_FRAMES_STFT;
+	p.preemphasis = 0.0, p.scale = 1.0;
+	return lw_spec_create_ex(device, &p, err);
+}
+
+// w[i] of a window of W samples, in double
+static double lw_sp_window(int window, uint32_t i, uint32_t W)
+{
+	if (window == LW_SPEC_RECT)
+		return 1.0;
+	if (window == LW_SPEC_HANN)
+		return 0.5 - 0.5 * std::cos(2.0 * M_PI * (double)i / (double)W);
+	const double a = 2.0 * M_PI * (double)i / (double)(W - 1u);
+	if (window == LW_SPEC_HAMMING)
+		return 0.54 - 0.46 * std::cos(a);
+	if (window == LW_SPEC_HANN_SYM)
+		return 0.5 - 0.5 * std::cos(a);
+	if (window == LW_SPEC_POVEY)
+		return std::pow(0.5 - 0.5 * std::cos(a), 0.85);
+	return 0.42 - 0.5 * std::cos(a) + 0.08 * std::cos(2.0 * a); // LW_SPEC_BLACKMAN
+}
+
+lw_spec *lw_spec_create_ex(int device, const lw_spec_params *prm, int *err)
+{
 	int dummy;
 	if (!err)
 		err = &dummy;
 	*err = LW_OK;
+	if (!prm) {
+		*err = LW_ERR_NULL_ARG;
+		return nullptr;
+	}
+	const uint32_t n_fft = prm->n_fft, win_length = prm->win_length, hop = prm->hop, n_mels = prm->n_mels;
+	const int window = prm->window, center = prm->center;
+	const float *fb = prm->fb;
+	const bool kaldi = prm->framing == LW_SPEC_FRAMES_KALDI_SNIP || prm->framing == LW_SPEC_FRAMES_KALDI_EDGES;
+	const bool symmetric = window == LW_SPEC_POVEY || window == LW_SPEC_HAMMING || window == LW_SPEC_HANN_SYM || window == LW_SPEC_BLACKMAN;
 	if (n_fft < 2 || n_fft > LW_SPEC_MAX_FFT || win_length < 1 || win_length > n_fft || hop < 1 || hop > 65535 || n_mels > LW_SPEC_MAX_MELS ||
-			(window != LW_SPEC_HANN && window != LW_SPEC_RECT)) {
+			(window != LW_SPEC_HANN && window != LW_SPEC_RECT && !symmetric) || (symmetric && win_length < 2) ||
+			(prm->framing != LW_SPEC_FRAMES_STFT && !kaldi) || (kaldi && center) || (prm->remove_dc != 0 && prm->remove_dc != 1) ||
+			(prm->energy != 0 && prm->energy != 1) || !(prm->preemphasis >= 0.0 && prm->preemphasis <= 1.0) ||
+			!(prm->scale > 0.0 && std::isfinite(prm->scale)) || prm->reserved != 0) {
 		*err = LW_ERR_UNSUPPORTED;
 		return nullptr;
 	}
@@ -63,23 +109,41 @@ lw_spec *lw_spec_create(int device, uint32_t n_fft, uint32_t win_length, uint32_
 	auto sp = std::make_unique<lw_spec>();
 	sp->device = device;
 	sp->n_fft = n_fft, sp->win_length = win_length, sp->hop = hop, sp->n_mels = n_mels, sp->center = center != 0;
-	const LwSpecPlan p = sp->plan = lw_spec_plan(n_fft, win_length, n_mels);
+	sp->framing = prm->framing, sp->remove_dc = prm->remove_dc != 0, sp->energy = prm->energy != 0, sp->scale = prm->scale;
+	if (prm->framing == LW_SPEC_FRAMES_KALDI_EDGES)
+		sp->pad_mode = LW_SPEC_PAD_SYMMETRIC;
+	sp->plan = lw_spec_plan(n_fft, win_length, n_mels);
+	if (kaldi)
+		sp->plan.offset = 0; // the window starts at sample 0 of the frame
+	const LwSpecPlan p = sp->plan;
 	const uint32_t B = p.bins;
-	// ---- the tables, in double, each rounded once
+	// ---- the tables, in double, each rounded once: pre-emphasis, window and scale folded in (c = 0 and scale = 1: g itself)
 	sp->basis.resize((size_t)2 * win_length * B);
 	std::vector<float> dev((size_t)p.passes * p.k_pad * 2 * LW_SP_COLS, 0.0f);
-	for (uint32_t i = 0; i < win_length; i++) {
-		const double w = window == LW_SPEC_HANN ? 0.5 - 0.5 * std::cos(2.0 * M_PI * (double)i / (double)win_length) : 1.0;
+	const double c = prm->preemphasis, scale = prm->scale;
+	std::vector<double> win(win_length);
+	for (uint32_t i = 0; i < win_length; i++)
+		win[i] = lw_sp_window(window, i, win_length);
+	auto g = [&](uint32_t i, uint32_t j, bool sine) { // g_i of bin j; g_W = 0
+		if (i >= win_length)
+			return 0.0;
+		const double w = win[i];
 		const uint64_t k = (uint64_t)i + p.offset;
-		for (uint32_t j = 0; j < B; j++) {
-			const double ang = 2.0 * M_PI * (double)(k * j % n_fft) / (double)n_fft;
-			const float c = (float)(w * std::cos(ang)), s = (float)(-w * std::sin(ang));
-			sp->basis[(size_t)i * B + j] = c;
-			sp->basis[((size_t)win_length + i) * B + j] = s;
-			dev[lw_spec_basis_at(p, i, 0, j)] = c;
-			dev[lw_spec_basis_at(p, i, 1, j)] = s;
-		}
-	}
+		const double ang = 2.0 * M_PI * (double)(k * j % n_fft) / (double)n_fft;
+		return sine ? -w * std::sin(ang) : w * std::cos(ang);
+	};
+	for (uint32_t i = 0; i < win_length; i++)
+		for (uint32_t j = 0; j < B; j++)
+			for (uint32_t sine = 0; sine < 2u; sine++) {
+				double v = g(i, j, sine != 0);
+				if (c != 0.0)
+					v = (i == 0 ? 1.0 - c : 1.0) * v - c * g(i + 1u, j, sine != 0);
+				if (scale != 1.0)
+					v = scale * v;
+				const float r = (float)v;
+				sp->basis[((size_t)sine * win_length + i) * B + j] = r;
+				dev[lw_spec_basis_at(p, i, sine, j)] = r;
+			}
 	bool ok = lw_hip_ok(hipMalloc((void **)&sp->d_basis, dev.size() * sizeof(float)), "hipMalloc(spec basis)") &&
 		lw_hip_ok(hipMemcpy(sp->d_basis, dev.data(), dev.size() * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(spec basis)");
 	if (ok && n_mels) {
@@ -128,12 +192,16 @@ uint32_t lw_spec_bins(const lw_spec *sp)
 
 uint32_t lw_spec_features(const lw_spec *sp)
 {
-	return sp ? (sp->n_mels ? sp->n_mels : sp->plan.bins) : 0;
+	return sp ? (sp->n_mels ? sp->n_mels : sp->plan.bins) + (sp->energy ? 1u : 0u) : 0;
 }
 
 uint64_t lw_spec_frames(const lw_spec *sp, uint64_t len)
 {
-	return sp ? lw_spec_n_frames(len, sp->n_fft, sp->hop, sp->center) : 0;
+	if (!sp)
+		return 0;
+	if (sp->framing != LW_SPEC_FRAMES_STFT)
+		return lw_spec_kaldi_frames(len, sp->win_length, sp->hop, sp->framing == LW_SPEC_FRAMES_KALDI_SNIP);
+	return lw_spec_n_frames(len, sp->n_fft, sp->hop, sp->center);
 }
 
 size_t lw_spec_basis(const lw_spec *sp, float *dst)
@@ -174,7 +242,8 @@ int lw_spec_set_pad_mode(lw_spec *sp, int mode)
 {
 	if (!sp)
 		return LW_ERR_NULL_ARG;
-	if ((mode != LW_SPEC_PAD_ZERO && mode != LW_SPEC_PAD_REFLECT) || (mode == LW_SPEC_PAD_REFLECT && !sp->center))
+	if ((mode != LW_SPEC_PAD_ZERO && mode != LW_SPEC_PAD_REFLECT) || (mode == LW_SPEC_PAD_REFLECT && !sp->center) ||
+			sp->framing != LW_SPEC_FRAMES_STFT) // (a Kaldi framing has its own)
 		return LW_ERR_UNSUPPORTED;
 	sp->pad_mode = mode;
 	return LW_OK;
@@ -189,7 +258,10 @@ int lw_spec_rows(lw_spec *sp, int fmt, uint32_t ch, const void *d_src, size_t n_
 		return LW_ERR_UNSUPPORTED;
 	if (ch == 0 || ch > 255 || n_src_rows > UINT32_MAX)
 		return LW_ERR_CAPACITY;
-	const uint64_t F = sp->n_mels ? sp->n_mels : sp->plan.bins;
+	const uint64_t F = lw_spec_features(sp); // (the energy line counts)
+	const bool kaldi = sp->framing != LW_SPEC_FRAMES_STFT;
+	const int64_t lead = kaldi ? lw_spec_kaldi_lead(sp->win_length, sp->hop, sp->framing == LW_SPEC_FRAMES_KALDI_SNIP)
+	                           : (int64_t)sp->plan.offset - (int64_t)(sp->center ? sp->n_fft / 2 : 0);
 	// both buffers must be addressable in 64 bits of BYTES
 	uint64_t e = 0;
 	if (__builtin_mul_overflow((uint64_t)ch, (uint64_t)src_capacity, &e) || __builtin_mul_overflow(e, (uint64_t)n_src_rows, &e) || e > UINT64_MAX / 4 ||
@@ -206,9 +278,16 @@ int lw_spec_rows(lw_spec *sp, int fmt, uint32_t ch, const void *d_src, size_t n_
 			return LW_ERR_CAPACITY;
 		if (sp->pad_mode == LW_SPEC_PAD_REFLECT && len[i] != 0 && len[i] < lw_spec_reflect_min_len(sp->n_fft))
 			return LW_ERR_CAPACITY; // one reflection does not reach every support sample
-		const uint64_t frames = lw_spec_n_frames(len[i], sp->n_fft, sp->hop, sp->center);
+		const uint64_t frames = lw_spec_frames(sp, len[i]);
 		if (frames > frame_capacity)
 			return LW_ERR_CAPACITY;
+		if (sp->pad_mode == LW_SPEC_PAD_SYMMETRIC && frames) {
+			// the first and the last index the row's frames touch (len <= the capacity of a buffer: no overflow); one reflection
+			// reaches [-len, 2 len - 1]
+			const int64_t first = lead, last = (int64_t)((frames - 1) * sp->hop) + lead + (int64_t)sp->win_length - 1, n = (int64_t)len[i];
+			if (first < -n || last > 2 * n - 1)
+				return LW_ERR_CAPACITY;
+		}
 		sp->rows.push_back(LwSpecRow{len[i], frames, row});
 		sp->taken.push_back(row);
 		most = std::max(most, frames);
@@ -251,7 +330,11 @@ int lw_spec_rows(lw_spec *sp, int fmt, uint32_t ch, const void *d_src, size_t n_
 	a.src = (const float *)d_src, a.dst = (float *)d_dst, a.basis = sp->d_basis, a.fb = sp->d_fb, a.rows = s.d;
 	a.s = itl ? LwSpecLayout{(uint64_t)src_capacity * ch, 1, ch} : LwSpecLayout{(uint64_t)src_capacity * ch, src_capacity, 1};
 	a.d_line = frame_capacity, a.d_ch = F * frame_capacity, a.d_row = a.d_ch * ch;
-	a.lead = (int64_t)p.offset - (int64_t)(sp->center ? sp->n_fft / 2 : 0);
+	a.lead = lead;
+	if (sp->remove_dc || sp->energy) {
+		a.remove_dc = sp->remove_dc, a.energy = sp->energy, a.escale = sp->scale * sp->scale;
+		a.span = lw_spec_span_fits(sp->hop, sp->win_length) ? (LW_SP_TF - 1u) * sp->hop + sp->win_length : 0u;
+	}
 	a.hop = sp->hop, a.win_length = sp->win_length, a.k_pad = p.k_pad, a.bins = p.bins, a.passes = p.passes, a.n_mels = sp->n_mels, a.mel_pad = p.mel_pad;
 	a.pad_mode = (uint32_t)sp->pad_mode;
 	for (size_t r0 = 0; r0 < n_src_rows; r0 += 65535) {

@@ -100,8 +100,37 @@ struct LwSpecArgs {
 	int64_t lead;                 // o - pad: sample 0 of frame t's SUPPORT is x[t * hop + lead]
 	uint32_t hop, win_length, k_pad, bins, passes, n_mels, mel_pad;
 	uint32_t row0; // first source row of this launch (blockIdx.z counts from it)
-	uint32_t pad_mode; // LW_SPEC_PAD_ZERO / LW_SPEC_PAD_REFLECT: what x[i] is outside [0, len)
+	uint32_t pad_mode; // LW_SPEC_PAD_ZERO / LW_SPEC_PAD_REFLECT / LW_SPEC_PAD_SYMMETRIC: what x[i] is outside [0, len)
+	// the per-frame prologue (k_spec<.., .., 1>); all zero: as before
+	uint32_t remove_dc; // x'_k = x_k - mu, mu the frame's mean
+	uint32_t energy;    // line 0 of the destination is the frame's energy, the spectrum or mel lines follow from line 1
+	uint32_t span;      // 31 * hop + win_length when the prologue stages the tile's samples through LDS (lw_spec_span_fits), else 0
+	double escale;      // scale * scale, what the energy is multiplied by
 };
+
+// The prologue's sums run over the samples of 32 frames, hop apart.  When the tile's span of 31 * hop + win_length samples fits
+// the P region of LDS (free until the first power), it is staged there once, coalesced, sample s at word s + (s >> 5): the skew
+// spreads the 32 chain lanes, which read hop words apart, over the banks where hop is a multiple of 32 (hop = 160: bank
+// 5 f + k + (k >> 5) mod 32, all different).  Otherwise the chain lanes read the row itself.
+#define LW_SP_SPAN_AT(s) ((s) + ((s) >> 5))
+static inline bool lw_spec_span_fits(uint32_t hop, uint32_t win_length)
+{
+	const uint64_t span = (uint64_t)(LW_SP_TF - 1u) * hop + win_length;
+	return span + (span >> 5) + 1u <= (uint64_t)LW_SP_COLS * LW_SP_TF;
+}
+
+// Kaldi framing (LW_SPEC_FRAMES_KALDI_SNIP, LW_SPEC_FRAMES_KALDI_EDGES): frames are counted by the window, which starts at sample 0
+// of the frame.  lead: the input index of support sample 0 of frame 0.
+static inline uint64_t lw_spec_kaldi_frames(uint64_t len, uint32_t win_length, uint32_t hop, bool snip)
+{
+	if (snip)
+		return len < win_length ? 0 : 1u + (len - win_length) / hop;
+	return (len + hop / 2u) / hop;
+}
+static inline int64_t lw_spec_kaldi_lead(uint32_t win_length, uint32_t hop, bool snip)
+{
+	return snip ? 0 : (int64_t)(hop / 2u) - (int64_t)(win_length / 2u);
+}
 
 // grid = (tiles of the row with the most frames, channels, rows of this launch <= 65535); a workgroup whose tile starts at or
 // behind its row's n_frames does nothing.  Nothing outside [0, n_frames) of a destination line is written.

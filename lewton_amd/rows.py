@@ -383,8 +383,9 @@ class Resampler:
         return out
 
 
-_SPEC_WINDOWS = {"hann": 0, "rect": 1}      # LW_SPEC_HANN, LW_SPEC_RECT
+_SPEC_WINDOWS = {"hann": 0, "rect": 1, "povey": 2, "hamming_sym": 3, "hann_sym": 4, "blackman_sym": 5}   # LW_SPEC_HANN ... LW_SPEC_BLACKMAN
 _SPEC_PAD_MODES = {"zero": 0, "reflect": 1}  # LW_SPEC_PAD_ZERO, LW_SPEC_PAD_REFLECT
+_SPEC_FRAMINGS = {("stft", True): 0, ("stft", False): 0, ("kaldi", True): 1, ("kaldi", False): 2}   # (framing, snip_edges): LW_SPEC_FRAMES_*
 SPEC_MAX_FFT, SPEC_MAX_MELS = 2048, 256     # LW_SPEC_MAX_FFT, LW_SPEC_MAX_MELS
 
 
@@ -431,6 +432,34 @@ def mel_filterbank(sample_rate, n_fft, n_mels, fmin=0.0, fmax=None, scale="htk",
     return w.astype(np.float32)
 
 
+def kaldi_mel_banks(sample_rate, n_fft, n_mels, low_freq=20.0, high_freq=0.0):
+    """[n_mels][n_fft // 2 + 1] float32: Kaldi's mel banks (kaldi-native-fbank, torchaudio.compliance.kaldi.get_mel_banks without
+    VTLN), triangles in the MEL domain, computed in float64 and rounded once.  mel(f) = 1127 ln(1 + f / 700); high_freq <= 0 is
+    an offset from sample_rate / 2; the n_mels + 2 points are equally spaced in mel from mel(low_freq) to mel(high_freq); bin
+    i < n_fft / 2 at m = mel(i * sample_rate / n_fft) gets a weight only when left < m < right: (m - left) / (centre - left) when
+    m <= centre, else (right - m) / (right - centre).  The Nyquist column is zero.  n_fft must be even.  Needs no GPU."""
+    if isinstance(n_mels, bool) or not isinstance(n_mels, (int, np.integer)) or not 1 <= n_mels <= SPEC_MAX_MELS:
+        raise ValueError("n_mels=%r: 1 .. %d" % (n_mels, SPEC_MAX_MELS))
+    if isinstance(n_fft, bool) or not isinstance(n_fft, (int, np.integer)) or not 2 <= n_fft <= SPEC_MAX_FFT or n_fft % 2:
+        raise ValueError("n_fft=%r: even, 2 .. %d" % (n_fft, SPEC_MAX_FFT))
+    sample_rate, low, high = float(sample_rate), float(low_freq), float(high_freq)
+    if not sample_rate > 0:
+        raise ValueError("sample_rate > 0 is required")
+    nyquist = 0.5 * sample_rate
+    if high <= 0.0:
+        high += nyquist
+    if not 0.0 <= low < high <= nyquist:
+        raise ValueError("0 <= low_freq < high_freq <= sample_rate / 2 is required, not %r, %r" % (low_freq, high_freq))
+    mel_low, mel_high = 1127.0 * np.log(1.0 + low / 700.0), 1127.0 * np.log(1.0 + high / 700.0)
+    delta = (mel_high - mel_low) / (int(n_mels) + 1)
+    q = np.arange(int(n_mels), dtype=np.float64)[:, None]
+    left, centre, right = mel_low + q * delta, mel_low + (q + 1.0) * delta, mel_low + (q + 2.0) * delta
+    m = 1127.0 * np.log(1.0 + np.arange(int(n_fft) // 2, dtype=np.float64) * (sample_rate / int(n_fft)) / 700.0)[None, :]
+    w = np.where(m <= centre, (m - left) / (centre - left), (right - m) / (right - centre))
+    w = np.where((m > left) & (m < right), w, 0.0)
+    return np.concatenate([w, np.zeros((int(n_mels), 1))], axis=1).astype(np.float32)
+
+
 def _spec_params(n_fft, hop, win_length, window, mel):
     """(win_length, the mel matrix as contiguous float32 or None), or ValueError for what lw_spec_create refuses"""
     for name, v, lo, hi in (("n_fft", n_fft, 2, SPEC_MAX_FFT), ("hop", hop, 1, 65535)):
@@ -441,7 +470,9 @@ def _spec_params(n_fft, hop, win_length, window, mel):
     if isinstance(win_length, bool) or not isinstance(win_length, (int, np.integer)) or not 1 <= win_length <= n_fft:
         raise ValueError("win_length=%r: an integer in 1 .. n_fft" % (win_length,))
     if window not in _SPEC_WINDOWS:
-        raise ValueError("window=%r: \"hann\" or \"rect\"" % (window,))
+        raise ValueError("window=%r: one of %s" % (window, ", ".join(sorted(_SPEC_WINDOWS))))
+    if window not in ("hann", "rect") and win_length < 2:
+        raise ValueError("window=%r needs win_length >= 2" % (window,))
     if mel is not None:
         mel = np.ascontiguousarray(mel, np.float32)
         if mel.ndim != 2 or mel.shape[1] != n_fft // 2 + 1 or not 1 <= mel.shape[0] <= SPEC_MAX_MELS:
@@ -451,29 +482,49 @@ def _spec_params(n_fft, hop, win_length, window, mel):
 
 class Spectrogram:
     """lw_spec: rows of f32 PCM -> power spectrum or mel features on the GPU (k_spec), by the windowed DFT of
-    include/lewton_amd.h ("spectral frames of rows"), a contract on bits.  window: "hann" (periodic) or "rect"; win_length: n_fft
-    when None; mel: None for the power spectrum [n_fft // 2 + 1 lines], or a matrix [n_mels][n_fft // 2 + 1] (mel_filterbank).
+    include/lewton_amd.h ("spectral frames of rows"), a contract on bits.  window: "hann" (periodic), "rect", or the symmetric
+    (i / (win_length - 1)) "povey", "hamming_sym", "hann_sym", "blackman_sym"; win_length: n_fft when None; mel: None for the power spectrum [n_fft // 2 + 1 lines], or a matrix [n_mels][n_fft // 2 + 1] (mel_filterbank).
     pad_mode: what a centred frame sees beyond the row, "zero" (+0.0) or "reflect" (x[-i], x[2 (len - 1) - i]: torch.stft's
     default; centred objects only, and run() then refuses a row of 0 < len < n_fft - n_fft // 2 + 1 samples).
-    Parameter errors are ValueError and need no GPU; the object itself lives on cuda:device."""
+    framing: "stft" (the rule above), or "kaldi": frames are counted by the window, which starts at sample 0 of the frame
+    (center must then be False and pad_mode "zero"); snip_edges=True drops the incomplete tail, False centres the frames and
+    reflects the row with the edge sample repeated (run() then refuses a row too short for one reflection).  preemphasis (0 .. 1)
+    and scale (> 0; Kaldi's sample range is 32768) are folded into the table; remove_dc subtracts every frame's mean from it;
+    energy puts the frame's energy (after remove_dc, before pre-emphasis and window, times scale^2) in line 0, the other lines
+    behind it.  Parameter errors are ValueError and need no GPU; the object itself lives on cuda:device."""
 
-    def __init__(self, n_fft=400, hop=160, win_length=None, window="hann", center=True, mel=None, device=0, pad_mode="zero"):
+    def __init__(self, n_fft=400, hop=160, win_length=None, window="hann", center=True, mel=None, device=0, pad_mode="zero",
+                 framing="stft", snip_edges=True, preemphasis=0.0, remove_dc=False, energy=False, scale=1.0):
         self.win_length, self._mel = _spec_params(n_fft, hop, win_length, window, mel)
         if pad_mode not in _SPEC_PAD_MODES or (pad_mode == "reflect" and not center):
             raise ValueError("pad_mode=%r: \"zero\", or \"reflect\" with center=True" % (pad_mode,))
-        self.pad_mode = pad_mode
+        if framing not in ("stft", "kaldi") or snip_edges not in (True, False, 0, 1):
+            raise ValueError("framing=%r: \"stft\" or \"kaldi\", with snip_edges True or False" % (framing,))
+        if framing == "kaldi" and (center or pad_mode != "zero"):
+            raise ValueError("framing=\"kaldi\" needs center=False and pad_mode=\"zero\": snip_edges decides what a frame sees")
+        if remove_dc not in (True, False, 0, 1) or energy not in (True, False, 0, 1):
+            raise ValueError("remove_dc and energy are True or False")
+        try:
+            preemphasis, scale = float(preemphasis), float(scale)
+        except (TypeError, ValueError):
+            raise ValueError("preemphasis and scale must be numbers")
+        if not 0.0 <= preemphasis <= 1.0 or not (scale > 0.0 and np.isfinite(scale)):
+            raise ValueError("preemphasis in 0 .. 1 and a positive finite scale are required")
+        self.pad_mode, self.framing, self.snip_edges = pad_mode, framing, bool(snip_edges)
+        self.preemphasis, self.scale, self.remove_dc, self.energy, self.window = preemphasis, scale, bool(remove_dc), bool(energy), window
         self.n_fft, self.hop, self.center, self.device = int(n_fft), int(hop), bool(center), device
         _gpu()
         err = C.c_int(0)
         n_mels = 0 if self._mel is None else self._mel.shape[0]
-        self._h = N.lw_spec_create(device, self.n_fft, self.win_length, self.hop, _SPEC_WINDOWS[window], int(self.center), n_mels,
-                                   None if self._mel is None else self._mel.ctypes.data_as(C.c_void_p), C.byref(err))
+        p = N.SpecParams(self.n_fft, self.win_length, self.hop, n_mels, None if self._mel is None else self._mel.ctypes.data, _SPEC_WINDOWS[window],
+                         int(self.center), _SPEC_FRAMINGS[framing, bool(snip_edges)], int(self.remove_dc), int(self.energy), 0, preemphasis, scale)
+        self._h = N.lw_spec_create_ex(device, C.byref(p), C.byref(err))
         if not self._h:
             if err.value in (N.ERR_UNSUPPORTED, N.ERR_NULL_ARG):
-                raise ValueError("lw_spec_create refused the parameters")
-            raise RuntimeError("lw_spec_create failed (%d): %s" % (err.value, N.device_error()))
-        assert self.bins == self.n_fft // 2 + 1 and self.features == (n_mels or self.bins)
-        if N.lw_spec_set_pad_mode(self._h, _SPEC_PAD_MODES[pad_mode]):
+                raise ValueError("lw_spec_create_ex refused the parameters")
+            raise RuntimeError("lw_spec_create_ex failed (%d): %s" % (err.value, N.device_error()))
+        assert self.bins == self.n_fft // 2 + 1 and self.features == (n_mels or self.bins) + int(self.energy)
+        if framing == "stft" and N.lw_spec_set_pad_mode(self._h, _SPEC_PAD_MODES[pad_mode]):
             self.close()
             raise ValueError("lw_spec_set_pad_mode refused pad_mode=%r" % (pad_mode,))
 
@@ -492,7 +543,7 @@ class Spectrogram:
 
     @property
     def features(self):
-        """lines per row and channel of the output: n_mels, or bins without a mel matrix"""
+        """lines per row and channel of the output: n_mels, or bins without a mel matrix, and one more with energy"""
         return int(N.lw_spec_features(self._h))
 
     @property
@@ -987,6 +1038,100 @@ class Cepstrum:
         if rc:
             raise RuntimeError("lw_cep_rows: %d %s" % (rc, N.device_error()))
         return out
+
+
+FLT_EPSILON = float(np.finfo(np.float32).eps)      # Kaldi's floor under the logarithm
+
+
+class KaldiFbank:
+    """Kaldi's filterbank front end on the GPU: what torchaudio.compliance.kaldi.fbank and kaldi-native-fbank compute, as the chain
+    Spectrogram(framing="kaldi", ...) -> LogCompress("ln", floor=FLT_EPSILON, top=inf, add=0, mul=1) in place -> (use_energy and
+    energy_floor > 0) line 0 clamped at ln(energy_floor) by torch -> (subtract_mean) Normalize.cmvn(variance=False).  Argument
+    names and defaults are torchaudio's; a value this front end does not offer is a ValueError: dither != 0, htk_compat,
+    raw_energy=False, use_power=False, use_log_fbank=False, vtln_warp != 1, blackman_coeff != 0.42, channel != -1 (every channel of
+    a row is processed), min_duration != 0.  scale (not torchaudio's): what the samples are multiplied by, 32768 where a model was
+    trained on Kaldi's 16-bit sample range.  frame_length and frame_shift are milliseconds.
+
+    The output is the chain's [row][ch][F][frame], F = num_mel_bins (+ 1 with use_energy, the energy in line 0), NOT torchaudio's
+    [frame][F]: out[r, c].T is what torchaudio returns for channel c of row r."""
+
+    def __init__(self, blackman_coeff=0.42, channel=-1, dither=0.0, energy_floor=1.0, frame_length=25.0, frame_shift=10.0, high_freq=0.0,
+                 htk_compat=False, low_freq=20.0, min_duration=0.0, num_mel_bins=23, preemphasis_coefficient=0.97, raw_energy=True,
+                 remove_dc_offset=True, round_to_power_of_two=True, sample_frequency=16000.0, snip_edges=True, subtract_mean=False,
+                 use_energy=False, use_log_fbank=True, use_power=True, vtln_high=-500.0, vtln_low=100.0, vtln_warp=1.0, window_type="povey",
+                 scale=1.0, device=0):
+        for name, v, only in (("dither", dither, 0.0), ("htk_compat", htk_compat, False), ("raw_energy", raw_energy, True), ("use_power", use_power, True),
+                              ("use_log_fbank", use_log_fbank, True), ("vtln_warp", vtln_warp, 1.0), ("blackman_coeff", blackman_coeff, 0.42),
+                              ("channel", channel, -1), ("min_duration", min_duration, 0.0)):
+            if v != only:
+                raise ValueError("%s=%r is not offered (only %r)" % (name, v, only))
+        windows = {"povey": "povey", "hamming": "hamming_sym", "hanning": "hann_sym", "rectangular": "rect", "blackman": "blackman_sym"}
+        if window_type not in windows:
+            raise ValueError("window_type=%r: one of %s" % (window_type, ", ".join(sorted(windows))))
+        try:
+            sample_frequency, energy_floor = float(sample_frequency), float(energy_floor)
+            win = int(sample_frequency * float(frame_length) * 0.001)
+            hop = int(sample_frequency * float(frame_shift) * 0.001)
+        except (TypeError, ValueError, OverflowError):
+            raise ValueError("sample_frequency, frame_length, frame_shift and energy_floor must be finite numbers")
+        if win < 2 or hop < 1:
+            raise ValueError("frame_length and frame_shift give a window of %d and a shift of %d samples" % (win, hop))
+        n_fft = 1 << (win - 1).bit_length() if round_to_power_of_two else win
+        if not energy_floor >= 0.0:
+            raise ValueError("energy_floor=%r: non-negative" % (energy_floor,))
+        self.use_energy, self.subtract_mean, self.energy_floor, self.device = bool(use_energy), bool(subtract_mean), energy_floor, device
+        self.banks = kaldi_mel_banks(sample_frequency, n_fft, num_mel_bins, low_freq, high_freq)
+        self.spec = Spectrogram(n_fft, hop, win, windows[window_type], center=False, mel=self.banks, device=device, framing="kaldi",
+                                snip_edges=snip_edges, preemphasis=preemphasis_coefficient, remove_dc=bool(remove_dc_offset),
+                                energy=self.use_energy, scale=scale)
+        self.log = self.norm = None
+        try:
+            self.log = LogCompress("ln", floor=FLT_EPSILON, top=float("inf"), add=0.0, mul=1.0, device=device)
+            if self.subtract_mean:
+                self.norm = Normalize.cmvn(variance=False, device=device)
+        except Exception:
+            self.close()
+            raise
+
+    def close(self):
+        for part in (getattr(self, "spec", None), getattr(self, "log", None), getattr(self, "norm", None)):
+            if part is not None:
+                part.close()
+
+    @property
+    def features(self):
+        return self.spec.features
+
+    def frames(self, n):
+        return self.spec.frames(n)
+
+    def run(self, pcm, lengths, out=None, fill_to=None, samples="f32", stream=None):
+        """row i of pcm ([B, C, T] float32, or [B, T, C] for samples="f32_interleaved"), lengths[i] samples per channel -> row i
+        of out, float32 [B][C][F][frame capacity] (None: a zeroed tensor that holds the largest frame count and fill_to).
+        fill_to: None, one count for all rows or one per row: positions [frames[i], fill_to[i]) of every line receive
+        ln(FLT_EPSILON), Kaldi's lowest value, or 0 with subtract_mean.  Asynchronous; returns (out, frames)."""
+        torch = _gpu()
+        if out is None:
+            n_src, ch, _ = self.spec.check_tensor(pcm, samples, "pcm")
+            lens = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+            if len(lens) != n_src or any(v < 0 for v in lens):
+                raise ValueError("lengths= needs one non-negative entry per row of pcm")
+            fill = fill_to.tolist() if hasattr(fill_to, "tolist") else fill_to
+            fill = [] if fill is None else [int(fill)] if isinstance(fill, (int, np.integer)) else [int(v) for v in fill]
+            cap = max([self.spec.frames(v) for v in lens] + fill, default=0)
+            out = torch.zeros((n_src, ch, self.features, cap), dtype=torch.float32, device="cuda:%d" % self.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream or None
+        out, frames = self.spec.run(pcm, lengths, out=out, samples=samples, stream=stream)
+        self.log.run(out, frames, fill_to=fill_to, stream=stream)
+        if self.use_energy and self.energy_floor > 0.0 and out.shape[3]:
+            with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=self.device) if stream else torch.cuda.default_stream(self.device)):
+                line = out[:, :, 0, :]
+                written = torch.arange(out.shape[3], device=out.device)[None, None, :] < frames.to(out.device)[:, None, None]
+                line.copy_(torch.where(written, torch.clamp(line, min=float(np.log(self.energy_floor))), line))
+        if self.norm is not None:
+            self.norm.run(out, frames, fill_to=fill_to, stream=stream)
+        return out, frames
 
 
 def _normalizer(normalize, samples, device):
