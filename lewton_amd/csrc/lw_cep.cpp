@@ -1,22 +1,10 @@
 // Cepstra and deltas of feature rows (lw_cep_*, lw_cep_rows; include/lewton_amd.h "cepstra and deltas of feature rows"): a matrix
 // across the feature lines of f32 [row][ch][n_in][capacity] rows (MFCC: a DCT of log-mel lines) and regression deltas along the
 // frames, a contract on bits.  Everything about a call is decided here on the host before anything is queued (the refusals, the
-// tile plan); k_cep (lw_kernels_cep.hip) does the work in one launch per 65535 rows.  The call's per-row records travel through
-// pinned arrays in rotation, each guarded by an event, as lw_norm_rows' do.  Nothing else in the library calls into this file.
-#include "lw_internal.hpp"
+// tile plan); k_cep (lw_kernels_cep.hip) does the work in one launch per 65535 rows.  The call's per-row records are staged as
+// lw_stage.hpp describes.  Nothing else in the library calls into this file.
+#include "lw_stage.hpp"
 #include "lw_cep.hpp"
-
-#include <algorithm>
-#include <cstring>
-
-#define LW_CP_SLOTS 3 // record arrays in rotation: calls queued back to back do not wait for each other's kernels
-
-struct lw_cp_slot {
-	LwCepRow *h = nullptr, *d = nullptr; // pinned / device, cap records each
-	size_t cap = 0;
-	hipEvent_t done = nullptr; // recorded behind the last launch that read d
-	bool pending = false;
-};
 
 struct lw_cep {
 	int device = 0;
@@ -27,8 +15,7 @@ struct lw_cep {
 	std::vector<float> matrix; // [n_out][n_in], the caller's (empty for the identity)
 	float *d_mt = nullptr;     // [n_in][mt_stride], transposed and padded with +0.0
 	float w[LW_CP_MAX_WIDTH] = {};
-	lw_cp_slot slot[LW_CP_SLOTS];
-	unsigned next = 0;
+	LwStageRing<LwCepRow> ring;
 	int last_launches = -1;
 	std::vector<LwCepRow> rows;
 };
@@ -50,8 +37,8 @@ lw_cep *lw_cep_create(int device, uint32_t n_in, uint32_t n_out, const float *ma
 		return nullptr;
 	}
 	const LwCepPlan plan = lw_cep_plan(n_out, order, width);
-	int ndev = 0, lds_limit = 0;
-	if (!lw_hip_ok(hipGetDeviceCount(&ndev), "hipGetDeviceCount") || device < 0 || device >= ndev || !lw_hip_ok(hipSetDevice(device), "hipSetDevice") ||
+	int lds_limit = 0;
+	if (lw_stage_device(device) ||
 			!lw_hip_ok(hipDeviceGetAttribute(&lds_limit, hipDeviceAttributeMaxSharedMemoryPerBlock, device), "hipDeviceGetAttribute(LDS per workgroup)") ||
 			(size_t)lds_limit < plan.lds) { // k_cep's workgroup does not fit this device
 		*err = LW_ERR_DEVICE;
@@ -61,9 +48,7 @@ lw_cep *lw_cep_create(int device, uint32_t n_in, uint32_t n_out, const float *ma
 	cp->device = device, cp->n_in = n_in, cp->n_out = n_out, cp->order = order, cp->width = width, cp->identity = !matrix, cp->plan = plan;
 	cp->mt_stride = (n_out + LW_CP_GROUP - 1u) & ~(LW_CP_GROUP - 1u);
 	lw_cep_weights(width, cp->w);
-	bool ok = true;
-	for (auto &sl : cp->slot)
-		ok = ok && lw_hip_ok(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming), "hipEventCreate(cep rows)");
+	bool ok = cp->ring.create("hipEventCreate(cep rows)");
 	if (ok && matrix) {
 		cp->matrix.assign(matrix, matrix + (size_t)n_out * n_in);
 		std::vector<float> mt((size_t)n_in * cp->mt_stride, 0.0f);
@@ -87,14 +72,7 @@ void lw_cep_destroy(lw_cep *cp)
 		return;
 	(void)hipSetDevice(cp->device);
 	(void)hipDeviceSynchronize();
-	for (auto &s : cp->slot) {
-		if (s.h)
-			(void)hipHostFree(s.h);
-		if (s.d)
-			(void)hipFree(s.d);
-		if (s.done)
-			(void)hipEventDestroy(s.done);
-	}
+	cp->ring.destroy();
 	if (cp->d_mt)
 		(void)hipFree(cp->d_mt);
 	delete cp;
@@ -141,66 +119,45 @@ int lw_cep_rows(lw_cep *cp, uint32_t ch, const void *d_src, void *d_dst, size_t 
 	if (ch == 0 || ch > 255 || n_rows > UINT32_MAX)
 		return LW_ERR_CAPACITY;
 	const uint64_t lines = (uint64_t)ch * std::max(cp->n_in, cp->n_out * (1u + cp->order)); // the larger of the two buffers
-	uint64_t e = 0; // each must be addressable in 64 bits of BYTES
-	if (__builtin_mul_overflow(lines, (uint64_t)frame_capacity, &e) || __builtin_mul_overflow(e, (uint64_t)n_rows, &e) || e > UINT64_MAX / 4)
+	if (!lw_rows_bytes_ok(lines, frame_capacity, n_rows)) // each must be addressable in 64 bits of BYTES
 		return LW_ERR_CAPACITY;
 	// ---- plan: every row is checked before anything is queued, so a refused call has written nothing
 	cp->rows.clear();
-	uint64_t most = 0, span = 0;
-	for (size_t i = 0; i < n_rows; i++) {
-		const uint64_t fill = fill_to ? fill_to[i] : 0;
-		if (n_frames[i] > frame_capacity || fill > frame_capacity)
-			return LW_ERR_CAPACITY;
-		cp->rows.push_back(LwCepRow{n_frames[i], std::max(n_frames[i], fill)});
-		most = std::max(most, n_frames[i]);
-		span = std::max(span, cp->rows.back().fill_end);
-	}
-	if ((most && !d_src) || (span && !d_dst))
-		return LW_ERR_NULL_ARG;
-	const uint64_t tiles = (span + cp->plan.tile - 1u) / cp->plan.tile;
+	LwFillSpan m;
+	if (int rc = lw_stage_fill_rows(n_rows, n_frames, fill_to, frame_capacity, d_src, d_dst, m, [&](uint64_t n, uint64_t fill_end) {
+		    cp->rows.push_back(LwCepRow{n, fill_end});
+		    return LW_OK;
+	    }))
+		return rc;
+	const uint64_t tiles = (m.span + cp->plan.tile - 1u) / cp->plan.tile;
 	if (tiles > LW_CP_MAX_TILES) // what a grid of 256-lane workgroups can count in its first dimension
 		return LW_ERR_CAPACITY;
-	if (n_rows == 0 || span == 0) {
+	if (n_rows == 0 || m.span == 0) {
 		cp->last_launches = 0;
 		return LW_OK;
 	}
-	// ---- queue: the records, then the launches, 65535 rows each
+	// ---- queue: the records, then the launches
 	HIP_TRY(hipSetDevice(cp->device));
 	hipStream_t st = (hipStream_t)hip_stream;
-	lw_cp_slot &s = cp->slot[cp->next];
-	if (s.pending) { // an earlier call's copy of these records may still be in use
-		HIP_TRY(hipEventSynchronize(s.done));
-		s.pending = false;
-	}
-	if (s.cap < n_rows) {
-		if (s.h)
-			(void)hipHostFree(s.h);
-		if (s.d)
-			(void)hipFree(s.d);
-		s.h = s.d = nullptr;
-		s.cap = 0;
-		const size_t cap = std::max<size_t>(n_rows, 64);
-		HIP_TRY(hipHostMalloc((void **)&s.h, cap * sizeof(LwCepRow), 0));
-		HIP_TRY(hipMalloc((void **)&s.d, cap * sizeof(LwCepRow)));
-		s.cap = cap;
-	}
-	std::memcpy(s.h, cp->rows.data(), n_rows * sizeof(LwCepRow));
-	HIP_TRY(hipMemcpyAsync(s.d, s.h, n_rows * sizeof(LwCepRow), hipMemcpyHostToDevice, st));
+	if (int rc = cp->ring.acquire(n_rows))
+		return rc;
+	LwStageGuard staged = cp->ring.guard(st);
+	if (int rc = cp->ring.upload(cp->rows, st))
+		return rc;
 	LwCepArgs a{};
-	a.rows = s.d, a.line_el = frame_capacity;
+	a.rows = cp->ring.dev(), a.line_el = frame_capacity;
 	a.ch = ch, a.n_in = cp->n_in, a.n_out = cp->n_out, a.order = cp->order, a.width = cp->width;
 	a.identity = cp->identity, a.mt_stride = cp->mt_stride, a.plan = cp->plan;
 	std::memcpy(a.w, cp->w, sizeof(a.w));
-	int launches = 0;
-	for (size_t r0 = 0; r0 < n_rows; r0 += 65535) {
-		a.row0 = (uint32_t)r0;
-		HIP_TRY(lw_launch_cep(a, cp->d_mt, (const float *)d_src, (float *)d_dst, (uint32_t)tiles, (uint32_t)std::min<size_t>(n_rows - r0, 65535), st));
-		launches++;
-	}
-	HIP_TRY(hipEventRecord(s.done, st));
-	s.pending = true;
+	const int launches = lw_stage_launch(n_rows, "lw_launch_cep", [&](uint32_t row0, uint32_t n) {
+		a.row0 = row0;
+		return lw_launch_cep(a, cp->d_mt, (const float *)d_src, (float *)d_dst, (uint32_t)tiles, n, st);
+	});
+	if (launches < 0)
+		return LW_ERR_DEVICE;
+	if (int rc = staged.commit())
+		return rc;
 	cp->last_launches = launches;
-	cp->next = (cp->next + 1) % LW_CP_SLOTS;
 	return LW_OK;
 }
 

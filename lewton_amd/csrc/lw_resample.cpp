@@ -2,32 +2,20 @@
 // ([row][ch][sample] or [row][sample][ch] in device memory) resampled by a rational ratio into another rows buffer, by a windowed-
 // sinc polyphase filter whose taps and fold order are a contract on bits.  The taps are evaluated here in double and rounded once;
 // everything about a call is decided here on the host before anything is queued (the refusals, the output lengths, the launch
-// geometry); k_resample (lw_kernels_resample.hip) does the fold.  The call's per-row records travel through pinned arrays in
-// rotation, each guarded by an event, as lw_rows' descriptors do.  Nothing else in the library calls into this file.
-#include "lw_internal.hpp"
+// geometry); k_resample (lw_kernels_resample.hip) does the fold.  The call's per-row records are staged as lw_stage.hpp
+// describes.  Nothing else in the library calls into this file.
+#include "lw_stage.hpp"
 #include "lw_resample.hpp"
 
-#include <algorithm>
 #include <cmath>
-#include <cstring>
 #include <numeric>
-
-#define LW_RS_SLOTS 3 // record arrays in rotation: calls queued back to back do not wait for each other's kernels
-
-struct lw_rs_slot {
-	LwResampleRow *h = nullptr, *d = nullptr; // pinned / device, cap records each
-	size_t cap = 0;
-	hipEvent_t done = nullptr; // recorded behind the last launch that read d
-	bool pending = false;
-};
 
 struct lw_resampler {
 	int device = 0;
 	uint32_t orig = 0, new_ = 0, half_width = 0, k_taps = 0;
 	std::vector<float> taps; // [new][K], the public order
 	float *d_taps = nullptr; // [K][new] by n mod new, the kernel's order (lw_resample.hpp)
-	lw_rs_slot slot[LW_RS_SLOTS];
-	unsigned next = 0;
+	LwStageRing<LwResampleRow> ring;
 	bool taps_in_lds = true;
 	int last_route = -1;
 	std::vector<LwResampleRow> plan;
@@ -94,8 +82,7 @@ lw_resampler *lw_resampler_create(int device, uint32_t in_rate, uint32_t out_rat
 		*err = LW_ERR_UNSUPPORTED;
 		return nullptr;
 	}
-	int ndev = 0;
-	if (!lw_hip_ok(hipGetDeviceCount(&ndev), "hipGetDeviceCount") || device < 0 || device >= ndev || !lw_hip_ok(hipSetDevice(device), "hipSetDevice")) {
+	if (lw_stage_device(device)) {
 		*err = LW_ERR_DEVICE;
 		return nullptr;
 	}
@@ -120,9 +107,7 @@ lw_resampler *lw_resampler_create(int device, uint32_t in_rate, uint32_t out_rat
 	}
 	bool ok = lw_hip_ok(hipMalloc((void **)&rs->d_taps, dev.size() * sizeof(float)), "hipMalloc(resampler taps)") &&
 		lw_hip_ok(hipMemcpy(rs->d_taps, dev.data(), dev.size() * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(resampler taps)");
-	for (auto &sl : rs->slot)
-		ok = ok && lw_hip_ok(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming), "hipEventCreate(resampler rows)");
-	if (!ok) {
+	if (!ok || !rs->ring.create("hipEventCreate(resampler rows)")) {
 		*err = LW_ERR_DEVICE;
 		lw_resampler_destroy(rs.release());
 		return nullptr;
@@ -136,14 +121,7 @@ void lw_resampler_destroy(lw_resampler *rs)
 		return;
 	(void)hipSetDevice(rs->device);
 	(void)hipDeviceSynchronize();
-	for (auto &s : rs->slot) {
-		if (s.h)
-			(void)hipHostFree(s.h);
-		if (s.d)
-			(void)hipFree(s.d);
-		if (s.done)
-			(void)hipEventDestroy(s.done);
-	}
+	rs->ring.destroy();
 	if (rs->d_taps)
 		(void)hipFree(rs->d_taps);
 	delete rs;
@@ -198,30 +176,22 @@ int lw_resample_rows(lw_resampler *rs, int fmt, uint32_t ch, const void *d_src, 
 	if (ch == 0 || ch > 255 || n_src_rows > UINT32_MAX)
 		return LW_ERR_CAPACITY;
 	// both buffers must be addressable in 64 bits of BYTES
-	uint64_t e = 0;
-	if (__builtin_mul_overflow((uint64_t)ch, (uint64_t)src_capacity, &e) || __builtin_mul_overflow(e, (uint64_t)n_src_rows, &e) || e > UINT64_MAX / 4 ||
-			__builtin_mul_overflow((uint64_t)ch, (uint64_t)dst_capacity, &e) || __builtin_mul_overflow(e, (uint64_t)n_dst_rows, &e) || e > UINT64_MAX / 4)
+	if (!lw_rows_bytes_ok(ch, src_capacity, n_src_rows) || !lw_rows_bytes_ok(ch, dst_capacity, n_dst_rows))
 		return LW_ERR_CAPACITY;
 	// ---- plan: every row is checked before anything is queued, so a refused call has written nothing
 	rs->plan.clear();
-	rs->taken.clear();
 	uint64_t longest = 0;
 	bool any_in = false;
-	for (size_t i = 0; i < n_src_rows; i++) {
-		const uint64_t row = dst_row ? dst_row[i] : i;
-		if (len[i] > src_capacity || row >= n_dst_rows)
-			return LW_ERR_CAPACITY;
-		const uint64_t out = out_len_of(rs, len[i]);
-		if (out > dst_capacity)
-			return LW_ERR_CAPACITY;
-		rs->plan.push_back(LwResampleRow{len[i], out, row});
-		rs->taken.push_back(row);
-		longest = std::max(longest, out);
-		any_in = any_in || len[i] != 0;
-	}
-	std::sort(rs->taken.begin(), rs->taken.end());
-	if (std::adjacent_find(rs->taken.begin(), rs->taken.end()) != rs->taken.end())
-		return LW_ERR_CAPACITY; // two source rows for one destination row
+	if (int rc = lw_stage_mapped_rows(rs->taken, n_src_rows, len, dst_row, src_capacity, n_dst_rows, [&](uint64_t len_i, uint64_t row) {
+		    const uint64_t out = out_len_of(rs, len_i);
+		    if (out > dst_capacity)
+			    return LW_ERR_CAPACITY;
+		    rs->plan.push_back(LwResampleRow{len_i, out, row});
+		    longest = std::max(longest, out);
+		    any_in = any_in || len_i != 0;
+		    return LW_OK;
+	    }))
+		return rc;
 	if ((any_in && !d_src) || (longest && !d_dst))
 		return LW_ERR_NULL_ARG;
 	const LwResamplePlan p = lw_resample_plan(rs->orig, rs->new_, rs->k_taps, rs->taps_in_lds);
@@ -230,42 +200,28 @@ int lw_resample_rows(lw_resampler *rs, int fmt, uint32_t ch, const void *d_src, 
 		return LW_ERR_CAPACITY;
 	if (longest == 0)
 		return LW_OK;
-	// ---- queue: the records, then one launch per 65535 rows
+	// ---- queue: the records, then the launches
 	HIP_TRY(hipSetDevice(rs->device));
 	hipStream_t st = (hipStream_t)hip_stream;
-	lw_rs_slot &s = rs->slot[rs->next];
-	if (s.pending) { // an earlier call's copy of these records may still be on its way
-		HIP_TRY(hipEventSynchronize(s.done));
-		s.pending = false;
-	}
-	if (s.cap < n_src_rows) {
-		if (s.h)
-			(void)hipHostFree(s.h);
-		if (s.d)
-			(void)hipFree(s.d);
-		s.h = s.d = nullptr;
-		s.cap = 0;
-		const size_t cap = std::max<size_t>(n_src_rows, 64);
-		HIP_TRY(hipHostMalloc((void **)&s.h, cap * sizeof(LwResampleRow), 0));
-		HIP_TRY(hipMalloc((void **)&s.d, cap * sizeof(LwResampleRow)));
-		s.cap = cap;
-	}
-	std::memcpy(s.h, rs->plan.data(), n_src_rows * sizeof(LwResampleRow));
-	HIP_TRY(hipMemcpyAsync(s.d, s.h, n_src_rows * sizeof(LwResampleRow), hipMemcpyHostToDevice, st));
+	if (int rc = rs->ring.acquire(n_src_rows))
+		return rc;
+	LwStageGuard staged = rs->ring.guard(st);
+	if (int rc = rs->ring.upload(rs->plan, st))
+		return rc;
 	const bool itl = fmt == LW_FMT_F32_INTERLEAVED;
 	LwResampleArgs a{};
-	a.src = (const float *)d_src, a.dst = (float *)d_dst, a.taps = rs->d_taps, a.rows = s.d;
+	a.src = (const float *)d_src, a.dst = (float *)d_dst, a.taps = rs->d_taps, a.rows = rs->ring.dev();
 	a.s = itl ? LwResampleLayout{(uint64_t)src_capacity * ch, 1, ch} : LwResampleLayout{(uint64_t)src_capacity * ch, src_capacity, 1};
 	a.d = itl ? LwResampleLayout{(uint64_t)dst_capacity * ch, 1, ch} : LwResampleLayout{(uint64_t)dst_capacity * ch, dst_capacity, 1};
 	a.orig = rs->orig, a.new_ = rs->new_, a.half_width = rs->half_width, a.k_taps = rs->k_taps, a.blocks = p.blocks;
-	for (size_t r0 = 0; r0 < n_src_rows; r0 += 65535) {
-		a.row0 = (uint32_t)r0;
-		HIP_TRY(lw_launch_resample(a, p, (uint32_t)tiles, ch, (uint32_t)std::min<size_t>(n_src_rows - r0, 65535), st));
-	}
-	HIP_TRY(hipEventRecord(s.done, st));
-	s.pending = true;
+	if (lw_stage_launch(n_src_rows, "lw_launch_resample", [&](uint32_t row0, uint32_t n) {
+		    a.row0 = row0;
+		    return lw_launch_resample(a, p, (uint32_t)tiles, ch, n, st);
+	    }) < 0)
+		return LW_ERR_DEVICE;
+	if (int rc = staged.commit())
+		return rc;
 	rs->last_route = p.route;
-	rs->next = (rs->next + 1) % LW_RS_SLOTS;
 	return LW_OK;
 }
 

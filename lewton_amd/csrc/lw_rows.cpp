@@ -97,9 +97,7 @@ int lw_rows_synth(lw_rows *r, lw_batch *b, const lw_row_place *place, size_t n, 
 	const size_t ch = r->dec->T.ch, es = lw_elem_size(r->fmt);
 	const bool itl = lw_fmt_interleaved(r->fmt);
 	const size_t out_elems = lw_batch_out_elems(b);
-	uint64_t row_elems = 0, all_elems = 0; // the rows buffer must be addressable in 64 bits of BYTES
-	if (__builtin_mul_overflow((uint64_t)ch, (uint64_t)row_capacity, &row_elems) || __builtin_mul_overflow(row_elems, (uint64_t)n_rows, &all_elems) ||
-			all_elems > UINT64_MAX / es || out_elems > UINT32_MAX)
+	if (!lw_rows_bytes_ok(ch, row_capacity, n_rows, es) || out_elems > UINT32_MAX)
 		return LW_ERR_CAPACITY;
 	// ---- plan: every packet is checked and cut before anything is queued, so a refused call has written nothing
 	const lw_packet_result *res = lw_batch_results(b);
@@ -167,14 +165,12 @@ int lw_rows_synth(lw_rows *r, lw_batch *b, const lw_row_place *place, size_t n, 
 		s.pending = false;
 	}
 	std::memcpy(s.h_seg, r->plan.data(), r->plan.size() * sizeof(LwRowSeg));
-	HIP_TRY(hipMemcpyAsync(s.d_seg, s.h_seg, r->plan.size() * sizeof(LwRowSeg), hipMemcpyHostToDevice, st));
-	HIP_TRY(lw_launch_rows(r->d_stage, d_rows, s.d_seg, (uint32_t)r->plan.size(), (int)es, st));
-	HIP_TRY(hipEventRecord(s.done, st));
-	s.pending = true;
+	LwStageGuard staged(s.done, s.pending, r->next, st); // (lw_stage.hpp: a failed launch leaves the slot marked as well)
 	r->last_done = s.done;
 	r->last_stream = hip_stream;
-	r->next = (r->next + 1) % LW_ROWS_SLOTS;
-	return LW_OK;
+	HIP_TRY(hipMemcpyAsync(s.d_seg, s.h_seg, r->plan.size() * sizeof(LwRowSeg), hipMemcpyHostToDevice, st));
+	HIP_TRY(lw_launch_rows(r->d_stage, d_rows, s.d_seg, (uint32_t)r->plan.size(), (int)es, st));
+	return staged.commit();
 }
 
 size_t lw_rows_last_segments(const lw_rows *r)

@@ -1,9 +1,9 @@
 // struct lw_rows, shared by the two translation units that work on it: lw_rows.cpp (create, destroy, lw_rows_synth) and
 // lw_rows_mix.cpp (lw_rows_synth_mix).  lw_rows.cpp references nothing that lw_rows_mix.cpp defines.
 #pragma once
-#include "lw_internal.hpp"
+#include "lw_stage.hpp"
 
-#define LW_ROWS_SLOTS 3 // descriptor arrays in rotation: calls queued back to back do not wait for each other's kernels
+#define LW_ROWS_SLOTS LW_STAGE_SLOTS // descriptor arrays in rotation (lw_stage.hpp), sized once: at create, and at the first mix use
 
 struct lw_rows_slot {
 	LwRowSeg *h_seg = nullptr, *d_seg = nullptr; // pinned / device, seg_cap descriptors each

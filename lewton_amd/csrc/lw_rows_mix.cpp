@@ -46,9 +46,7 @@ extern "C" int lw_rows_synth_mix(lw_rows *r, lw_batch *b, const lw_row_place *pl
 		return LW_ERR_UNSUPPORTED; // the i16 formats route only: nobody wants quantised samples mixed
 	const bool itl = lw_fmt_interleaved(r->fmt);
 	const size_t out_elems = lw_batch_out_elems(b);
-	uint64_t row_elems = 0, all_elems = 0; // the rows buffer must be addressable in 64 bits of BYTES
-	if (__builtin_mul_overflow((uint64_t)out_ch, (uint64_t)row_capacity, &row_elems) || __builtin_mul_overflow(row_elems, (uint64_t)n_rows, &all_elems) ||
-			all_elems > UINT64_MAX / es || out_elems > UINT32_MAX)
+	if (!lw_rows_bytes_ok(out_ch, row_capacity, n_rows, es) || out_elems > UINT32_MAX)
 		return LW_ERR_CAPACITY;
 	// ---- plan: every packet is checked and cut before anything is queued, so a refused call has written nothing
 	const lw_packet_result *res = lw_batch_results(b);
@@ -124,13 +122,11 @@ extern "C" int lw_rows_synth_mix(lw_rows *r, lw_batch *b, const lw_row_place *pl
 	const size_t piece_bytes = n_pieces * sizeof(LwRowMixPiece);
 	std::memcpy(s.h, r->mix_plan.data(), piece_bytes);
 	std::memcpy((uint8_t *)s.h + piece_bytes, mix->coef, coef_bytes);
+	LwStageGuard staged(s.done, s.pending, r->mix_next, st); // (lw_stage.hpp: a failed launch leaves the slot marked as well)
+	r->last_done = s.done;
+	r->last_stream = hip_stream;
 	HIP_TRY(hipMemcpyAsync(s.d, s.h, piece_bytes + coef_bytes, hipMemcpyHostToDevice, st));
 	HIP_TRY(lw_launch_rows_mix(r->d_stage, d_rows, (const LwRowMixPiece *)s.d, (uint32_t)n_pieces, (const float *)((const uint8_t *)s.d + piece_bytes),
 			(uint32_t)ch, (uint32_t)out_ch, (uint64_t)row_capacity, (int)es, itl, st));
-	HIP_TRY(hipEventRecord(s.done, st));
-	s.pending = true;
-	r->last_done = s.done;
-	r->last_stream = hip_stream;
-	r->mix_next = (r->mix_next + 1) % LW_ROWS_SLOTS;
-	return LW_OK;
+	return staged.commit();
 }

@@ -2,23 +2,12 @@
 // ([row][ch][sample] or [row][sample][ch] in device memory) cut into overlapping frames and turned into a power spectrum or mel
 // features, [row][ch][F][frame], by a windowed DFT whose basis and fold order are a contract on bits.  The basis is evaluated
 // here in double and rounded once; everything about a call is decided here on the host before anything is queued (the refusals,
-// the frame counts, the launch geometry); k_spec (lw_kernels_spec.hip) does the folds.  The call's per-row records travel through
-// pinned arrays in rotation, each guarded by an event, as lw_resample_rows' do.  Nothing else in the library calls into this file.
-#include "lw_internal.hpp"
+// the frame counts, the launch geometry); k_spec (lw_kernels_spec.hip) does the folds.  The call's per-row records are staged as
+// lw_stage.hpp describes.  Nothing else in the library calls into this file.
+#include "lw_stage.hpp"
 #include "lw_spec.hpp"
 
-#include <algorithm>
 #include <cmath>
-#include <cstring>
-
-#define LW_SP_SLOTS 3 // record arrays in rotation: calls queued back to back do not wait for each other's kernels
-
-struct lw_sp_slot {
-	LwSpecRow *h = nullptr, *d = nullptr; // pinned / device, cap records each
-	size_t cap = 0;
-	hipEvent_t done = nullptr; // recorded behind the last launch that read d
-	bool pending = false;
-};
 
 struct lw_spec {
 	int device = 0;
@@ -31,8 +20,7 @@ struct lw_spec {
 	LwSpecPlan plan{};
 	std::vector<float> basis;                  // [2][win_length][B], the public order
 	float *d_basis = nullptr, *d_fb = nullptr; // the kernel's orders (lw_spec.hpp)
-	lw_sp_slot slot[LW_SP_SLOTS];
-	unsigned next = 0;
+	LwStageRing<LwSpecRow> ring;
 	int route = LW_SP_ROUTE_MFMA, last_route = -1;
 	std::vector<LwSpecRow> rows;
 	std::vector<uint64_t> taken;
@@ -99,8 +87,8 @@ lw_spec *lw_spec_create_ex(int device, const lw_spec_params *prm, int *err)
 		*err = LW_ERR_NULL_ARG;
 		return nullptr;
 	}
-	int ndev = 0, lds_limit = 0;
-	if (!lw_hip_ok(hipGetDeviceCount(&ndev), "hipGetDeviceCount") || device < 0 || device >= ndev || !lw_hip_ok(hipSetDevice(device), "hipSetDevice") ||
+	int lds_limit = 0;
+	if (lw_stage_device(device) ||
 			!lw_hip_ok(hipDeviceGetAttribute(&lds_limit, hipDeviceAttributeMaxSharedMemoryPerBlock, device), "hipDeviceGetAttribute(LDS per workgroup)") ||
 			(size_t)lds_limit < LW_SP_LDS_FLOATS * sizeof(float)) { // k_spec's workgroup does not fit this device
 		*err = LW_ERR_DEVICE;
@@ -154,9 +142,7 @@ lw_spec *lw_spec_create_ex(int device, const lw_spec_params *prm, int *err)
 		ok = lw_hip_ok(hipMalloc((void **)&sp->d_fb, m.size() * sizeof(float)), "hipMalloc(spec mel matrix)") &&
 			lw_hip_ok(hipMemcpy(sp->d_fb, m.data(), m.size() * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(spec mel matrix)");
 	}
-	for (auto &sl : sp->slot)
-		ok = ok && lw_hip_ok(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming), "hipEventCreate(spec rows)");
-	if (!ok) {
+	if (!ok || !sp->ring.create("hipEventCreate(spec rows)")) {
 		*err = LW_ERR_DEVICE;
 		lw_spec_destroy(sp.release());
 		return nullptr;
@@ -170,14 +156,7 @@ void lw_spec_destroy(lw_spec *sp)
 		return;
 	(void)hipSetDevice(sp->device);
 	(void)hipDeviceSynchronize();
-	for (auto &s : sp->slot) {
-		if (s.h)
-			(void)hipHostFree(s.h);
-		if (s.d)
-			(void)hipFree(s.d);
-		if (s.done)
-			(void)hipEventDestroy(s.done);
-	}
+	sp->ring.destroy();
 	if (sp->d_basis)
 		(void)hipFree(sp->d_basis);
 	if (sp->d_fb)
@@ -263,38 +242,29 @@ int lw_spec_rows(lw_spec *sp, int fmt, uint32_t ch, const void *d_src, size_t n_
 	const int64_t lead = kaldi ? lw_spec_kaldi_lead(sp->win_length, sp->hop, sp->framing == LW_SPEC_FRAMES_KALDI_SNIP)
 	                           : (int64_t)sp->plan.offset - (int64_t)(sp->center ? sp->n_fft / 2 : 0);
 	// both buffers must be addressable in 64 bits of BYTES
-	uint64_t e = 0;
-	if (__builtin_mul_overflow((uint64_t)ch, (uint64_t)src_capacity, &e) || __builtin_mul_overflow(e, (uint64_t)n_src_rows, &e) || e > UINT64_MAX / 4 ||
-			__builtin_mul_overflow((uint64_t)ch * F, (uint64_t)frame_capacity, &e) || __builtin_mul_overflow(e, (uint64_t)n_dst_rows, &e) ||
-			e > UINT64_MAX / 4)
+	if (!lw_rows_bytes_ok(ch, src_capacity, n_src_rows) || !lw_rows_bytes_ok((uint64_t)ch * F, frame_capacity, n_dst_rows))
 		return LW_ERR_CAPACITY;
 	// ---- plan: every row is checked before anything is queued, so a refused call has written nothing
 	sp->rows.clear();
-	sp->taken.clear();
 	uint64_t most = 0;
-	for (size_t i = 0; i < n_src_rows; i++) {
-		const uint64_t row = dst_row ? dst_row[i] : i;
-		if (len[i] > src_capacity || row >= n_dst_rows)
-			return LW_ERR_CAPACITY;
-		if (sp->pad_mode == LW_SPEC_PAD_REFLECT && len[i] != 0 && len[i] < lw_spec_reflect_min_len(sp->n_fft))
-			return LW_ERR_CAPACITY; // one reflection does not reach every support sample
-		const uint64_t frames = lw_spec_frames(sp, len[i]);
-		if (frames > frame_capacity)
-			return LW_ERR_CAPACITY;
-		if (sp->pad_mode == LW_SPEC_PAD_SYMMETRIC && frames) {
-			// the first and the last index the row's frames touch (len <= the capacity of a buffer: no overflow); one reflection
-			// reaches [-len, 2 len - 1]
-			const int64_t first = lead, last = (int64_t)((frames - 1) * sp->hop) + lead + (int64_t)sp->win_length - 1, n = (int64_t)len[i];
-			if (first < -n || last > 2 * n - 1)
-				return LW_ERR_CAPACITY;
-		}
-		sp->rows.push_back(LwSpecRow{len[i], frames, row});
-		sp->taken.push_back(row);
-		most = std::max(most, frames);
-	}
-	std::sort(sp->taken.begin(), sp->taken.end());
-	if (std::adjacent_find(sp->taken.begin(), sp->taken.end()) != sp->taken.end())
-		return LW_ERR_CAPACITY; // two source rows for one destination row
+	if (int rc = lw_stage_mapped_rows(sp->taken, n_src_rows, len, dst_row, src_capacity, n_dst_rows, [&](uint64_t len_i, uint64_t row) {
+		    if (sp->pad_mode == LW_SPEC_PAD_REFLECT && len_i != 0 && len_i < lw_spec_reflect_min_len(sp->n_fft))
+			    return LW_ERR_CAPACITY; // one reflection does not reach every support sample
+		    const uint64_t frames = lw_spec_frames(sp, len_i);
+		    if (frames > frame_capacity)
+			    return LW_ERR_CAPACITY;
+		    if (sp->pad_mode == LW_SPEC_PAD_SYMMETRIC && frames) {
+			    // the first and the last index the row's frames touch (len <= the capacity of a buffer: no overflow); one reflection
+			    // reaches [-len, 2 len - 1]
+			    const int64_t first = lead, last = (int64_t)((frames - 1) * sp->hop) + lead + (int64_t)sp->win_length - 1, n = (int64_t)len_i;
+			    if (first < -n || last > 2 * n - 1)
+				    return LW_ERR_CAPACITY;
+		    }
+		    sp->rows.push_back(LwSpecRow{len_i, frames, row});
+		    most = std::max(most, frames);
+		    return LW_OK;
+	    }))
+		return rc;
 	if (most && (!d_src || !d_dst)) // (a row with a frame has a sample)
 		return LW_ERR_NULL_ARG;
 	const uint64_t tiles = (most + LW_SP_TF - 1) / LW_SP_TF;
@@ -302,32 +272,18 @@ int lw_spec_rows(lw_spec *sp, int fmt, uint32_t ch, const void *d_src, size_t n_
 		return LW_ERR_CAPACITY;
 	if (most == 0)
 		return LW_OK;
-	// ---- queue: the records, then one launch per 65535 rows
+	// ---- queue: the records, then the launches
 	HIP_TRY(hipSetDevice(sp->device));
 	hipStream_t st = (hipStream_t)hip_stream;
-	lw_sp_slot &s = sp->slot[sp->next];
-	if (s.pending) { // an earlier call's copy of these records may still be on its way
-		HIP_TRY(hipEventSynchronize(s.done));
-		s.pending = false;
-	}
-	if (s.cap < n_src_rows) {
-		if (s.h)
-			(void)hipHostFree(s.h);
-		if (s.d)
-			(void)hipFree(s.d);
-		s.h = s.d = nullptr;
-		s.cap = 0;
-		const size_t cap = std::max<size_t>(n_src_rows, 64);
-		HIP_TRY(hipHostMalloc((void **)&s.h, cap * sizeof(LwSpecRow), 0));
-		HIP_TRY(hipMalloc((void **)&s.d, cap * sizeof(LwSpecRow)));
-		s.cap = cap;
-	}
-	std::memcpy(s.h, sp->rows.data(), n_src_rows * sizeof(LwSpecRow));
-	HIP_TRY(hipMemcpyAsync(s.d, s.h, n_src_rows * sizeof(LwSpecRow), hipMemcpyHostToDevice, st));
+	if (int rc = sp->ring.acquire(n_src_rows))
+		return rc;
+	LwStageGuard staged = sp->ring.guard(st);
+	if (int rc = sp->ring.upload(sp->rows, st))
+		return rc;
 	const bool itl = fmt == LW_FMT_F32_INTERLEAVED;
 	const LwSpecPlan &p = sp->plan;
 	LwSpecArgs a{};
-	a.src = (const float *)d_src, a.dst = (float *)d_dst, a.basis = sp->d_basis, a.fb = sp->d_fb, a.rows = s.d;
+	a.src = (const float *)d_src, a.dst = (float *)d_dst, a.basis = sp->d_basis, a.fb = sp->d_fb, a.rows = sp->ring.dev();
 	a.s = itl ? LwSpecLayout{(uint64_t)src_capacity * ch, 1, ch} : LwSpecLayout{(uint64_t)src_capacity * ch, src_capacity, 1};
 	a.d_line = frame_capacity, a.d_ch = F * frame_capacity, a.d_row = a.d_ch * ch;
 	a.lead = lead;
@@ -337,14 +293,14 @@ int lw_spec_rows(lw_spec *sp, int fmt, uint32_t ch, const void *d_src, size_t n_
 	}
 	a.hop = sp->hop, a.win_length = sp->win_length, a.k_pad = p.k_pad, a.bins = p.bins, a.passes = p.passes, a.n_mels = sp->n_mels, a.mel_pad = p.mel_pad;
 	a.pad_mode = (uint32_t)sp->pad_mode;
-	for (size_t r0 = 0; r0 < n_src_rows; r0 += 65535) {
-		a.row0 = (uint32_t)r0;
-		HIP_TRY(lw_launch_spec(a, sp->route, (uint32_t)tiles, ch, (uint32_t)std::min<size_t>(n_src_rows - r0, 65535), st));
-	}
-	HIP_TRY(hipEventRecord(s.done, st));
-	s.pending = true;
+	if (lw_stage_launch(n_src_rows, "lw_launch_spec", [&](uint32_t row0, uint32_t n) {
+		    a.row0 = row0;
+		    return lw_launch_spec(a, sp->route, (uint32_t)tiles, ch, n, st);
+	    }) < 0)
+		return LW_ERR_DEVICE;
+	if (int rc = staged.commit())
+		return rc;
 	sp->last_route = sp->route;
-	sp->next = (sp->next + 1) % LW_SP_SLOTS;
 	return LW_OK;
 }
 

@@ -7,7 +7,7 @@
 //   packets.bin: [u32 length][bytes] of the three header packets, then of the audio packets of one stream (one batch, one
 //   PreviousWindowRight: the first packet yields no samples)
 //   places.txt: one line "row skip keep t0" per audio packet
-//   CASE: ok (default) | twice | refuse | null_rows | null_place | null_batch | null_r | other_fmt | other_decoder | n_short | small_max
+//   CASE: ok (default) | twice | fail (the k_rows launch of the first of two calls fails) | refuse | null_rows | null_place | null_batch | null_r | other_fmt | other_decoder | n_short | small_max
 //   output: "R status n_samples out_offset" per packet, "S src count dst" per piece of each k_rows launch, "RC rc",
 //   "LAUNCHES k_rows synth" (synth: 1 when a synthesis launcher ran), "N segments copied_elems"
 #include "../../include/lewton_amd.h"
@@ -22,10 +22,15 @@
 
 static uint64_t g_src_elems = 0, g_dst_elems = 0;
 static int g_rows_launches = 0;
+static bool g_fail_rows_launch = false; // the next k_rows launch fails, once
 
 hipError_t lw_launch_rows(const void *d_src, void *d_dst, const LwRowSeg *d_segs, uint32_t n_segs, int elem_size, hipStream_t)
 {
 	g_rows_launches++;
+	if (g_fail_rows_launch) {
+		g_fail_rows_launch = false;
+		return hipErrorLaunchFailure;
+	}
 	if (!d_src || !d_dst || (elem_size != 2 && elem_size != 4)) {
 		printf("BAD arguments\n");
 		exit(3);
@@ -130,7 +135,8 @@ int main(int argc, char **argv)
 			lw_pwr_free(p2);
 		}
 		// every CASE but ok / twice is expected to be refused: armed, the first synthesis launcher that runs takes this to 0
-		const bool armed = cs != "ok" && cs != "twice";
+		const bool armed = cs != "ok" && cs != "twice" && cs != "fail";
+		g_fail_rows_launch = cs == "fail";
 		lw_standin_fail_launch.store(armed ? 1 : 0);
 		int rc;
 		if (cs == "null_rows")
@@ -145,7 +151,7 @@ int main(int argc, char **argv)
 			rc = lw_rows_synth(r, b, place.data(), n - 1, rows, n_rows, cap, nullptr);
 		else {
 			rc = lw_rows_synth(r, bx, place.data(), n, rows, n_rows, cap, nullptr); // (refuse: places the test made unacceptable)
-			if (rc == LW_OK && cs == "twice") {
+			if ((rc == LW_OK && cs == "twice") || (rc == LW_ERR_DEVICE && cs == "fail")) { // (fail: the object takes the next call)
 				printf("RC %d\n", rc);
 				rc = lw_rows_synth(r, bx, place.data(), n, rows, n_rows, cap, nullptr);
 			}

@@ -9,6 +9,7 @@
 //   places.txt: one line "row skip keep t0" per audio packet
 //   MATRIX: a text file "out_ch in_ch" and then out_ch * in_ch coefficients (out_ch / in_ch are passed on as they stand)
 //   CASE: ok | twice | two (MATRIX, then MATRIX_B without synchronising) | plain_between (mix, lw_rows_synth, mix) | refuse |
+//         fail (the k_rows_mix launch of the first of two calls fails) |
 //         null_mix | null_coef | null_rows | null_place | null_batch | null_r | other_fmt | n_short
 //   output: "R status n_samples out_offset" per packet; per k_rows_mix launch "M out_ch in_ch cap itl coefficient bits..." and
 //   "P src stride count dst" per piece; "K n" per k_rows launch; "RC rc" per call; "A coefficient bits..." per k_rows_mix launch:
@@ -27,6 +28,7 @@
 
 static uint64_t g_src_elems = 0, g_rows = 0;
 static int g_mix_launches = 0, g_rows_launches = 0;
+static bool g_fail_mix_launch = false; // the next k_rows_mix launch fails, once
 static std::vector<std::pair<const float *, uint32_t>> g_coef; // what each k_rows_mix launch was given, looked at again at the end
 
 hipError_t lw_launch_rows(const void *, void *, const LwRowSeg *, uint32_t n_segs, int, hipStream_t)
@@ -40,6 +42,10 @@ hipError_t lw_launch_rows_mix(const void *d_src, void *d_dst, const LwRowMixPiec
 		uint32_t out_ch, uint64_t row_capacity, int elem_size, bool interleaved, hipStream_t)
 {
 	g_mix_launches++;
+	if (g_fail_mix_launch) {
+		g_fail_mix_launch = false;
+		return hipErrorLaunchFailure;
+	}
 	if (!d_src || !d_dst || !d_pieces || !d_coef || (elem_size != 2 && elem_size != 4) || out_ch == 0 || out_ch > LW_ROWS_MIX_MAX_OUT || in_ch == 0) {
 		printf("BAD arguments\n");
 		exit(3);
@@ -175,7 +181,8 @@ int main(int argc, char **argv)
 			lw_pwr_free(p2);
 		}
 		// every CASE but these is expected to be refused: armed, the first synthesis launcher that runs takes this to 0
-		const bool armed = cs != "ok" && cs != "twice" && cs != "two" && cs != "plain_between";
+		const bool armed = cs != "ok" && cs != "twice" && cs != "two" && cs != "plain_between" && cs != "fail";
+		g_fail_mix_launch = cs == "fail";
 		lw_standin_fail_launch.store(armed ? 1 : 0);
 		int rc;
 		if (cs == "null_mix")
@@ -196,18 +203,18 @@ int main(int argc, char **argv)
 			rc = lw_rows_synth_mix(r, b, place.data(), n - 1, &ma.mix, rows, n_rows, cap, nullptr);
 		else {
 			rc = lw_rows_synth_mix(r, bx, place.data(), n, &ma.mix, rows, n_rows, cap, nullptr); // (refuse: what the test made unacceptable)
-			if (rc == LW_OK && (cs == "twice" || cs == "two" || cs == "plain_between")) {
+			if ((rc == LW_OK && (cs == "twice" || cs == "two" || cs == "plain_between")) || (rc == LW_ERR_DEVICE && cs == "fail")) {
 				printf("RC %d\n", rc);
 				Matrix again;
-				if (cs == "twice" && !read_matrix(argv[8], again))
+				if ((cs == "twice" || cs == "fail") && !read_matrix(argv[8], again))
 					return 2;
 				std::fill(ma.coef.begin(), ma.coef.end(), -123.0f); // the first call has copied its matrix: the caller's is free
 				if (cs == "plain_between") {
 					rc = lw_rows_synth(r, b, place.data(), n, rows, n_rows, cap, nullptr);
 					printf("RC %d\n", rc);
 				}
-				if (rc == LW_OK)
-					rc = lw_rows_synth_mix(r, b, place.data(), n, cs == "twice" ? &again.mix : &mb.mix, rows, n_rows, cap, nullptr);
+				if (rc == LW_OK || cs == "fail") // (fail: the object takes the next call)
+					rc = lw_rows_synth_mix(r, b, place.data(), n, cs == "two" || cs == "plain_between" ? &mb.mix : &again.mix, rows, n_rows, cap, nullptr);
 			}
 		}
 		printf("RC %d\n", rc);

@@ -209,6 +209,18 @@ def test_capacity_refusals_are_decided_for_every_packet_first(harness, tmp_path)
     assert rcs == [OK] and pieces
 
 
+def test_a_failed_k_rows_launch_is_a_status_and_the_next_call_is_accepted(harness, tmp_path):
+    """the launch behind the descriptors' upload fails: LW_ERR_DEVICE (33), and the same call again is accepted and launches its
+    whole list (the slot the failed call used stays marked: lewton_amd/csrc/lw_stage.hpp; tests/test_host_stage_ring.py has the
+    model of what is in flight)"""
+    path = _packets_file(tmp_path, SETUPS["stereo"](), "LLSL", 8, 5)
+    res = _results(_run(harness, path, 2, "results"))
+    places, t = _cursor_places(res)
+    _, want, _, _ = _synth(harness, tmp_path, path, 2, places, 1, t)
+    rcs, pieces, launches, _ = _synth(harness, tmp_path, path, 2, places, 1, t, "fail")
+    assert rcs == [33, OK] and launches == (2, 0) and pieces == want and want
+
+
 def test_destination_beyond_2_to_the_32_elements(harness, tmp_path):
     """i16 planar stereo, 3 rows of 2^30 samples: row 2 starts at element 2^32 of the rows buffer"""
     path = _packets_file(tmp_path, SETUPS["stereo"](), "LLSL", 8, 7)

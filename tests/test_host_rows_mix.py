@@ -263,6 +263,15 @@ def test_capacity_refusals_are_decided_for_every_packet_first(harness, tmp_path)
     assert rcs == [OK] and launches[0][5]
 
 
+def test_a_failed_k_rows_mix_launch_is_a_status_and_the_next_call_is_accepted(harness, tmp_path):
+    """the launch behind the upload of pieces and matrix fails: LW_ERR_DEVICE (33), and the same call again is accepted and is
+    handed its pieces and its matrix (the slot the failed call used stays marked: lewton_amd/csrc/lw_stage.hpp)"""
+    path, res, places, t = _refusal_setup(harness, tmp_path)
+    rcs, launches, after, counts, intro = _synth(harness, tmp_path, path, 2, places, 1, t, "fail", _matrix_file(tmp_path, "a.txt", MONO))
+    assert rcs == [33, OK] and counts == (2, 0, 0) and len(launches) == 1 and after == [_bits(MONO)]
+    _check(launches[0], res, places, 2, MONO, False, t, intro)
+
+
 @pytest.mark.parametrize("fmt", ["f32", "f32_interleaved"])
 def test_two_matrices_back_to_back_each_launch_has_its_own(harness, tmp_path, fmt):
     """matrix A, then matrix B of another out_ch without synchronising: each launcher is handed its own matrix, and A's is
