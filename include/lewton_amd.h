@@ -668,6 +668,76 @@ int lw_cep_rows(lw_cep *cp, uint32_t ch, const void *d_src, void *d_dst, size_t 
 		const uint64_t *fill_to, void *hip_stream);
 int lw_cep_last_launches(const lw_cep *cp);
 
+/* ---- frame-major model input ---------------------------------------------------------------------------------------------
+ * The last step between the chain's feature rows and a model that reads [batch][frame][feature] (WeNet, icefall, ESPnet, FunASR,
+ * SeamlessM4T, AST, BEATs): transpose, splice or stack-and-skip a context of frames, a global shift and scale per output element,
+ * ONE rounding to the model's number format, padding and the padding mask, on the GPU, as a pass of its own (k_pack) that reads
+ * the source once and writes the destination once.  Source: f32 [row][ch][F][frame_capacity], the layout of every stage before
+ * it; row i has n_frames[i] frames.  An object is made from (F, left, right, stride, edge, dtype, shift, scale, pad); W = left +
+ * right + 1, D = W * F.  Destination: [row][ch][out_capacity][D] of dtype (LW_PACK_F32, LW_PACK_BF16, LW_PACK_F16): a frame is D
+ * contiguous elements, element j = k * F + f is feature line f of context position k, k = 0 the oldest frame (Kaldi's
+ * splice-feats and FunASR's LFR order).  A contract on BITS.
+ *   Frames of a row, T = n_frames[row], all in signed 64-bit integers:
+ *     LW_PACK_EDGE_REPLICATE  T_out = ceil(T / stride);  context position k of output frame u is source frame
+ *                             c(u * stride - left + k), c(i) = min(max(i, 0), T - 1)   (FunASR's apply_lfr(m, n) is left =
+ *                             (m - 1) / 2, right = m - 1 - left, stride = n)
+ *     LW_PACK_EDGE_VALID      T_out = T < W ? 0 : (T - W) / stride + 1;  source frame u * stride + k, never outside the row
+ *                             ("stack m skip n": left = 0, right = m - 1, stride = n)
+ *   Value, with x the source element:  v = x;  if shift is given v = v + shift[j], ONE rounded f32 addition;  if scale is given
+ *     v = v * scale[j], ONE rounded f32 multiplication;  nothing is fused.  A step whose array is NULL is SKIPPED, not done with 0
+ *     or 1 (-0.0 + 0.0 is not a bit copy).  shift and scale are D HOST floats each, copied at creation, indexed by the OUTPUT
+ *     element j (a per-line vector is repeated W times by the caller).  With both NULL and LW_PACK_F32 the pass is a bit copy of
+ *     every value, NaN payloads included.
+ *   Conversion: one rounding of v, in integer arithmetic on its bit pattern u (a = u & 0x7fffffff, s = the sign moved to bit 15):
+ *     LW_PACK_BF16  a > 0x7f800000 (a NaN, taken FIRST): a NaN.  Otherwise (u + 0x7fff + ((u >> 16) & 1)) >> 16: round to nearest
+ *                   even on bit 16; a finite value may round to infinity.
+ *     LW_PACK_F16   a > 0x7f800000: a NaN.  a >= 0x47800000 (65536 and above, infinity): s | 0x7c00.  a >= 0x38800000 (2^-14 and
+ *                   above): m = a - 0x38000000;  s | ((m + 0xfff + ((m >> 13) & 1)) >> 13), which carries into the exponent and,
+ *                   from 65520 on, into infinity.  a < 0x33000000 (below 2^-25): s.  Otherwise a subnormal: e = a >> 23, sh = 126 - e
+ *                   (14 .. 24), M = (a & 0x7fffff) | 0x800000, r = M >> sh, rem = M & ((1 << sh) - 1), half = 1 << (sh - 1);
+ *                   r = r + 1 if rem > half or (rem == half and r is odd);  s | r.  IEEE round to nearest even throughout.
+ *     A NaN stays a NaN; which NaN is outside the contract.  Every other bit is inside it, the sign of a zero included.
+ *   Fill and mask: positions [T_out, max(T_out, fill_to[row])) of every channel receive pad, an f32 parameter converted by the same
+ *     rule, without shift or scale.  d_mask, when given, is uint8 [n_rows][out_capacity]: 1 on [0, T_out), 0 on [T_out, fill_end),
+ *     written once, not once per channel.  Nothing else of either buffer is written, and nothing of d_src at or beyond n_frames of
+ *     a line is read.  Any overlap of source and destination is the caller's error.
+ *
+ * lw_pack_rows: n_frames and fill_to (may be NULL: nothing is filled; in OUTPUT frames) are HOST arrays, copied during the call.
+ * Asynchronous on hip_stream; calls on one object may be queued back to back.  ONE kernel launch per 65535 rows, none when nothing
+ * is to be written.  A workgroup takes lw_pack_tile_frames consecutive output frames of a row and channel; the bits depend
+ * neither on the tile nor on the grid.  lw_pack_width: D.  lw_pack_frames: T_out of T, on the host.  lw_pack_convert: the
+ * conversion of one value on the host, from the same source as the kernel's; the bit pattern in the low 32 or 16 bits.
+ * lw_pack_last_launches: the kernels the last accepted call queued, -1 = no call yet.
+ * Refusals, decided on the host before anything is queued:
+ *   LW_ERR_NULL_ARG     pk or p NULL, n_frames NULL with rows, d_src NULL with frames to read, d_dst NULL with elements to write
+ *   LW_ERR_UNSUPPORTED  (create) an unknown edge or dtype, F outside 1 .. 65535, left or right > LW_PACK_MAX_CONTEXT, stride == 0 or
+ *                       > LW_PACK_MAX_STRIDE, pad NaN
+ *   LW_ERR_DEVICE       (create) no such device, or one whose workgroups have less LDS than the kernel's image (min(F, 32) lines
+ *                       of up to 289 floats; the device is asked)
+ *   LW_ERR_CAPACITY     n_frames[i] > frame_capacity, lw_pack_frames(n_frames[i]) or fill_to[i] > out_capacity, ch == 0 or > 255, a
+ *                       buffer that 64 bits of bytes cannot address, more than 2^24 - 1 tiles in a row (a grid dimension holds
+ *                       fewer than 2^32 lanes, a workgroup has 256) */
+#define LW_PACK_MAX_CONTEXT 16
+#define LW_PACK_MAX_STRIDE 16
+typedef struct lw_pack lw_pack;
+enum { LW_PACK_F32 = 0, LW_PACK_BF16 = 1, LW_PACK_F16 = 2 };
+enum { LW_PACK_EDGE_REPLICATE = 0, LW_PACK_EDGE_VALID = 1 };
+typedef struct {
+	uint32_t F, left, right, stride;
+	int32_t edge, dtype;
+	float pad;
+	uint32_t reserved; /* 0 */
+} lw_pack_params;
+lw_pack *lw_pack_create(int device, const lw_pack_params *p, const float *shift, const float *scale, int *err);
+void lw_pack_destroy(lw_pack *pk);
+uint32_t lw_pack_width(const lw_pack *pk);
+uint32_t lw_pack_tile_frames(const lw_pack *pk);
+uint64_t lw_pack_frames(const lw_pack *pk, uint64_t T);
+uint32_t lw_pack_convert(const lw_pack *pk, float v);
+int lw_pack_rows(lw_pack *pk, uint32_t ch, const void *d_src, void *d_dst, size_t n_rows, size_t frame_capacity, size_t out_capacity,
+		const uint64_t *n_frames, const uint64_t *fill_to, uint8_t *d_mask, void *hip_stream);
+int lw_pack_last_launches(const lw_pack *pk);
+
 /* ---- staging ring (BASELINE north_star: "pinned hipMemcpyAsync staging ring so entropy decode of packet N+1 overlaps
  * GPU synthesis of packet N") ------------------------------------------------------------------------------------------
  * A ring of `slots` staging slots on the decoder's device; a slot = one batch object (pinned records + device mirror), a device

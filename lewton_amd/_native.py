@@ -68,6 +68,11 @@ class NormParams(C.Structure):
                 ("target", C.c_double)]
 
 
+class PackParams(C.Structure):
+    _fields_ = [("F", C.c_uint32), ("left", C.c_uint32), ("right", C.c_uint32), ("stride", C.c_uint32), ("edge", C.c_int32), ("dtype", C.c_int32),
+                ("pad", C.c_float), ("reserved", C.c_uint32)]
+
+
 class OggPacket(C.Structure):
     _fields_ = [("data", C.c_void_p), ("len", C.c_size_t), ("stream_serial", C.c_uint32), ("absgp_page", C.c_uint64),
                 ("first_in_stream", C.c_uint8), ("last_in_stream", C.c_uint8), ("first_in_page", C.c_uint8),
@@ -202,6 +207,15 @@ SYMBOLS = {
     "lw_cep_tile_frames": (C.c_uint32, [C.c_void_p]),
     "lw_cep_rows": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lw_cep_last_launches": (C.c_int, [C.c_void_p]),
+    "lw_pack_create": (C.c_void_p, [C.c_int, C.POINTER(PackParams), C.c_void_p, C.c_void_p, intp]),
+    "lw_pack_destroy": (None, [C.c_void_p]),
+    "lw_pack_width": (C.c_uint32, [C.c_void_p]),
+    "lw_pack_tile_frames": (C.c_uint32, [C.c_void_p]),
+    "lw_pack_frames": (C.c_uint64, [C.c_void_p, C.c_uint64]),
+    "lw_pack_convert": (C.c_uint32, [C.c_void_p, C.c_float]),
+    "lw_pack_rows": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_void_p]),
+    "lw_pack_last_launches": (C.c_int, [C.c_void_p]),
     "lw_ring_create": (C.c_void_p, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, intp]),
     "lw_ring_destroy": (None, [C.c_void_p]),
     "lw_ring_stage": (C.c_int, [C.c_void_p, C.POINTER(Packet), C.c_size_t, C.c_int]),
@@ -287,6 +301,8 @@ FEAT_LOG_NONE, FEAT_LOG_LN, FEAT_LOG_LOG10, FEAT_LOG_DB = 0, 1, 2, 3
 FEAT_SCOPE_ROW, FEAT_SCOPE_CHANNEL = 0, 1
 NORM_SCALE_NONE, NORM_SCALE_STD, NORM_SCALE_RMS, NORM_SCALE_PEAK = 0, 1, 2, 3
 NORM_SCOPE_ROW, NORM_SCOPE_CHANNEL, NORM_SCOPE_LINE = 0, 1, 2
+PACK_F32, PACK_BF16, PACK_F16 = 0, 1, 2
+PACK_EDGE_REPLICATE, PACK_EDGE_VALID = 0, 1
 
 
 def fmt_dtype(fmt):

@@ -44,6 +44,12 @@ bit), over a waveform tensor [B, C, T] or a feature tensor [B, C, F, frames]:
     Normalize.wav2vec2().run(pcm, lengths)                                  # in place; or decode_ogg_files(..., normalize="wav2vec2")
     Normalize.cmvn().run(feats, frames, fill_to=3000)
 
+FramePack turns the chain's [B, C, F, frames] into the [B, C, frames, W * F] most other speech models read (lw_pack_rows, k_pack in
+csrc/lw_kernels_pack.hip: transpose, context splice and stride, a global shift and scale, one rounding to float32, bfloat16 or
+float16, padding and the padding mask in one launch, bit for bit):
+
+    out, out_frames, mask = FramePack.lfr(80, shift=s, scale=g, dtype="bf16").run(feats, frames, want_mask=True)
+
 torch is imported inside the functions, never at module import.
 """
 import ctypes as C
@@ -1132,6 +1138,183 @@ class KaldiFbank:
         if self.norm is not None:
             self.norm.run(out, frames, fill_to=fill_to, stream=stream)
         return out, frames
+
+
+PACK_MAX_CONTEXT, PACK_MAX_STRIDE, PACK_MAX_F = 16, 16, 65535      # LW_PACK_MAX_CONTEXT, LW_PACK_MAX_STRIDE, the limit on F
+_PACK_DTYPES = {"f32": 0, "bf16": 1, "f16": 2}                     # LW_PACK_F32, LW_PACK_BF16, LW_PACK_F16
+_PACK_EDGES = {"replicate": 0, "valid": 1}                         # LW_PACK_EDGE_REPLICATE, LW_PACK_EDGE_VALID
+
+
+def _pack_params(n_in, left, right, stride, edge, dtype, shift, scale, pad):
+    """(F, left, right, stride, edge, dtype, shift, scale, pad) checked, the two vectors as contiguous float32 [W * F] or None; or
+    ValueError for what lw_pack_create refuses"""
+    if not _is_int(n_in) or not 1 <= n_in <= PACK_MAX_F:
+        raise ValueError("n_in=%r: an integer in 1 .. %d" % (n_in, PACK_MAX_F))
+    for name, v in (("left", left), ("right", right)):
+        if not _is_int(v) or not 0 <= v <= PACK_MAX_CONTEXT:
+            raise ValueError("%s=%r: an integer in 0 .. %d" % (name, v, PACK_MAX_CONTEXT))
+    if not _is_int(stride) or not 1 <= stride <= PACK_MAX_STRIDE:
+        raise ValueError("stride=%r: an integer in 1 .. %d" % (stride, PACK_MAX_STRIDE))
+    if edge not in _PACK_EDGES:
+        raise ValueError("edge=%r: \"replicate\" or \"valid\"" % (edge,))
+    if dtype not in _PACK_DTYPES:
+        raise ValueError("dtype=%r: \"f32\", \"bf16\" or \"f16\"" % (dtype,))
+    try:
+        pad = float(pad)
+    except (TypeError, ValueError):
+        raise ValueError("pad must be a number")
+    if pad != pad:
+        raise ValueError("pad must not be a NaN")
+    D = (int(left) + int(right) + 1) * int(n_in)
+    vecs = []
+    for name, v in (("shift", shift), ("scale", scale)):
+        if v is not None:
+            try:
+                v = np.ascontiguousarray(v, np.float32)
+            except (TypeError, ValueError):
+                raise ValueError("%s= must be an array of numbers" % name)
+            if v.shape != (D,):
+                raise ValueError("%s= must hold W * n_in = %d values (one per OUTPUT element), not %r" % (name, D, v.shape))
+        vecs.append(v)
+    return int(n_in), int(left), int(right), int(stride), edge, dtype, vecs[0], vecs[1], pad
+
+
+class FramePack:
+    """lw_pack: feature rows [rows][C][n_in][frame capacity] (float32, the chain's layout) -> [rows][C][out capacity][W * n_in]
+    frames of float32, bfloat16 or float16 on the GPU (k_pack), by the rule of include/lewton_amd.h ("frame-major model input"), a
+    contract on bits: W = left + right + 1 frames of context per output frame, every stride-th frame, the edge frames replicated
+    (edge="replicate": ceil(T / stride) frames, FunASR's LFR) or only whole windows (edge="valid": Kaldi's splice without
+    padding, "stack m skip n"); then + shift[j], * scale[j] per OUTPUT element j = k * n_in + f where given (a global CMVN), ONE
+    rounding to dtype, pad beyond the frames and the padding mask.  Parameter errors are ValueError and need no GPU; the object
+    itself lives on cuda:device."""
+
+    def __init__(self, n_in, left=0, right=0, stride=1, edge="replicate", dtype="f32", shift=None, scale=None, pad=0.0, device=0):
+        (self.n_in, self.left, self.right, self.stride, self.edge, self.dtype, self._shift, self._scale,
+         self.pad) = _pack_params(n_in, left, right, stride, edge, dtype, shift, scale, pad)
+        self.device = device
+        _gpu()
+        err = C.c_int(0)
+        p = N.PackParams(self.n_in, self.left, self.right, self.stride, _PACK_EDGES[edge], _PACK_DTYPES[dtype], self.pad, 0)
+        self._h = N.lw_pack_create(device, C.byref(p), None if self._shift is None else self._shift.ctypes.data_as(C.c_void_p),
+                                   None if self._scale is None else self._scale.ctypes.data_as(C.c_void_p), C.byref(err))
+        if not self._h:
+            if err.value in (N.ERR_UNSUPPORTED, N.ERR_NULL_ARG):
+                raise ValueError("lw_pack_create refused the parameters")
+            raise RuntimeError("lw_pack_create failed (%d): %s" % (err.value, N.device_error()))
+        assert self.width == (self.left + self.right + 1) * self.n_in
+
+    @classmethod
+    def transpose(cls, n_in, **kw):
+        """[n_in][frame] -> [frame][n_in], nothing else"""
+        return cls(n_in, **kw)
+
+    @classmethod
+    def splice(cls, n_in, left, right, **kw):
+        """Kaldi's splice-feats: every frame with `left` frames before it and `right` behind, the edge frames replicated"""
+        return cls(n_in, left, right, **kw)
+
+    @classmethod
+    def subsample(cls, n_in, n, **kw):
+        """Kaldi's subsample-feats: every n-th frame"""
+        return cls(n_in, 0, 0, n, **kw)
+
+    @classmethod
+    def stack(cls, n_in, m, n, **kw):
+        """"stack m skip n": frames u * n .. u * n + m - 1, whole windows only"""
+        if not _is_int(m) or m < 1:
+            raise ValueError("m=%r: a positive integer" % (m,))
+        return cls(n_in, 0, m - 1, n, edge="valid", **kw)
+
+    @classmethod
+    def lfr(cls, n_in, m=7, n=6, **kw):
+        """FunASR's low frame rate input (apply_lfr): m frames stacked, every n-th kept, (m - 1) // 2 copies of the first frame
+        in front and the last frame repeated behind"""
+        if not _is_int(m) or m < 1:
+            raise ValueError("m=%r: a positive integer" % (m,))
+        return cls(n_in, (m - 1) // 2, m - 1 - (m - 1) // 2, n, **kw)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            N.lw_pack_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        if N is not None and getattr(N, "lw_pack_destroy", None) is not None:  # not during interpreter shutdown
+            self.close()
+
+    @property
+    def width(self):
+        """elements per output frame: D = W * n_in"""
+        return int(N.lw_pack_width(self._h))
+
+    @property
+    def tile_frames(self):
+        """the output frames one workgroup produces (lw_pack_tile_frames)"""
+        return int(N.lw_pack_tile_frames(self._h))
+
+    def frames(self, T):
+        """output frames of a row of T frames (lw_pack_frames)"""
+        return int(N.lw_pack_frames(self._h, int(T)))
+
+    def convert(self, v):
+        """the contract's conversion of one float32 value on the host (lw_pack_convert): the bit pattern as an integer"""
+        return int(N.lw_pack_convert(self._h, float(np.float32(v))))
+
+    def last_launches(self):
+        """kernels the last call queued: 1 per 65535 rows, 0 when nothing was to be written; -1: no call yet"""
+        return N.lw_pack_last_launches(self._h)
+
+    def run(self, feat, frames, out=None, fill_to=None, want_mask=False, stream=None):
+        """lw_pack_rows: frames[i] frames of every line of row i of feat (float32 [rows][C][n_in][frame capacity]) -> out
+        ([rows][C][out capacity][width] of the object's dtype; None: a zeroed tensor whose capacity is the largest of the rows'
+        output frames and fill_to; it must not overlap feat).  fill_to: None, one count for all rows or one per row, in OUTPUT
+        frames -- positions [out_frames[i], fill_to[i]) of every channel receive pad.  want_mask: True for a zeroed uint8 tensor
+        [rows][out capacity], or such a tensor of the caller's: 1 on a row's frames, 0 on its padding up to fill_to, nothing else
+        of it written.  Nothing else of out is written either.  stream: a hipStream_t value; None = torch's current stream on the object's
+        device.  Asynchronous; returns (out, out_frames) or (out, out_frames, mask), out_frames a numpy uint64 array."""
+        torch = _gpu()
+        if (feat.dtype != torch.float32 or feat.device.type != "cuda" or feat.device.index != self.device or not feat.is_contiguous() or
+                feat.dim() != 4 or feat.shape[2] != self.n_in):
+            raise ValueError("feat must be a contiguous float32 tensor [rows][C][%d][frames] on cuda:%d" % (self.n_in, self.device))
+        n_rows, ch, _, cap = feat.shape
+        counts = [int(v) for v in (frames.tolist() if hasattr(frames, "tolist") else frames)]
+        if len(counts) != n_rows or any(v < 0 for v in counts):
+            raise ValueError("frames= needs one non-negative entry per row of feat")
+        fill = None
+        if fill_to is not None:
+            fill = fill_to.tolist() if hasattr(fill_to, "tolist") else fill_to
+            fill = [int(fill)] * n_rows if isinstance(fill, (int, np.integer)) else [int(v) for v in fill]
+            if len(fill) != n_rows or any(v < 0 for v in fill):
+                raise ValueError("fill_to= needs one non-negative count, or one per row of feat")
+        out_frames = np.asarray([self.frames(v) for v in counts], np.uint64)
+        tdtype = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}[self.dtype]
+        if out is None:
+            out_cap = max(out_frames.tolist() + (fill or []), default=0)
+            out = torch.zeros((n_rows, ch, out_cap, self.width), dtype=tdtype, device=feat.device)
+        if out.dtype != tdtype or out.device.type != "cuda" or out.device.index != self.device or not out.is_contiguous() or out.dim() != 4:
+            raise ValueError("out must be a contiguous %s tensor [rows][C][frames][width] on cuda:%d" % (tdtype, self.device))
+        if tuple(out.shape[:2]) != (n_rows, ch) or out.shape[3] != self.width:
+            raise ValueError("out must be (%d, %d, frames, %d), not %r" % (n_rows, ch, self.width, tuple(out.shape)))
+        out_cap = out.shape[2]
+        mask = None
+        if want_mask is True:
+            mask = torch.zeros((n_rows, out_cap), dtype=torch.uint8, device=feat.device)
+        elif want_mask is not False and want_mask is not None:
+            mask = want_mask
+            if (mask.dtype != torch.uint8 or mask.device != out.device or not mask.is_contiguous() or tuple(mask.shape) != (n_rows, out_cap)):
+                raise ValueError("want_mask= must be True or a contiguous uint8 tensor (%d, %d) on cuda:%d" % (n_rows, out_cap, self.device))
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream or None
+        counts = np.asarray(counts, np.uint64)
+        fill = None if fill is None else np.asarray(fill, np.uint64)
+        rc = N.lw_pack_rows(self._h, ch, C.c_void_p(feat.data_ptr()), C.c_void_p(out.data_ptr()), n_rows, cap, out_cap,
+                            counts.ctypes.data_as(C.c_void_p), None if fill is None else fill.ctypes.data_as(C.c_void_p),
+                            None if mask is None else C.c_void_p(mask.data_ptr()), stream)
+        if rc in (N.ERR_NULL_ARG, N.ERR_CAPACITY, N.ERR_UNSUPPORTED):
+            raise ValueError("lw_pack_rows refused the call (%d)" % rc)
+        if rc:
+            raise RuntimeError("lw_pack_rows: %d %s" % (rc, N.device_error()))
+        return (out, out_frames) if mask is None else (out, out_frames, mask)
 
 
 def _normalizer(normalize, samples, device):
