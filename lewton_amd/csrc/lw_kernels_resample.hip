@@ -46,7 +46,7 @@ LW_RS_FN bool lw_rs_tile(const LwResampleArgs &a, uint32_t tile_outputs, uint32_
 {
 	const LwResampleRow r = a.rows[(uint64_t)a.row0 + bz];
 	t.len = r.len, t.out_len = r.out_len;
-	t.n0 = (uint64_t)bx * tile_outputs;
+	t.n0 = ((uint64_t)a.tile0 + bx) * tile_outputs;
 	if (t.n0 >= r.out_len)
 		return false;
 	t.x0 = (int64_t)(t.n0 / a.new_ * a.orig) - (int64_t)a.half_width; // (route GLOBAL does not use it)
@@ -234,7 +234,7 @@ hipError_t lw_launch_resample(const LwResampleArgs &a, const LwResamplePlan &p, 
 {
 	if (tiles == 0 || n_rows == 0)
 		return hipSuccess;
-	if (ch == 0 || ch > 65535u || n_rows > 65535u || p.lds_floats > LW_RS_LDS_FLOATS || p.blocks != a.blocks)
+	if (ch == 0 || ch > 65535u || n_rows > 65535u || tiles > LW_RS_MAX_TILES || p.lds_floats > LW_RS_LDS_FLOATS || p.blocks != a.blocks)
 		return hipErrorInvalidValue;
 	const dim3 grid(tiles, ch, n_rows);
 	switch (p.route) {

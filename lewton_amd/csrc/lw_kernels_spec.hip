@@ -62,7 +62,7 @@ LW_SP_FN bool lw_sp_tile(const LwSpecArgs &a, uint32_t bx, uint32_t by, uint32_t
 {
 	const LwSpecRow r = a.rows[(uint64_t)a.row0 + bz];
 	t.len = r.len, t.n_frames = r.n_frames;
-	t.f0 = (uint64_t)bx * LW_SP_TF;
+	t.f0 = ((uint64_t)a.tile0 + bx) * LW_SP_TF;
 	if (t.f0 >= r.n_frames)
 		return false;
 	t.x0 = (int64_t)(t.f0 * a.hop) + a.lead;
@@ -485,7 +485,7 @@ hipError_t lw_launch_spec(const LwSpecArgs &a, int route, uint32_t tiles, uint32
 {
 	if (tiles == 0 || n_rows == 0)
 		return hipSuccess;
-	if (ch == 0 || ch > 65535u || n_rows > 65535u || a.k_pad == 0 || a.k_pad % LW_SP_KT || a.mel_pad > 256u || a.mel_pad % 32u ||
+	if (ch == 0 || ch > 65535u || n_rows > 65535u || tiles > LW_SP_MAX_TILES || a.k_pad == 0 || a.k_pad % LW_SP_KT || a.mel_pad > 256u || a.mel_pad % 32u ||
 			(a.n_mels != 0 && !a.fb))
 		return hipErrorInvalidValue;
 	const dim3 grid(tiles, ch, n_rows);

@@ -216,7 +216,13 @@ int lw_resample_rows(lw_resampler *rs, int fmt, uint32_t ch, const void *d_src, 
 	a.orig = rs->orig, a.new_ = rs->new_, a.half_width = rs->half_width, a.k_taps = rs->k_taps, a.blocks = p.blocks;
 	if (lw_stage_launch(n_src_rows, "lw_launch_resample", [&](uint32_t row0, uint32_t n) {
 		    a.row0 = row0;
-		    return lw_launch_resample(a, p, (uint32_t)tiles, ch, n, st);
+		    for (uint64_t t0 = 0; t0 < tiles; t0 += LW_RS_MAX_TILES) { // (a grid dimension holds fewer than 2^32 lanes)
+			    a.tile0 = (uint32_t)t0;
+			    const hipError_t e = lw_launch_resample(a, p, (uint32_t)std::min<uint64_t>(tiles - t0, LW_RS_MAX_TILES), ch, n, st);
+			    if (e != hipSuccess)
+				    return e;
+		    }
+		    return hipSuccess;
 	    }) < 0)
 		return LW_ERR_DEVICE;
 	if (int rc = staged.commit())

@@ -31,6 +31,7 @@ struct LwResampleArgs {
 	uint32_t orig, new_, half_width, k_taps;
 	uint32_t blocks; // M: a tile is J runs of M * new consecutive outputs
 	uint32_t row0;   // first source row of this launch (blockIdx.z counts from it)
+	uint32_t tile0;  // first tile of this launch (blockIdx.x counts from it)
 };
 
 // Where the taps and the input span of a tile are read from.
@@ -42,6 +43,9 @@ enum {
 };
 
 #define LW_RS_THREADS 512u
+#define LW_RS_MAX_TILES 0x7fffffu // tiles of ONE launch: tiles * 512 lanes stays below 2^32, the most a grid dimension holds in lanes
+                                  // (a launch past it is accepted, and workgroups of it never run); a row with more
+                                  // tiles takes several launches, each with its tile0
 #define LW_RS_LDS_FLOATS 20480u // 80 KiB per workgroup: two workgroups per CU (160 KiB)
 #define LW_RS_PASSES 8u // a tile stops growing at this many full passes of the workgroup
 

@@ -295,7 +295,13 @@ int lw_spec_rows(lw_spec *sp, int fmt, uint32_t ch, const void *d_src, size_t n_
 	a.pad_mode = (uint32_t)sp->pad_mode;
 	if (lw_stage_launch(n_src_rows, "lw_launch_spec", [&](uint32_t row0, uint32_t n) {
 		    a.row0 = row0;
-		    return lw_launch_spec(a, sp->route, (uint32_t)tiles, ch, n, st);
+		    for (uint64_t t0 = 0; t0 < tiles; t0 += LW_SP_MAX_TILES) { // (a grid dimension holds fewer than 2^32 lanes)
+			    a.tile0 = (uint32_t)t0;
+			    const hipError_t e = lw_launch_spec(a, sp->route, (uint32_t)std::min<uint64_t>(tiles - t0, LW_SP_MAX_TILES), ch, n, st);
+			    if (e != hipSuccess)
+				    return e;
+		    }
+		    return hipSuccess;
 	    }) < 0)
 		return LW_ERR_DEVICE;
 	if (int rc = staged.commit())

@@ -27,6 +27,9 @@ struct LwSpecLayout {
 // support, ascending) goes in tiles of LW_SP_KT staged through LDS.
 #define LW_SP_THREADS 256u
 #define LW_SP_TF 32u    // frames per workgroup: the N of the 32x32x2 matrix instruction
+#define LW_SP_MAX_TILES 0xffffffu // tiles of ONE launch: tiles * 256 lanes stays below 2^32, the most a grid dimension holds in lanes
+                                  // (a launch past it is accepted, and workgroups of it never run); a row with more
+                                  // tiles takes several launches, each with its tile0
 #define LW_SP_KT 16u    // support samples per staged tile
 #define LW_SP_COLS 256u // bins per pass: 4 waves x 2 tiles x 32
 #define LW_SP_XS 33u    // row stride of the staged frame tile [k][frame] (odd: the staging stores spread over the banks)
@@ -100,6 +103,7 @@ struct LwSpecArgs {
 	int64_t lead;                 // o - pad: sample 0 of frame t's SUPPORT is x[t * hop + lead]
 	uint32_t hop, win_length, k_pad, bins, passes, n_mels, mel_pad;
 	uint32_t row0; // first source row of this launch (blockIdx.z counts from it)
+	uint32_t tile0; // first tile of this launch (blockIdx.x counts from it)
 	uint32_t pad_mode; // LW_SPEC_PAD_ZERO / LW_SPEC_PAD_REFLECT / LW_SPEC_PAD_SYMMETRIC: what x[i] is outside [0, len)
 	// the per-frame prologue (k_spec<.., .., 1>); all zero: as before
 	uint32_t remove_dc; // x'_k = x_k - mu, mu the frame's mean
@@ -132,6 +136,6 @@ static inline int64_t lw_spec_kaldi_lead(uint32_t win_length, uint32_t hop, bool
 	return snip ? 0 : (int64_t)(hop / 2u) - (int64_t)(win_length / 2u);
 }
 
-// grid = (tiles of the row with the most frames, channels, rows of this launch <= 65535); a workgroup whose tile starts at or
-// behind its row's n_frames does nothing.  Nothing outside [0, n_frames) of a destination line is written.
+// grid = (tiles of this launch <= LW_SP_MAX_TILES, from a.tile0 on, channels, rows of this launch <= 65535); a workgroup whose
+// tile starts at or behind its row's n_frames does nothing.  Nothing outside [0, n_frames) of a destination line is written.
 hipError_t lw_launch_spec(const LwSpecArgs &a, int route, uint32_t tiles, uint32_t ch, uint32_t n_rows, hipStream_t st);

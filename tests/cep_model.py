@@ -123,3 +123,44 @@ def dct_reference(n_out, n_in, norm, lifter):
                 v *= 1.0 + (lifter / 2.0) * np.sin(np.pi * q / lifter)
             m[q, f] = v
     return m.astype(F32)
+
+
+def _delta_of(s, s_lo, lo, hi, T, N):
+    """the delta at frames [lo, hi) of lines s that hold frames [s_lo, s_lo + s.shape[1]) of a row of T frames"""
+    w = delta_weights(N)
+    acc = np.zeros((s.shape[0], hi - lo), F32)
+    for n in range(1, N + 1):
+        after = np.array([min(max(t + n, 0), T - 1) - s_lo for t in range(lo, hi)], np.int64)
+        before = np.array([min(max(t - n, 0), T - 1) - s_lo for t in range(lo, hi)], np.int64)
+        assert hi == lo or (min(after.min(), before.min()) >= 0 and max(after.max(), before.max()) < s.shape[1])
+        with np.errstate(over="ignore", invalid="ignore"):
+            d = s[:, after] - s[:, before]
+        assert d.dtype == F32
+        acc = fmaf(w[n - 1], d, acc)
+    return acc
+
+
+def window(row, a, b, T, fill_end, before, matrix, order, N):
+    """The window form of rows() for ONE row and channel that is +0.0 outside a few windows (tests/sparse_rows.py: row has n_in
+    lines of at least T frames): frames [a, b) of every destination line after the call, from `before` float32
+    [n_out * (1 + order)][b - a].  Each delta level is computed over the frames the next one refers to, the indices clamped into
+    [0, T - 1] in Python integers -- at the row's true ends, wherever the window lies"""
+    assert 0 <= a <= b and T <= fill_end
+    out = np.array(before, F32, copy=True)
+    lo, hi = min(a, T), min(b, T)
+    if hi > lo:
+        spans = [(lo, hi)]                                           # the frames level `order`, .., 0 must cover
+        for _ in range(order):
+            spans.append((max(0, spans[-1][0] - N), min(T, spans[-1][1] + N)))
+        spans.reverse()
+        s_lo, s_hi = spans[0]
+        level = static(row.clipped(T).take(s_lo, s_hi), matrix)
+        n_out = level.shape[0]
+        out[:n_out, lo - a:hi - a] = level[:, lo - s_lo:hi - s_lo]
+        for k in range(1, order + 1):
+            level, (s_lo, s_hi) = _delta_of(level, s_lo, spans[k][0], spans[k][1], T, N), spans[k]
+            out[k * n_out:(k + 1) * n_out, lo - a:hi - a] = level[:, lo - s_lo:hi - s_lo]
+    f0, f1 = min(max(a, T), fill_end), min(b, fill_end)
+    if f1 > f0:
+        out[:, f0 - a:f1 - a] = 0.0
+    return out

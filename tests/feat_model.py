@@ -124,3 +124,35 @@ def source(n_frames, ch, F, cap, floor, seed, inf_row=None):
             v[0, F - 1, n // 2] = np.inf
         x[r, :, :, :n] = v
     return x
+
+
+def window(row, C, F, a, b, n, fill_end, before, kind=LOG10, scope=ROW, floor=1e-10, top=8.0, add=4.0, mul=0.25):
+    """The window form of rows() for ONE row that is +0.0 outside a few windows (tests/sparse_rows.py: row has C * F lines,
+    channel-major, of at least n elements): positions [a, b) of every line of the destination after the call, from `before`
+    float32 [C][F][b - a], what they held before it.  The maximum is taken over every element of the row: the windows' values, and
+    what x = +0.0 gives wherever the row has an element outside them.  Returns (after, M as float32 [] or [C])"""
+    assert row.lines == C * F and 0 <= a <= b and n <= fill_end
+    floor = F32(floor)
+    l0 = log(kind, np.array([floor], F32))[0]
+    src = row.clipped(n)
+
+    def step12(x):
+        with np.errstate(invalid="ignore"):
+            return log(kind, np.where(x > floor, x, floor).astype(F32))
+    l = step12(src.values()).reshape(C, F, -1)
+    rest = step12(np.zeros(1, F32)) if src.covered() < n else np.zeros(0, F32)
+    if n == 0:
+        Ms = np.full((C,), l0, F32)
+    elif scope == ROW:
+        Ms = np.full((C,), total_max(np.concatenate([l.ravel(), rest])), F32)
+    else:
+        Ms = np.array([total_max(np.concatenate([l[c].ravel(), rest])) for c in range(C)], F32)
+    out = np.array(before, F32, copy=True).reshape(C, F, b - a)
+    lo, hi = min(a, n), min(b, n)
+    x = src.take(lo, hi).reshape(C, F, hi - lo)
+    for c in range(C):
+        out[c, :, lo - a:hi - a] = finish(step12(x[c]), Ms[c], top, add, mul)
+        f0, f1 = min(max(a, n), fill_end), min(b, fill_end)
+        if f1 > f0:
+            out[c, :, f0 - a:f1 - a] = finish(np.array([l0], F32), Ms[c], top, add, mul)[0]
+    return out, (Ms[0] if scope == ROW else Ms)

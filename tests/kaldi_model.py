@@ -202,3 +202,14 @@ def bound(basis, fb, Xp, mu, re, im, lin, energy, scale=1.0):
         m, dm = np.concatenate([E, m], axis=1), np.concatenate([U * E + 2.0 ** -40 * S2, dm], axis=1)
     l = np.log(np.maximum(m, F64(EPS)))
     return dm / np.maximum(m - dm, F64(EPS)) + 2 * U * np.maximum(np.abs(l), 1.0)
+
+
+def frame_matrix_window(row, a, b, W, hop, snip):
+    """The window form of frame_matrix for a row that is +0.0 outside a few windows (tests/sparse_rows.py: one line, row.n its
+    len): frames [a, b), every index by sym_index's rule at the row's true ends"""
+    n = row.n
+    assert accepted(n, W, hop, snip) and 0 <= a <= b <= n_frames(n, W, hop, snip)
+    i = (np.arange(a, b, dtype=np.int64) * hop + first_index(0, W, hop, snip))[:, None] + np.arange(W, dtype=np.int64)[None, :]
+    i = np.where(i < 0, -i - 1, i)
+    i = np.where(i >= n, 2 * n - 1 - i, i)
+    return row.gather(i)[0]

@@ -154,3 +154,51 @@ def source(n, ch, F, cap, seed, offset=0.0, special=False):
             v[pick] = odd[rng.integers(0, r % (len(odd) + 1), int(pick.sum()))]
         x[r, :, :, :k] = v
     return x
+
+
+def exact_sums(values):
+    """(S1, S2, P) of float32 values that are integers / 1024 of magnitude at most 1024, in Python integers: both sums are
+    exactly representable in float64 and every partial sum of any bracketing is too, so the contract's tree gives these bits
+    whatever its shape.  Zeros add nothing: a row that is +0.0 outside its windows has the sums of its windows"""
+    v = np.asarray(values, F32).ravel()
+    k = v.astype(F64) * 1024.0
+    assert np.array_equal(k, np.rint(k)) and (np.abs(k) <= 1 << 20).all(), "values must be integers / 1024"
+    ints = [int(i) for i in k]
+    s1, s2 = sum(ints), sum(i * i for i in ints)
+    assert abs(s1) < 1 << 53 and s2 < 1 << 53
+    P = (v.view(np.uint32) & np.uint32(0x7FFFFFFF)).max().view(F32) if len(v) else F32(0)
+    return float(s1) / 1024.0, float(s2) / float(1 << 20), P
+
+
+def window(row, C, F, a, b, n, fill_end, before, center=1, scale=STD, scope=ROW, eps=1e-7, target=1.0, scalars_of=None):
+    """The window form of rows() for ONE row that is +0.0 outside a few windows (tests/sparse_rows.py: row has C * F lines,
+    channel-major, of at least n elements, its values integers / 1024): positions [a, b) of every line of the destination after
+    the call, from `before` float32 [C][F][b - a].  S1, S2 and P are exact_sums of the windows, N the scope's lines times n.
+    scalars_of(S1, S2, P, N) -> (m, g): step 3 (None: scalars() above).  Returns (after, stats float64 [], [C] or [C][F] + [2])"""
+    assert row.lines == C * F and 0 <= a <= b and n <= fill_end
+    src = row.clipped(n)
+    vals = src.values().reshape(C, F, -1)
+    stats = np.zeros((C, F, 2), F64)
+    groups = [[(c, l) for c in range(C) for l in range(F)]] if scope == ROW else \
+        [[(c, l) for l in range(F)] for c in range(C)] if scope == CHANNEL else [[(c, l)] for c in range(C) for l in range(F)]
+    for grp in groups:
+        if n == 0:
+            m, g = 0.0, 1.0
+        else:
+            S1, S2, P = exact_sums(np.concatenate([vals[c, l] for c, l in grp]))
+            if scalars_of is None:
+                m, g = (float(v) for v in scalars(center, scale, eps, target, S1, S2, P, len(grp) * n))
+            else:
+                m, g = scalars_of(S1, S2, P, len(grp) * n)
+        for c, l in grp:
+            stats[c, l] = m, g
+    out = np.array(before, F32, copy=True).reshape(C, F, b - a)
+    lo, hi = min(a, n), min(b, n)
+    x = src.take(lo, hi).reshape(C, F, hi - lo)
+    for c in range(C):
+        for l in range(F):
+            out[c, l, lo - a:hi - a] = apply(x[c, l], stats[c, l, 0], stats[c, l, 1])
+    f0, f1 = min(max(a, n), fill_end), min(b, fill_end)
+    if f1 > f0:
+        out[:, :, f0 - a:f1 - a] = 0.0
+    return out, (stats[0, 0] if scope == ROW else stats[:, 0] if scope == CHANNEL else stats)

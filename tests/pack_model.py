@@ -193,3 +193,36 @@ SPECIAL_BITS = [0x00000000, 0x80000000, 0x00000001, 0x807FFFFF, 0x00800000, 0x7F
                 0x32FFFFFF, 0xB3000000, 0x33C00000, 0x33800000, 0x34400000, 0x387FC000, 0x387FE000, 0x387FF000, 0x38800000, 0x38801000,
                 0x3F808000, 0x3F818000, 0x3F808001, 0x3F807FFF, 0xBF808000, 0x3F800000, 0x7F7F8000, 0x7F7F7FFF]
 SPECIALS = np.array(SPECIAL_BITS, np.uint32).view(F32)
+
+
+def window(row, a, b, T, fill_end, before, mask_before, left, right, stride, edge, dtype, shift=None, scale=None, pad=0.0):
+    """The window form of rows() for ONE row and channel that is +0.0 outside a few windows (tests/sparse_rows.py: row has F lines
+    of at least T frames): output frames [a, b) after the call, from `before` (bit patterns [b - a][W * F]) and mask_before (uint8
+    [b - a], or None).  The source frames and the clamp at the row's true ends in Python integers.  Returns (after, mask)"""
+    W, F = left + right + 1, row.lines
+    k = out_frames(T, left, right, stride, edge)
+    assert 0 <= a <= b and k <= fill_end
+    out = np.array(before, copy=True)
+    msk = None if mask_before is None else np.array(mask_before, copy=True)
+    lo, hi = min(a, k), min(b, k)
+    if hi > lo:
+        if edge == VALID:
+            idx = [[u * stride + j for j in range(W)] for u in range(lo, hi)]
+        else:
+            idx = [[min(max(u * stride - left + j, 0), T - 1) for j in range(W)] for u in range(lo, hi)]
+        v = np.ascontiguousarray(row.clipped(T).gather(np.array(idx, np.int64)).transpose(1, 2, 0)).reshape(hi - lo, W * F)   # [u][k][f]
+        with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+            if shift is not None:
+                v = v + np.asarray(shift, F32)[None, :]
+            if scale is not None:
+                v = v * np.asarray(scale, F32)[None, :]
+        assert v.dtype == F32
+        out[lo - a:hi - a] = convert(v, dtype)
+        if msk is not None:
+            msk[lo - a:hi - a] = 1
+    f0, f1 = min(max(a, k), fill_end), min(b, fill_end)
+    if f1 > f0:
+        out[f0 - a:f1 - a] = convert(np.array([pad], F32), dtype)[0]
+        if msk is not None:
+            msk[f0 - a:f1 - a] = 0
+    return out, msk

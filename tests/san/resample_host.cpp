@@ -28,6 +28,7 @@
 static int g_launches = 0;
 static std::vector<std::pair<const LwResampleRow *, uint32_t>> g_rows; // what each launch was given, looked at again at the end
 static bool g_run = true;
+static std::vector<std::pair<uint32_t, uint32_t>> g_tiles; // (tile0, tiles) of each launch
 
 template <int ROUTE, int J> static void run_tile(const LwResampleArgs &a, const LwResamplePlan &p, uint32_t bx, uint32_t by, uint32_t bz)
 {
@@ -53,7 +54,8 @@ hipError_t lw_launch_resample(const LwResampleArgs &a, const LwResamplePlan &p, 
 {
 	g_launches++;
 	g_rows.emplace_back(a.rows + a.row0, n_rows);
-	if (!a.rows || !a.taps || p.lds_floats > LW_RS_LDS_FLOATS || p.blocks != a.blocks || ch == 0 || n_rows > 65535u) {
+	g_tiles.emplace_back(a.tile0, tiles);
+	if (!a.rows || !a.taps || p.lds_floats > LW_RS_LDS_FLOATS || p.blocks != a.blocks || ch == 0 || n_rows > 65535u || tiles > LW_RS_MAX_TILES) {
 		printf("BAD arguments\n");
 		exit(3);
 	}
@@ -344,12 +346,23 @@ int main(int argc, char **argv)
 			map[2] = 2;
 		else if (cs == "row_twice_empty")
 			map[1] = 3; // the row without samples names a row another one has
-		else if (cs != "ok" && cs != "ok_exact")
+		else if (cs == "ok_many_tiles") {
+			// one row of 2^37 outputs: more tiles than one launch holds, whatever the plan's tile (nothing runs here, no sample is touched)
+			g_run = false;
+			dc = (size_t)1 << 37, len[0] = sc = ((size_t)1 << 37) / 160 * 441, len[1] = len[2] = 0;
+		} else if (cs != "ok" && cs != "ok_exact")
 			return 2;
 		if (cs == "ok_exact")
 			dc = 363, sc = 1000;
 		const int rc = lw_resample_rows(h, fmt, ch, s, 3, sc, l, mp, d, n_dst, dc, nullptr);
 		printf("RC %d\nLAUNCHES %d\n", rc, g_launches);
+		if (cs == "ok_many_tiles") {
+			uint32_t orig, new_, hw, k;
+			lw_resampler_geometry(rs, &orig, &new_, &hw, &k);
+			printf("TILE %u\n", lw_resample_plan(orig, new_, k, 1).tile);
+			for (const auto &g : g_tiles)
+				printf("TILES %u %u\n", g.first, g.second);
+		}
 	} else {
 		return 2;
 	}

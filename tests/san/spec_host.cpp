@@ -30,6 +30,7 @@
 static int g_launches = 0;
 static std::vector<std::pair<const LwSpecRow *, uint32_t>> g_rows; // what each launch was given, looked at again at the end
 static bool g_run = true;
+static std::vector<std::pair<uint32_t, uint32_t>> g_tiles; // (tile0, tiles) of each launch
 
 bool lw_hip_ok(hipError_t e, const char *) // (lw_runtime.cpp's, without its thread-local text)
 {
@@ -81,7 +82,9 @@ hipError_t lw_launch_spec(const LwSpecArgs &a, int route, uint32_t tiles, uint32
 {
 	g_launches++;
 	g_rows.emplace_back(a.rows + a.row0, n_rows);
-	if (!a.rows || !a.basis || (a.n_mels && !a.fb) || (route != 0 && route != 1) || ch == 0 || n_rows > 65535u || a.k_pad % LW_SP_KT || a.mel_pad % 32u) {
+	g_tiles.emplace_back(a.tile0, tiles);
+	if (!a.rows || !a.basis || (a.n_mels && !a.fb) || (route != 0 && route != 1) || ch == 0 || n_rows > 65535u || a.k_pad % LW_SP_KT || a.mel_pad % 32u ||
+			tiles > LW_SP_MAX_TILES) {
 		printf("BAD arguments\n");
 		exit(3);
 	}
@@ -407,6 +410,9 @@ int main(int argc, char **argv)
 			printf("RC %d\nLAUNCHES %d\n", lw_spec_set_route(sp, 2), g_launches);
 			lw_spec_destroy(sp);
 			return 0;
+		} else if (cs == "ok_many_tiles") {
+			// one row of 2^30 + 1 frames: 2^25 + 1 tiles, more than one launch holds (nothing runs here, and no sample is touched)
+			len[0] = sc = (size_t)160 << 30, len[1] = len[2] = 0, fc = ((size_t)1 << 30) + 1;
 		} else if (cs != "ok" && cs != "ok_exact" && cs != "ok_route1")
 			return 2;
 		if (cs == "ok_exact")
@@ -415,6 +421,9 @@ int main(int argc, char **argv)
 			return 3;
 		const int rc = lw_spec_rows(h, fmt, ch, s, 3, sc, l, mp, d, n_dst, fc, nullptr);
 		printf("RC %d\nLAUNCHES %d\n", rc, g_launches);
+		if (cs == "ok_many_tiles")
+			for (const auto &g : g_tiles)
+				printf("TILES %u %u\n", g.first, g.second);
 		if (rc == LW_OK && lw_spec_last_route(sp) != (cs == "ok_route1" ? 1 : 0))
 			return 3;
 	} else {

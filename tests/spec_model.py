@@ -75,3 +75,14 @@ def same_bits(got, want):
     w[w == 0x80000000] = 0
     same = g == w
     assert same.all(), (int((~same).sum()), np.argwhere(~same)[:4].tolist())
+
+
+def frame_matrix_window(row, a, b, n_fft, win_length, hop, center):
+    """The window form of frame_matrix for a row that is +0.0 outside a few windows (tests/sparse_rows.py: one line, row.n its
+    len): frames [a, b), float32 [b - a][win_length], +0.0 outside [0, len) at the row's true ends"""
+    L = row.n
+    assert 0 <= a <= b <= n_frames(L, n_fft, hop, center)
+    o, pad = (n_fft - win_length) // 2, (n_fft // 2 if center else 0)
+    idx = np.arange(a, b, dtype=np.int64)[:, None] * hop - pad + o + np.arange(win_length, dtype=np.int64)[None, :]
+    inside = (idx >= 0) & (idx < L)
+    return np.where(inside, row.gather(np.where(inside, idx, 0))[0], np.float32(0.0)).astype(np.float32)

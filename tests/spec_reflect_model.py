@@ -31,3 +31,15 @@ def frame_matrix(x, n_fft, win_length, hop):
     X = M.frame_matrix(np.pad(x, (pad, n_fft - pad), "reflect"), n_fft, win_length, hop, False)
     assert len(X) == 1 + len(x) // hop
     return X
+
+
+def frame_matrix_window(row, a, b, n_fft, win_length, hop):
+    """The window form of frame_matrix for a row that is +0.0 outside a few windows (tests/sparse_rows.py: one line, row.n its
+    len): frames [a, b) of the 1 + len // hop, every index reflected at the row's true ends as index() does"""
+    L = row.n
+    assert L >= min_len(n_fft) and 0 <= a <= b <= 1 + L // hop
+    o = (n_fft - win_length) // 2
+    i = np.arange(a, b, dtype=np.int64)[:, None] * hop - n_fft // 2 + o + np.arange(win_length, dtype=np.int64)[None, :]
+    i = np.where(i < 0, -i, i)
+    i = np.where(i >= L, 2 * (L - 1) - i, i)
+    return row.gather(i)[0]

@@ -1,5 +1,5 @@
 """k_pack past element 2^32 of its source and of its destination on the GPU (-m gpu): offsets no other test of FramePack reaches,
-one case per dtype.
+through the row (one case per dtype), the channel and the line index.
 
 The cases are in tests/rows_pack_large_gpu_cases.py and run ONCE, with pytest, in a process of their own that imports torch first
 (tests/test_gpu_rows.py says why); that process holds up to 51.6 GB of device memory.  Each test below stands for one group of
@@ -17,7 +17,7 @@ from common import ROOT
 pytestmark = pytest.mark.gpu
 
 CASES = os.path.join(ROOT, "tests", "rows_pack_large_gpu_cases.py")
-GROUPS = ["test_k_pack_past_2_to_the_32"]
+GROUPS = ["test_k_pack_past_2_to_the_32", "test_k_pack_channel_and_line_past_2_to_the_32"]
 
 
 @pytest.fixture(scope="module")

@@ -207,6 +207,21 @@ def test_exactly_full_is_accepted(harness):
     assert _run(harness, "refuse", "ok_exact") == ["RC 0", "LAUNCHES 1"]    # len == src_capacity, out_len == dst_capacity
 
 
+def test_a_row_of_more_tiles_than_a_launch_holds_takes_several(harness):
+    """a grid dimension holds fewer than 2^32 lanes, 2^23 - 1 workgroups of 512 (a launch past that is accepted, and workgroups of
+    it never run: k_spec left rows unwritten under LW_OK that way, tests/test_host_spec.py).  The tiles of a row of nearly
+    2^37 outputs go out in launches of at most 2^23 - 1, each with its tile0, and cover the row exactly once"""
+    out = _run(harness, "refuse", "ok_many_tiles")
+    assert out[0] == "RC 0"
+    launches, tile = int(out[1].split()[1]), int(out[2].split()[1])
+    tiles = [tuple(int(v) for v in line.split()[1:]) for line in out[3:]]
+    outputs = (1 << 37) // 160 * 160                                      # out_len of (2^37 // 160) * 441 samples at 441 -> 160
+    most = (1 << 23) - 1
+    want = -(-outputs // tile)
+    assert launches == len(tiles) == -(-want // most) > 1 and tile % 160 == 0
+    assert tiles == [(t0, min(most, want - t0)) for t0 in range(0, want, most)] and all(n * 512 < 1 << 32 for _, n in tiles)
+
+
 def test_two_calls_back_to_back_each_reach_their_own_lengths(harness):
     """the second call's records do not replace the first's, which its kernel reads later; the caller's array is free at once"""
     out = _run(harness, "two")

@@ -159,6 +159,17 @@ def test_exactly_full_is_accepted_on_both_routes(harness):
         assert _run(harness, "refuse", case) == ["RC 0", "LAUNCHES 1"]
 
 
+def test_a_row_of_more_tiles_than_a_launch_holds_takes_several(harness):
+    """2^30 + 1 frames are 2^25 + 1 tiles of 32; a grid dimension holds fewer than 2^32 lanes, 2^24 - 1 workgroups of 256 (a launch
+    past that is accepted, and workgroups of it never run: tests/rows_long_row_gpu_cases.py found frames left unwritten under
+    LW_OK).  The tiles go out in launches of at most 2^24 - 1, each with its tile0, and cover the row exactly once"""
+    out = _run(harness, "refuse", "ok_many_tiles")
+    assert out[:2] == ["RC 0", "LAUNCHES 3"]
+    tiles = [tuple(int(v) for v in line.split()[1:]) for line in out[2:]]
+    assert tiles == [(0, 0xFFFFFF), (0xFFFFFF, 0xFFFFFF), (2 * 0xFFFFFF, 3)]
+    assert sum(n for _, n in tiles) == -(-((1 << 30) + 1) // 32) and all(n * 256 < 1 << 32 for _, n in tiles)
+
+
 def test_two_calls_back_to_back_each_reach_their_own_lengths(harness):
     """the second call's records do not replace the first's, which its kernel reads later; the caller's array is free at once"""
     out = _run(harness, "two")
