@@ -439,6 +439,11 @@ int lw_resampler_set_taps_in_lds(lw_resampler *rs, int on);
  *           one rounding; Ed = 0 if !(Ed > 0);  E = (float)(Ed * (scale * scale)).  With energy, E is line 0 of the
  *           destination and the spectrum or mel lines follow from line 1: F = lw_spec_features counts it.  (Kaldi's
  *           raw_energy = true and column order without htk_compat; the logarithm is lw_feat_rows' business.)
+ *   output    LW_SPEC_OUT_POWER (0): the rule above.  LW_SPEC_OUT_COMPLEX: F = 2 B; line j < B is re[j] and line B + j is im[j],
+ *           the two chains of "spectrum" themselves, stored without forming P -- what torch.stft returns, split into planes,
+ *           and what lw_istft_rows reads.  Not with n_mels > 0, remove_dc or energy (LW_ERR_UNSUPPORTED); pre-emphasis, scale,
+ *           every window, framing and pad mode stay (they live in the table or in x).  The sign of a zero and which NaN a NaN
+ *           is stay outside the contract, every other bit is inside it.
  *
  * lw_spec_rows: source row i (len[i] samples per channel) goes to destination row dst_row[i] (NULL: row i).  len and dst_row
  * are HOST arrays, copied during the call.  Asynchronous on hip_stream; calls on one object may be queued back to back.
@@ -446,7 +451,8 @@ int lw_resampler_set_taps_in_lds(lw_resampler *rs, int on);
  *   LW_ERR_NULL_ARG     sp NULL, len NULL with rows, d_src / d_dst NULL with frames to compute; (create) fb NULL with n_mels > 0
  *   LW_ERR_UNSUPPORTED  (create) a parameter outside the limits above, an unknown window or framing, center with a Kaldi framing,
  *                       a symmetric window with win_length < 2, preemphasis outside [0, 1] or NaN, scale not finite or <= 0,
- *                       remove_dc or energy other than 0 or 1, reserved != 0;  (rows) an i16 format;
+ *                       remove_dc or energy other than 0 or 1, reserved != 0, an unknown output, LW_SPEC_OUT_COMPLEX with
+ *                       n_mels > 0, remove_dc or energy;  (rows) an i16 format;
  *                       (set_pad_mode) an unknown mode, reflect on an object that is not centred, any mode on a Kaldi-framed object
  *   LW_ERR_DEVICE       (create) no such device, or its LDS per workgroup is below the 67 648 bytes k_spec needs (asked of the
  *                       device, not assumed)
@@ -456,6 +462,7 @@ int lw_resampler_set_taps_in_lds(lw_resampler *rs, int on);
 typedef struct lw_spec lw_spec;
 enum { LW_SPEC_HANN = 0, LW_SPEC_RECT = 1, LW_SPEC_POVEY = 2, LW_SPEC_HAMMING = 3, LW_SPEC_HANN_SYM = 4, LW_SPEC_BLACKMAN = 5 };
 enum { LW_SPEC_FRAMES_STFT = 0, LW_SPEC_FRAMES_KALDI_SNIP = 1, LW_SPEC_FRAMES_KALDI_EDGES = 2 };
+enum { LW_SPEC_OUT_POWER = 0, LW_SPEC_OUT_COMPLEX = 1 };
 #define LW_SPEC_MAX_FFT 2048
 #define LW_SPEC_MAX_MELS 256
 typedef struct lw_spec_params {
@@ -469,6 +476,7 @@ typedef struct lw_spec_params {
 	uint32_t reserved;  /* must be 0 */
 	double preemphasis; /* in [0, 1] */
 	double scale;       /* finite, > 0 */
+	int32_t output;     /* LW_SPEC_OUT_*; 0 (a zeroed struct, and every struct written before the field existed) is the power */
 } lw_spec_params;
 lw_spec *lw_spec_create(int device, uint32_t n_fft, uint32_t win_length, uint32_t hop, int window, int center, uint32_t n_mels,
 		const float *fb, int *err);
@@ -491,6 +499,75 @@ int lw_spec_set_route(lw_spec *sp, int route);
 enum { LW_SPEC_PAD_ZERO = 0, LW_SPEC_PAD_REFLECT = 1, LW_SPEC_PAD_SYMMETRIC = 2 /* LW_SPEC_FRAMES_KALDI_EDGES' own, never set */ };
 int lw_spec_set_pad_mode(lw_spec *sp, int mode);
 int lw_spec_pad_mode(const lw_spec *sp);
+
+/* ---- inverse spectral frames of rows -------------------------------------------------------------------------------------
+ * Complex spectral frames -> rows of f32 PCM, on the GPU, as a pass of its own (k_istft): the way back from a model that works
+ * on the complex STFT (enhancement, separation, vocoder front ends), torch.istft.  The source is f32 [row][ch][2 B][frame_capacity],
+ * what lw_spec_rows writes under LW_SPEC_OUT_COMPLEX (line j < B is re[j], line B + j is im[j]); the destination is a rows buffer
+ * of either f32 format.  A contract on BITS.
+ *
+ * A lw_istft is made from the n_fft, win_length, hop, window and center of a lw_istft_params: STFT framing, the ranges and windows of
+ * lw_spec, and hop <= win_length (else there are gaps no frame covers) and ov = ceil(win_length / hop) <= LW_ISTFT_MAX_OVERLAP.
+ * With B = n_fft / 2 + 1, o = (n_fft - win_length) / 2, pad = center ? n_fft / 2 : 0 (integer divisions), T the row's frame
+ * count and P = T == 0 ? 0 : n_fft + (T - 1) * hop:
+ *   table   G[l][k], 0 <= l < 2 B, 0 <= k < win_length, evaluated in double and rounded ONCE to f32; w as lw_spec evaluates it.
+ *           a = 2 pi (((k + o) * j) mod n_fft) / n_fft (reduced in integers first); c_j = 1 for j == 0 and, when n_fft is even,
+ *           for j == n_fft / 2, else 2.  Line l = j < B: G = w[k] * c_j * cos(a) / n_fft.  Line l = B + j: G = -(w[k] * c_j *
+ *           sin(a)) / n_fft, but +0.0 exactly for j == 0 and for the even-n_fft Nyquist bin: irfft ignores those imaginary
+ *           parts, and so does this.  lw_istft_basis returns the table, [2 B][win_length].
+ *   frame   y_t[k]: acc = +0.0; for l = 0 .. 2 B - 1 ascending acc = fmaf(X[l][t], G[l][k], acc): ONE chain over the source's own
+ *           line order, never split.  Dense: a zero weight takes part like any other (an Inf in an ignored imaginary part
+ *           gives NaN).
+ *   add     in padded coordinates p.  xh[p]: acc = +0.0; for every frame t in [0, T) with 0 <= p - t * hop - o < win_length, in
+ *           ASCENDING t, acc = acc + y_t[p - t * hop - o], one rounded f32 add each (the fold starts at +0.0: a zero's sign
+ *           cannot reach the result).
+ *   env     env[p]: the same fold in double, over the same frames in the same order, of w2[k] = w[k] * w[k] (w in double; the
+ *           product one rounding, each add one rounding).  lw_istft_window2 returns w2.
+ *   output  sample n of the row is p = n + pad.  out[n] = (float)((double)xh[p] / env[p]) when p < P and env[p] > 1e-11 (the
+ *           double literal), else +0.0: one double division, one rounding to f32.  (torch.istft raises where the envelope is
+ *           small; here the sample has a defined value.)
+ *   length  out_len[i] is the caller's wish, as torch.istft(length=): it may pass the natural length
+ *           lw_istft_out_len(is, T) = T == 0 ? 0 : P - 2 * pad, and the samples behind what the frames cover are +0.0.
+ *           out_len == NULL: the natural lengths.  Exactly [0, out_len[i]) of every destination row and channel is written.
+ *   bits    p, t * hop and every element offset are 64-bit.  Which NaN a NaN is stays outside the contract; all else is a bit.
+ *
+ * lw_istft_rows: source row i (frames[i] frames) goes to destination row dst_row[i] (NULL: row i).  frames, dst_row and out_len
+ * are HOST arrays, copied during the call.  Asynchronous on hip_stream; calls on one object may be queued back to back.
+ * Refusals, decided on the host before anything is queued, so a refused call has written nothing:
+ *   LW_ERR_NULL_ARG     is NULL, frames NULL with rows, d_dst NULL with samples to write, d_src NULL with frames to read;
+ *                       (create) the params NULL
+ *   LW_ERR_UNSUPPORTED  (create) a parameter outside lw_spec's limits, an unknown window, center other than 0 or 1,
+ *                       hop > win_length, ov > LW_ISTFT_MAX_OVERLAP, reserved != 0;  (rows) an i16 format;
+ *                       (set_route, set_tile_frames) a value the object does not have
+ *   LW_ERR_DEVICE       (create) no such device, or its LDS per workgroup is below the 80 896 bytes k_istft needs (asked of the
+ *                       device, not assumed)
+ *   LW_ERR_CAPACITY     frames[i] > frame_capacity, out_len[i] > dst_capacity, dst_row[i] >= n_dst_rows, two source rows for one
+ *                       destination row, ch == 0 or > 255, a buffer not addressable in 64 bits of bytes */
+typedef struct lw_istft lw_istft;
+#define LW_ISTFT_MAX_OVERLAP 16
+typedef struct lw_istft_params {
+	uint32_t n_fft, win_length, hop;
+	int32_t window;    /* LW_SPEC_HANN ... LW_SPEC_BLACKMAN: the analysis window, which is the synthesis window */
+	int32_t center;    /* 0 or 1 */
+	uint32_t reserved; /* must be 0 */
+} lw_istft_params;
+lw_istft *lw_istft_create(int device, const lw_istft_params *p, int *err);
+void lw_istft_destroy(lw_istft *is);
+uint32_t lw_istft_bins(const lw_istft *is);                       /* B; the source has 2 B lines */
+uint64_t lw_istft_out_len(const lw_istft *is, uint64_t frames);   /* the natural length of a row of `frames` frames */
+size_t lw_istft_basis(const lw_istft *is, float *dst);            /* [2 B][win_length]; returns the count, dst NULL = size query */
+size_t lw_istft_window2(const lw_istft *is, double *dst);         /* [win_length] doubles, likewise */
+int lw_istft_rows(lw_istft *is, uint32_t ch, const void *d_src, size_t n_src_rows, size_t frame_capacity, const uint64_t *frames,
+		const uint32_t *dst_row, const uint64_t *out_len, int fmt, void *d_dst, size_t n_dst_rows, size_t dst_capacity, void *hip_stream);
+/* routes: 0 = the frame signals on the matrix cores (v_mfma_f32_32x32x2_f32), 1 = the same kernel body with per-lane fmaf
+ * chains; both give the same bits.  lw_istft_last_route: the route of the last queued call, -1 = no call yet. */
+int lw_istft_last_route(const lw_istft *is);
+int lw_istft_set_route(lw_istft *is, int route);
+/* A workgroup owns m * hop consecutive padded samples and recomputes the frames that reach into them, so m never reaches a
+ * bit.  lw_istft_tile_frames: the object's m.  lw_istft_set_tile_frames (debug: a test runs two values and demands identical
+ * bits): 1 <= m <= the m the object was created with, else LW_ERR_UNSUPPORTED. */
+uint32_t lw_istft_tile_frames(const lw_istft *is);
+int lw_istft_set_tile_frames(lw_istft *is, uint32_t m);
 
 /* ---- finishing feature rows ------------------------------------------------------------------------------------------------
  * Log compression, dynamic-range clamp, affine map and fill of finished feature rows, on the GPU, as a pass of its own (k_feat):

@@ -60,7 +60,12 @@ class FeatParams(C.Structure):
 class SpecParams(C.Structure):
     _fields_ = [("n_fft", C.c_uint32), ("win_length", C.c_uint32), ("hop", C.c_uint32), ("n_mels", C.c_uint32), ("fb", C.c_void_p),
                 ("window", C.c_int32), ("center", C.c_int32), ("framing", C.c_int32), ("remove_dc", C.c_int32), ("energy", C.c_int32),
-                ("reserved", C.c_uint32), ("preemphasis", C.c_double), ("scale", C.c_double)]
+                ("reserved", C.c_uint32), ("preemphasis", C.c_double), ("scale", C.c_double), ("output", C.c_int32)]
+
+
+class IstftParams(C.Structure):
+    _fields_ = [("n_fft", C.c_uint32), ("win_length", C.c_uint32), ("hop", C.c_uint32), ("window", C.c_int32), ("center", C.c_int32),
+                ("reserved", C.c_uint32)]
 
 
 class NormParams(C.Structure):
@@ -187,6 +192,18 @@ SYMBOLS = {
     "lw_spec_set_route": (C.c_int, [C.c_void_p, C.c_int]),
     "lw_spec_set_pad_mode": (C.c_int, [C.c_void_p, C.c_int]),
     "lw_spec_pad_mode": (C.c_int, [C.c_void_p]),
+    "lw_istft_create": (C.c_void_p, [C.c_int, C.POINTER(IstftParams), intp]),
+    "lw_istft_destroy": (None, [C.c_void_p]),
+    "lw_istft_bins": (C.c_uint32, [C.c_void_p]),
+    "lw_istft_out_len": (C.c_uint64, [C.c_void_p, C.c_uint64]),
+    "lw_istft_basis": (C.c_size_t, [C.c_void_p, C.c_void_p]),
+    "lw_istft_window2": (C.c_size_t, [C.c_void_p, C.c_void_p]),
+    "lw_istft_rows": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]),
+    "lw_istft_last_route": (C.c_int, [C.c_void_p]),
+    "lw_istft_set_route": (C.c_int, [C.c_void_p, C.c_int]),
+    "lw_istft_tile_frames": (C.c_uint32, [C.c_void_p]),
+    "lw_istft_set_tile_frames": (C.c_int, [C.c_void_p, C.c_uint32]),
     "lw_feat_create": (C.c_void_p, [C.c_int, C.POINTER(FeatParams), intp]),
     "lw_feat_destroy": (None, [C.c_void_p]),
     "lw_feat_log": (C.c_float, [C.c_void_p, C.c_float]),

@@ -28,6 +28,8 @@
 //   power  P of the pass goes to LDS as [bin][frame].  Without a mel matrix it is stored from there; with one, every lane keeps
 //          the accumulators of ONE frame and up to 32 mel bands in registers over all passes and folds P[j] in ascending j, the
 //          matrix slice [32 j][mel_pad] staged where the basis tile was (vector fmaf: a tenth of the arithmetic).
+//   complex  (LW_SPEC_OUT_COMPLEX, k_spec_complex) re of the pass goes through the same LDS region to the lines [0, B), then im
+//          to the lines [B, 2B): the accumulators as they are, P never formed.
 // Route 1 (LW_SP_ROUTE_FMA) is the same body with the matrix instruction replaced by per-lane fmaf chains over the same LDS
 // tiles and the same register layout: the fall-back, the second witness for the bits, and what tests/san/spec_host.cpp compiles
 // for the host (LW_SPEC_HOST) and runs lane by lane.
@@ -242,11 +244,10 @@ LW_SP_FN void lw_sp_power(const LwSpecArgs &a, uint32_t pass, uint32_t tid, floa
 	}
 }
 
-// ---- without a mel matrix: the pass's bins from LDS to their lines, consecutive lanes on consecutive frames
-// (PRO: the lines follow the energy line when there is one)
-template <int PRO = 0> LW_SP_FN void lw_sp_store_power(const LwSpecArgs &a, const LwSpTile &t, uint32_t pass, uint32_t tid, const float *lds)
+// ---- the pass's bins from the P region of LDS to the lines line0 + bin, consecutive lanes on consecutive frames
+LW_SP_FN void lw_sp_store_lines(const LwSpecArgs &a, const LwSpTile &t, uint32_t pass, uint32_t tid, const float *lds, uint32_t line0)
 {
-	const uint32_t f = tid % LW_SP_TF, line0 = PRO ? a.energy : 0u;
+	const uint32_t f = tid % LW_SP_TF;
 	if (t.f0 + f >= t.n_frames)
 		return;
 	for (uint32_t c = tid / LW_SP_TF; c < LW_SP_COLS; c += LW_SP_THREADS / LW_SP_TF) {
@@ -254,6 +255,28 @@ template <int PRO = 0> LW_SP_FN void lw_sp_store_power(const LwSpecArgs &a, cons
 		if (bin >= a.bins)
 			break;
 		a.dst[t.d_at + (uint64_t)(bin + line0) * a.d_line + t.f0 + f] = lds[LW_SP_LDS_P + c * LW_SP_TF + f];
+	}
+}
+
+// ---- without a mel matrix: the power (PRO: the lines follow the energy line when there is one)
+template <int PRO = 0> LW_SP_FN void lw_sp_store_power(const LwSpecArgs &a, const LwSpTile &t, uint32_t pass, uint32_t tid, const float *lds)
+{
+	lw_sp_store_lines(a, t, pass, tid, lds, PRO ? a.energy : 0u);
+}
+
+// ---- complex output (LW_SPEC_OUT_COMPLEX; OUT = 1 in the kernel): re (SINE = 0) or im (SINE = 1) of the pass into the P region,
+// laid out as lw_sp_power lays out P, and from there to the lines line0 + bin: re[j] on line j, im[j] on line B + j, the two
+// chains themselves and nothing formed from them
+template <int SINE> LW_SP_FN void lw_sp_part(const LwSpecArgs &a, uint32_t pass, uint32_t tid, float *lds, const LwSpLane &st)
+{
+	const uint32_t lane = tid & 63u, wave = tid >> 6, f = lane & 31u;
+#pragma unroll
+	for (uint32_t tt = 0; tt < 2u; tt++) {
+		if (!lw_sp_tile_live(a, pass, wave, tt))
+			continue;
+#pragma unroll
+		for (uint32_t r = 0; r < 16u; r++)
+			lds[LW_SP_LDS_P + (wave * 64u + tt * 32u + LW_SP_ROW(r, lane)) * LW_SP_TF + f] = st.acc[2 * tt + SINE][r];
 	}
 }
 
@@ -419,10 +442,12 @@ LW_SP_FN void lw_sp_pro_mu(uint32_t tid, const float *lds, float &mu0, float &mu
 
 #ifndef LW_SPEC_HOST
 
+// The body of both kernels.  OUT is the object's output (LW_SPEC_OUT_*) as a compile-time constant, for PAD's reason: k_spec is
+// the body with OUT = 0, the kernel it was before the complex output existed (profiles/rows_spec_resource_usage.txt), and
+// k_spec_complex the body with OUT = 1 and no prologue.
 // PRO = 0 is the kernel without the prologue, to the instruction: what every object without remove_dc and energy runs
-template <int ROUTE, int PAD, int PRO> __global__ void __launch_bounds__(LW_SP_THREADS) k_spec(LwSpecArgs a)
+template <int ROUTE, int PAD, int PRO, int OUT> LW_SP_FN void lw_sp_body(const LwSpecArgs &a, float *lw_sp_lds)
 {
-	extern __shared__ float lw_sp_lds[];
 	LwSpTile t;
 	if (!lw_sp_tile(a, blockIdx.x, blockIdx.y, blockIdx.z, t))
 		return; // (the whole workgroup: the tile is behind its row's last frame)
@@ -448,6 +473,16 @@ template <int ROUTE, int PAD, int PRO> __global__ void __launch_bounds__(LW_SP_T
 			lw_sp_mma<ROUTE>(a, pass, tid, lw_sp_lds, st);
 			__syncthreads();
 		}
+		if (OUT) { // re of the pass, then im, through the P region; the next pass's barriers stand behind the last reads
+			lw_sp_part<0>(a, pass, tid, lw_sp_lds, st);
+			__syncthreads();
+			lw_sp_store_lines(a, t, pass, tid, lw_sp_lds, 0u);
+			__syncthreads();
+			lw_sp_part<1>(a, pass, tid, lw_sp_lds, st);
+			__syncthreads();
+			lw_sp_store_lines(a, t, pass, tid, lw_sp_lds, a.bins);
+			continue;
+		}
 		lw_sp_power(a, pass, tid, lw_sp_lds, st);
 		__syncthreads();
 		if (a.n_mels == 0) {
@@ -461,8 +496,31 @@ template <int ROUTE, int PAD, int PRO> __global__ void __launch_bounds__(LW_SP_T
 			__syncthreads();
 		}
 	}
-	if (a.n_mels)
+	if (!OUT && a.n_mels)
 		lw_sp_store_mel<PRO>(a, t, tid, st);
+}
+
+template <int ROUTE, int PAD, int PRO> __global__ void __launch_bounds__(LW_SP_THREADS) k_spec(LwSpecArgs a)
+{
+	extern __shared__ float lw_sp_lds[];
+	lw_sp_body<ROUTE, PAD, PRO, 0>(a, lw_sp_lds);
+}
+
+template <int ROUTE, int PAD> __global__ void __launch_bounds__(LW_SP_THREADS) k_spec_complex(LwSpecArgs a)
+{
+	extern __shared__ float lw_sp_lds[];
+	lw_sp_body<ROUTE, PAD, 0, 1>(a, lw_sp_lds);
+}
+
+template <int ROUTE, int PAD> static hipError_t lw_sp_launch_complex(const LwSpecArgs &a, dim3 grid, hipStream_t st)
+{
+	static LwPerDeviceOnce once;
+	const hipError_t e = once.run([] {
+		return hipFuncSetAttribute((const void *)k_spec_complex<ROUTE, PAD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LW_SP_LDS_FLOATS * sizeof(float)));
+	});
+	if (e != hipSuccess)
+		return e;
+	return lw_launch_k(k_spec_complex<ROUTE, PAD>, grid, dim3(LW_SP_THREADS), (size_t)LW_SP_LDS_FLOATS * sizeof(float), st, a);
 }
 
 template <int ROUTE, int PAD, int PRO> static hipError_t lw_sp_launch(const LwSpecArgs &a, dim3 grid, hipStream_t st)
@@ -478,6 +536,8 @@ template <int ROUTE, int PAD, int PRO> static hipError_t lw_sp_launch(const LwSp
 
 template <int ROUTE, int PAD> static hipError_t lw_sp_launch_pro(const LwSpecArgs &a, dim3 grid, hipStream_t st)
 {
+	if (a.output == 1u)
+		return lw_sp_launch_complex<ROUTE, PAD>(a, grid, st);
 	return a.remove_dc || a.energy ? lw_sp_launch<ROUTE, PAD, 1>(a, grid, st) : lw_sp_launch<ROUTE, PAD, 0>(a, grid, st);
 }
 
@@ -486,7 +546,7 @@ hipError_t lw_launch_spec(const LwSpecArgs &a, int route, uint32_t tiles, uint32
 	if (tiles == 0 || n_rows == 0)
 		return hipSuccess;
 	if (ch == 0 || ch > 65535u || n_rows > 65535u || tiles > LW_SP_MAX_TILES || a.k_pad == 0 || a.k_pad % LW_SP_KT || a.mel_pad > 256u || a.mel_pad % 32u ||
-			(a.n_mels != 0 && !a.fb))
+			(a.n_mels != 0 && !a.fb) || a.output > 1u || (a.output == 1u && (a.n_mels || a.remove_dc || a.energy)))
 		return hipErrorInvalidValue;
 	const dim3 grid(tiles, ch, n_rows);
 	if (route != LW_SP_ROUTE_MFMA && route != LW_SP_ROUTE_FMA)

@@ -6,6 +6,7 @@
 // lw_stage.hpp describes.  Nothing else in the library calls into this file.
 #include "lw_stage.hpp"
 #include "lw_spec.hpp"
+#include "lw_window.hpp"
 
 #include <cmath>
 
@@ -16,6 +17,7 @@ struct lw_spec {
 	int pad_mode = LW_SPEC_PAD_ZERO;
 	int framing = LW_SPEC_FRAMES_STFT;
 	bool remove_dc = false, energy = false;
+	int output = LW_SPEC_OUT_POWER;
 	double scale = 1.0;
 	LwSpecPlan plan{};
 	std::vector<float> basis;                  // [2][win_length][B], the public order
@@ -43,23 +45,6 @@ lw_spec *lw_spec_create(int device, uint32_t n_fft, uint32_t win_length, uint32_
 	return lw_spec_create_ex(device, &p, err);
 }
 
-// w[i] of a window of W samples, in double
-static double lw_sp_window(int window, uint32_t i, uint32_t W)
-{
-	if (window == LW_SPEC_RECT)
-		return 1.0;
-	if (window == LW_SPEC_HANN)
-		return 0.5 - 0.5 * std::cos(2.0 * M_PI * (double)i / (double)W);
-	const double a = 2.0 * M_PI * (double)i / (double)(W - 1u);
-	if (window == LW_SPEC_HAMMING)
-		return 0.54 - 0.46 * std::cos(a);
-	if (window == LW_SPEC_HANN_SYM)
-		return 0.5 - 0.5 * std::cos(a);
-	if (window == LW_SPEC_POVEY)
-		return std::pow(0.5 - 0.5 * std::cos(a), 0.85);
-	return 0.42 - 0.5 * std::cos(a) + 0.08 * std::cos(2.0 * a); // LW_SPEC_BLACKMAN
-}
-
 lw_spec *lw_spec_create_ex(int device, const lw_spec_params *prm, int *err)
 {
 	int dummy;
@@ -74,12 +59,14 @@ lw_spec *lw_spec_create_ex(int device, const lw_spec_params *prm, int *err)
 	const int window = prm->window, center = prm->center;
 	const float *fb = prm->fb;
 	const bool kaldi = prm->framing == LW_SPEC_FRAMES_KALDI_SNIP || prm->framing == LW_SPEC_FRAMES_KALDI_EDGES;
-	const bool symmetric = window == LW_SPEC_POVEY || window == LW_SPEC_HAMMING || window == LW_SPEC_HANN_SYM || window == LW_SPEC_BLACKMAN;
+	const bool symmetric = lw_sp_window_symmetric(window);
 	if (n_fft < 2 || n_fft > LW_SPEC_MAX_FFT || win_length < 1 || win_length > n_fft || hop < 1 || hop > 65535 || n_mels > LW_SPEC_MAX_MELS ||
 			(window != LW_SPEC_HANN && window != LW_SPEC_RECT && !symmetric) || (symmetric && win_length < 2) ||
 			(prm->framing != LW_SPEC_FRAMES_STFT && !kaldi) || (kaldi && center) || (prm->remove_dc != 0 && prm->remove_dc != 1) ||
 			(prm->energy != 0 && prm->energy != 1) || !(prm->preemphasis >= 0.0 && prm->preemphasis <= 1.0) ||
-			!(prm->scale > 0.0 && std::isfinite(prm->scale)) || prm->reserved != 0) {
+			!(prm->scale > 0.0 && std::isfinite(prm->scale)) || prm->reserved != 0 ||
+			(prm->output != LW_SPEC_OUT_POWER && prm->output != LW_SPEC_OUT_COMPLEX) ||
+			(prm->output == LW_SPEC_OUT_COMPLEX && (n_mels != 0 || prm->remove_dc != 0 || prm->energy != 0))) { // (the complex lines are the chains themselves)
 		*err = LW_ERR_UNSUPPORTED;
 		return nullptr;
 	}
@@ -98,6 +85,7 @@ lw_spec *lw_spec_create_ex(int device, const lw_spec_params *prm, int *err)
 	sp->device = device;
 	sp->n_fft = n_fft, sp->win_length = win_length, sp->hop = hop, sp->n_mels = n_mels, sp->center = center != 0;
 	sp->framing = prm->framing, sp->remove_dc = prm->remove_dc != 0, sp->energy = prm->energy != 0, sp->scale = prm->scale;
+	sp->output = prm->output;
 	if (prm->framing == LW_SPEC_FRAMES_KALDI_EDGES)
 		sp->pad_mode = LW_SPEC_PAD_SYMMETRIC;
 	sp->plan = lw_spec_plan(n_fft, win_length, n_mels);
@@ -171,6 +159,8 @@ uint32_t lw_spec_bins(const lw_spec *sp)
 
 uint32_t lw_spec_features(const lw_spec *sp)
 {
+	if (sp && sp->output == LW_SPEC_OUT_COMPLEX)
+		return 2u * sp->plan.bins; // re[j] on line j, im[j] on line B + j
 	return sp ? (sp->n_mels ? sp->n_mels : sp->plan.bins) + (sp->energy ? 1u : 0u) : 0;
 }
 
@@ -293,6 +283,7 @@ int lw_spec_rows(lw_spec *sp, int fmt, uint32_t ch, const void *d_src, size_t n_
 	}
 	a.hop = sp->hop, a.win_length = sp->win_length, a.k_pad = p.k_pad, a.bins = p.bins, a.passes = p.passes, a.n_mels = sp->n_mels, a.mel_pad = p.mel_pad;
 	a.pad_mode = (uint32_t)sp->pad_mode;
+	a.output = (uint32_t)sp->output;
 	if (lw_stage_launch(n_src_rows, "lw_launch_spec", [&](uint32_t row0, uint32_t n) {
 		    a.row0 = row0;
 		    for (uint64_t t0 = 0; t0 < tiles; t0 += LW_SP_MAX_TILES) { // (a grid dimension holds fewer than 2^32 lanes)

@@ -110,6 +110,7 @@ struct LwSpecArgs {
 	uint32_t energy;    // line 0 of the destination is the frame's energy, the spectrum or mel lines follow from line 1
 	uint32_t span;      // 31 * hop + win_length when the prologue stages the tile's samples through LDS (lw_spec_span_fits), else 0
 	double escale;      // scale * scale, what the energy is multiplied by
+	uint32_t output;    // LW_SPEC_OUT_POWER, or LW_SPEC_OUT_COMPLEX: re on the lines [0, bins), im on [bins, 2 bins) (k_spec_complex)
 };
 
 // The prologue's sums run over the samples of 32 frames, hop apart.  When the tile's span of 31 * hop + win_length samples fits

@@ -37,6 +37,13 @@ fill, bit for bit) -- together the input of a Whisper-style model:
     feats, frames = sp.run(pcm, lengths, out=torch.zeros((B, 1, 80, 3000), device="cuda"))
     LogCompress.whisper().run(feats, frames, fill_to=3000)
 
+output="complex" keeps the phase (the re and im lines of every bin), and InverseSpectrogram is the way back (lw_istft_rows, k_istft
+in csrc/lw_kernels_istft.hip: inverse DFT on the matrix instruction, overlap-add and envelope division, bit for bit) -- what a
+mask-based enhancement or separation model stands between:
+
+    sp, inv = Spectrogram(512, 128, output="complex", pad_mode="reflect"), InverseSpectrogram(512, 128)
+    spec, frames = sp.run(pcm, lengths); pcm2, _ = inv.run(model(spec), frames, lengths=lengths)
+
 Normalize is the step the waveform models (wav2vec 2.0, HuBERT, WavLM) and utterance CMVN need (lw_norm_rows, k_norm in
 csrc/lw_kernels_norm.hip: mean and deviation, RMS or peak of a row, a channel or a line from double sums in a fixed order, bit for
 bit), over a waveform tensor [B, C, T] or a feature tensor [B, C, F, frames]:
@@ -391,8 +398,10 @@ class Resampler:
 
 _SPEC_WINDOWS = {"hann": 0, "rect": 1, "povey": 2, "hamming_sym": 3, "hann_sym": 4, "blackman_sym": 5}   # LW_SPEC_HANN ... LW_SPEC_BLACKMAN
 _SPEC_PAD_MODES = {"zero": 0, "reflect": 1}  # LW_SPEC_PAD_ZERO, LW_SPEC_PAD_REFLECT
+_SPEC_OUTPUTS = {"power": 0, "complex": 1}   # LW_SPEC_OUT_POWER, LW_SPEC_OUT_COMPLEX
 _SPEC_FRAMINGS = {("stft", True): 0, ("stft", False): 0, ("kaldi", True): 1, ("kaldi", False): 2}   # (framing, snip_edges): LW_SPEC_FRAMES_*
 SPEC_MAX_FFT, SPEC_MAX_MELS = 2048, 256     # LW_SPEC_MAX_FFT, LW_SPEC_MAX_MELS
+ISTFT_MAX_OVERLAP = 16                      # LW_ISTFT_MAX_OVERLAP
 
 
 def _mel_scale(f, scale):
@@ -497,11 +506,17 @@ class Spectrogram:
     reflects the row with the edge sample repeated (run() then refuses a row too short for one reflection).  preemphasis (0 .. 1)
     and scale (> 0; Kaldi's sample range is 32768) are folded into the table; remove_dc subtracts every frame's mean from it;
     energy puts the frame's energy (after remove_dc, before pre-emphasis and window, times scale^2) in line 0, the other lines
-    behind it.  Parameter errors are ValueError and need no GPU; the object itself lives on cuda:device."""
+    behind it.  output: "power", or "complex": 2 * bins lines, re[j] on line j and im[j] on line bins + j, the chains themselves
+    (as_complex() makes the complex tensor; InverseSpectrogram reads the lines as they are); not with mel=, remove_dc or energy.  Parameter errors are ValueError and need no GPU; the object itself lives on cuda:device."""
 
     def __init__(self, n_fft=400, hop=160, win_length=None, window="hann", center=True, mel=None, device=0, pad_mode="zero",
-                 framing="stft", snip_edges=True, preemphasis=0.0, remove_dc=False, energy=False, scale=1.0):
+                 framing="stft", snip_edges=True, preemphasis=0.0, remove_dc=False, energy=False, scale=1.0, output="power"):
         self.win_length, self._mel = _spec_params(n_fft, hop, win_length, window, mel)
+        if output not in _SPEC_OUTPUTS:
+            raise ValueError("output=%r: \"power\" or \"complex\"" % (output,))
+        if output == "complex" and (mel is not None or remove_dc or energy):
+            raise ValueError("output=\"complex\" stores the chains themselves: not with mel=, remove_dc or energy")
+        self.output = output
         if pad_mode not in _SPEC_PAD_MODES or (pad_mode == "reflect" and not center):
             raise ValueError("pad_mode=%r: \"zero\", or \"reflect\" with center=True" % (pad_mode,))
         if framing not in ("stft", "kaldi") or snip_edges not in (True, False, 0, 1):
@@ -523,13 +538,14 @@ class Spectrogram:
         err = C.c_int(0)
         n_mels = 0 if self._mel is None else self._mel.shape[0]
         p = N.SpecParams(self.n_fft, self.win_length, self.hop, n_mels, None if self._mel is None else self._mel.ctypes.data, _SPEC_WINDOWS[window],
-                         int(self.center), _SPEC_FRAMINGS[framing, bool(snip_edges)], int(self.remove_dc), int(self.energy), 0, preemphasis, scale)
+                         int(self.center), _SPEC_FRAMINGS[framing, bool(snip_edges)], int(self.remove_dc), int(self.energy), 0, preemphasis, scale, _SPEC_OUTPUTS[output])
         self._h = N.lw_spec_create_ex(device, C.byref(p), C.byref(err))
         if not self._h:
             if err.value in (N.ERR_UNSUPPORTED, N.ERR_NULL_ARG):
                 raise ValueError("lw_spec_create_ex refused the parameters")
             raise RuntimeError("lw_spec_create_ex failed (%d): %s" % (err.value, N.device_error()))
-        assert self.bins == self.n_fft // 2 + 1 and self.features == (n_mels or self.bins) + int(self.energy)
+        assert self.bins == self.n_fft // 2 + 1
+        assert self.features == (2 * self.bins if output == "complex" else (n_mels or self.bins) + int(self.energy))
         if framing == "stft" and N.lw_spec_set_pad_mode(self._h, _SPEC_PAD_MODES[pad_mode]):
             self.close()
             raise ValueError("lw_spec_set_pad_mode refused pad_mode=%r" % (pad_mode,))
@@ -566,6 +582,13 @@ class Spectrogram:
         assert N.lw_spec_basis(self._h, None) == out.size
         N.lw_spec_basis(self._h, out.ctypes.data_as(C.c_void_p))
         return out
+
+    @staticmethod
+    def as_complex(t):
+        """the complex tensor [..., B, frames] of an output="complex" result [..., 2 B, frames] (re lines, then im lines)"""
+        import torch
+        B = t.shape[-2] // 2
+        return torch.complex(t[..., :B, :], t[..., B:, :])
 
     def last_route(self):
         """0: the DFT fold ran on the matrix cores, 1: per-lane fmaf chains, -1: no call yet (lw_spec_last_route)"""
@@ -643,6 +666,129 @@ class Spectrogram:
                 x = torch.clamp(part, min=float(floor))
                 part.copy_(torch.where(written, torch.log(x) if log == "ln" else torch.log10(x), part))
         return out, torch.tensor(frames, dtype=torch.int64)
+
+
+class InverseSpectrogram:
+    """lw_istft: complex spectral frames [rows][C][2 * bins][frames] (Spectrogram(output="complex")'s lines: re, then im) -> rows
+    of f32 PCM on the GPU (k_istft), by the inverse DFT, overlap-add and envelope division of include/lewton_amd.h ("inverse
+    spectral frames of rows"), a contract on bits; torch.istft's algorithm with the analysis window.  window, win_length and
+    center as Spectrogram's; hop <= win_length and ceil(win_length / hop) <= 16.  Where the window envelope is not above 1e-11 a
+    sample is +0.0 (torch raises).  Parameter errors are ValueError and need no GPU; the object itself lives on cuda:device."""
+
+    def __init__(self, n_fft=400, hop=160, win_length=None, window="hann", center=True, device=0):
+        self.win_length, _ = _spec_params(n_fft, hop, win_length, window, None)
+        if hop > self.win_length or -(-self.win_length // hop) > ISTFT_MAX_OVERLAP:
+            raise ValueError("hop=%r: at most win_length, and at least win_length / %d" % (hop, ISTFT_MAX_OVERLAP))
+        self.n_fft, self.hop, self.center, self.window, self.device = int(n_fft), int(hop), bool(center), window, device
+        _gpu()
+        err = C.c_int(0)
+        p = N.IstftParams(self.n_fft, self.win_length, self.hop, _SPEC_WINDOWS[window], int(self.center), 0)
+        self._h = N.lw_istft_create(device, C.byref(p), C.byref(err))
+        if not self._h:
+            if err.value in (N.ERR_UNSUPPORTED, N.ERR_NULL_ARG):
+                raise ValueError("lw_istft_create refused the parameters")
+            raise RuntimeError("lw_istft_create failed (%d): %s" % (err.value, N.device_error()))
+        assert self.bins == self.n_fft // 2 + 1
+
+    def close(self):
+        if getattr(self, "_h", None):
+            N.lw_istft_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        if N is not None and getattr(N, "lw_istft_destroy", None) is not None:  # not during interpreter shutdown
+            self.close()
+
+    @property
+    def bins(self):
+        return int(N.lw_istft_bins(self._h))
+
+    @property
+    def tile_frames(self):
+        """m: a workgroup owns m * hop samples (lw_istft_tile_frames)"""
+        return int(N.lw_istft_tile_frames(self._h))
+
+    def set_tile_frames(self, m):
+        if N.lw_istft_set_tile_frames(self._h, int(m)):
+            raise ValueError("lw_istft_set_tile_frames refused m=%r" % (m,))
+
+    def out_len(self, frames):
+        """the natural length of a row of `frames` frames (lw_istft_out_len)"""
+        return int(N.lw_istft_out_len(self._h, int(frames)))
+
+    def basis(self):
+        """[2 * bins][win_length] float32: the cosine lines, then the sine lines, window and 1 / n_fft folded in"""
+        out = np.empty((2 * self.bins, self.win_length), np.float32)
+        assert N.lw_istft_basis(self._h, None) == out.size
+        N.lw_istft_basis(self._h, out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def window2(self):
+        """[win_length] float64: the squared window the envelope is folded from"""
+        out = np.empty(self.win_length, np.float64)
+        assert N.lw_istft_window2(self._h, None) == out.size
+        N.lw_istft_window2(self._h, out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def last_route(self):
+        """0: the frame signals ran on the matrix cores, 1: per-lane fmaf chains, -1: no call yet (lw_istft_last_route)"""
+        return N.lw_istft_last_route(self._h)
+
+    def set_route(self, route):
+        if N.lw_istft_set_route(self._h, int(route)):
+            raise ValueError("lw_istft_set_route refused route %r" % (route,))
+
+    def run(self, spec, frames, lengths=None, out=None, rows=None, stream=None, samples="f32"):
+        """lw_istft_rows: row i of spec (float32 [B, C, 2 * bins, frame capacity], frames[i] frames) -> row rows[i] of out (None:
+        row i), [rows][C][T] or, for samples="f32_interleaved", [rows][T][C]; lengths[i] samples of it are written (None: the
+        natural lengths, out_len(frames[i])), +0.0 behind what the frames cover; nothing else of out is written.  out=None: a
+        zeroed tensor of max(rows) + 1 rows and the largest length.  stream: a hipStream_t value; None = torch's current stream
+        on the object's device.  Asynchronous; returns (out, lengths), lengths an int64 host tensor with one entry per row of spec."""
+        torch = _gpu()
+        fmt = _FMT[samples]
+        if fmt not in (N.FMT_F32_PLANAR, N.FMT_F32_INTERLEAVED):
+            raise ValueError("the inverse spectrogram writes the f32 formats, not %r" % (samples,))
+        dev = "cuda:%d" % self.device
+        if spec.dtype != torch.float32 or spec.device.type != "cuda" or spec.device.index != self.device or not spec.is_contiguous():
+            raise ValueError("spec must be a contiguous float32 tensor on %s" % dev)
+        if spec.dim() != 4 or spec.shape[2] != 2 * self.bins:
+            raise ValueError("spec must be [rows][channels][%d lines][frames], not %r" % (2 * self.bins, tuple(spec.shape)))
+        n_src, ch, _, fcap = spec.shape
+        T = [int(v) for v in (frames.tolist() if hasattr(frames, "tolist") else frames)]
+        if len(T) != n_src or any(v < 0 for v in T):
+            raise ValueError("frames= needs one non-negative entry per row of spec")
+        if lengths is None:
+            lens = [self.out_len(v) for v in T]
+        else:
+            lens = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+            if len(lens) != n_src or any(v < 0 for v in lens):
+                raise ValueError("lengths= needs one non-negative entry per row of spec")
+        rmap = None
+        if rows is not None:
+            rows = [int(v) for v in (rows.tolist() if hasattr(rows, "tolist") else rows)]
+            if len(rows) != n_src or any(not 0 <= v < 1 << 32 for v in rows):
+                raise ValueError("rows= needs one destination row per row of spec")
+            rmap = np.asarray(rows, np.uint32)
+        itl = N.fmt_interleaved(fmt)
+        if out is None:
+            n_dst, cap = (max(rows) + 1 if rows else n_src), max(lens, default=0)
+            out = torch.zeros((n_dst, cap, ch) if itl else (n_dst, ch, cap), dtype=torch.float32, device=dev)
+        if out.dtype != torch.float32 or out.device.type != "cuda" or out.device.index != self.device or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32 tensor on %s" % dev)
+        if out.dim() != 3 or out.shape[1 + itl] != ch:
+            raise ValueError("out must be [rows][%d channels][samples] (interleaved: [rows][samples][channels]), not %r" % (ch, tuple(out.shape)))
+        n_dst, cap = out.shape[0], out.shape[2 - itl]
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream or None
+        Ta, La = np.asarray(T, np.uint64), np.asarray(lens, np.uint64)
+        rc = N.lw_istft_rows(self._h, ch, C.c_void_p(spec.data_ptr()), n_src, fcap, Ta.ctypes.data_as(C.c_void_p),
+                             None if rmap is None else rmap.ctypes.data_as(C.c_void_p), La.ctypes.data_as(C.c_void_p), fmt,
+                             C.c_void_p(out.data_ptr()), n_dst, cap, stream)
+        if rc in (N.ERR_NULL_ARG, N.ERR_CAPACITY, N.ERR_UNSUPPORTED):
+            raise ValueError("lw_istft_rows refused the call (%d)" % rc)
+        if rc:
+            raise RuntimeError("lw_istft_rows: %d %s" % (rc, N.device_error()))
+        return out, torch.tensor(lens, dtype=torch.int64)
 
 
 _FEAT_LOGS = {None: 0, "none": 0, "ln": 1, "log10": 2, "db": 3}      # LW_FEAT_LOG_*
