@@ -815,6 +815,112 @@ int lw_pack_rows(lw_pack *pk, uint32_t ch, const void *d_src, void *d_dst, size_
 		const uint64_t *n_frames, const uint64_t *fill_to, uint8_t *d_mask, void *hip_stream);
 int lw_pack_last_launches(const lw_pack *pk);
 
+/* ---- sliding-window normalisation of feature rows ---------------------------------------------------------------------------
+ * Kaldi's apply-cmvn-sliding on the GPU, as a pass of its own (k_slide): every frame of a feature line minus the mean of a window
+ * of frames around (center) or before it, optionally divided by the window's deviation -- what the x-vector recipes run with a
+ * 300-frame centred window between fbank / mfcc and the model, and what streaming ASR uses in place of utterance CMVN.  Source and
+ * destination are f32 [row][ch][F][frame_capacity], the layout of every stage before it; row i has T = n_frames[i] frames.  An
+ * object is made from (cmn_window W, min_cmn_window, center, norm_vars): 1 <= min_cmn_window <= W <= LW_SLIDE_MAX_WINDOW, center
+ * and norm_vars 0 or 1.  A contract on BITS, applied to every line on its own; the order of the sums is part of it.
+ *   1  The window [s, e) of frame t, Kaldi's rule, in signed 64-bit integers:
+ *        center:     s = t - W / 2 (integer division), e = s + W;      otherwise:  s = t - W, e = t + 1 (W + 1 frames, as in Kaldi)
+ *        if s < 0:  e -= s, then s = 0;      if not center and e > t:  e = max(t + 1, min_cmn_window);
+ *        if e > T:  s -= e - T, e = T, and s = 0 if s < 0.
+ *      (T, W, min, center) = (10, 4, 2, 1): t = 0, 1, 2, 3, 8, 9 have [0,4) [0,4) [0,4) [1,5) [6,10) [6,10);
+ *      (10, 4, 3, 0): t = 0, 1, 2, 3, 5, 9 have [0,3) [0,3) [0,3) [0,4) [1,6) [5,10).  Every window contains t and lies in
+ *      [t - W, t + W] and in [0, T); s and e never decrease with t, and s grows by at most one a frame.
+ *   2  Block sums.  A line is cut into blocks of 16 frames counted from the line's frame 0 (by index, not by address).  A_b: from
+ *      +0.0, add (double)x[16 b + i] for i = 0 .. 15 ascending, one rounded double add each.  Q_b: the same fold of the squares
+ *      (exact in double).
+ *   3  The window sum.  b0 = ceil(s / 16), b1 = floor(e / 16).  ONE accumulator from +0.0, one rounded double add per term:
+ *        b0 >= b1:   the elements s .. e - 1 ascending;
+ *        otherwise:  the elements s .. 16 b0 - 1, then A_b0 .. A_(b1 - 1), then the elements 16 b1 .. e - 1.
+ *      This is S.  Q is the same fold over the squares and Q_b.  (A 600-frame window takes at most 15 + 37 + 15 adds.)
+ *   4  The value.  n = e - s;  mu = S / (double)n.
+ *        without norm_vars:  z = (float)((double)x[t] - mu)
+ *        norm_vars, n == 1:  z = +0.0
+ *        norm_vars, n > 1:   v = Q / (double)n - mu * mu;  v = 1e-10 if !(v > 1e-10);  g = 1.0 / sqrt(v);
+ *                            z = (float)(((double)x[t] - mu) * g)
+ *      Every + - * / and sqrt is ONE IEEE double operation, nothing fused.
+ *   5  Positions [T, max(T, fill_to[row])) of every destination line receive +0.0.  Nothing else of d_dst is written, and nothing of
+ *      d_src at or beyond T of a line is read.  Any overlap of d_src and d_dst is the caller's error: neighbours are read, so there
+ *      is no in-place form.  The sign of a zero is inside the contract; which NaN a NaN result is, is outside it.
+ * Accuracy: an element of the window passes through at most d = 16 + 15 + ((W + 1) / 16 + 1) + 15 additions (16 in its block, then
+ * the terms of rule 3), so |S - exact| <= d * 2^-53 * sum |x| over the window (first order), the same for Q over the squares: d = 84
+ * at W = 600, 175 at W = 2048.  z without norm_vars is then within half an f32 ulp plus (d + 2) * 2^-53 * (mean |x| + |x[t]|) of the exactly
+ * centred value.  v = Q / n - mu * mu cancels as in "normalising rows": its relative error is about d * 2^-52 * (1 + mu^2 / v).
+ *
+ * lw_slide_rows: n_frames and fill_to (may be NULL: nothing is filled) are HOST arrays, copied during the call.  Asynchronous on
+ * hip_stream; calls on one object may be queued back to back.  ONE kernel launch per 65535 rows (the one-launch form: block sums
+ * are recomputed by every workgroup over its own span in LDS, nothing goes through scratch), none when nothing is to be written.
+ * A workgroup takes lw_slide_tile_frames consecutive frames (1024) of up to 16 lines of a row and channel and stages the frames
+ * its windows cover -- at most tile + W + 15 -- as floats, with their block sums as doubles, in at most 64 KiB of LDS (4.125 + 1
+ * bytes per staged frame and line; the number of lines is what fits, a multiple of four from four on: the chains of four lines
+ * run side by side in a lane).  No atomics, no workgroup waits on another; the bits depend
+ * neither on the tile nor on the grid.  lw_slide_set_tile_frames: a test's handle on the seams, a multiple of 16 in 16 .. 4096.
+ * lw_slide_window: rule 1 on the host, from the same source as the kernel's.  lw_slide_last_launches: the kernels the last
+ * accepted call queued, -1 = no call yet.
+ * Refusals, decided on the host before anything is queued:
+ *   LW_ERR_NULL_ARG     sl, p, start or end NULL, n_frames NULL with rows, d_src NULL with frames to read, d_dst NULL with elements
+ *                       to write
+ *   LW_ERR_UNSUPPORTED  (create) min_cmn_window == 0 or > cmn_window, cmn_window > LW_SLIDE_MAX_WINDOW, center or norm_vars not 0 or
+ *                       1; (set_tile_frames) a tile that is no multiple of 16 in 16 .. 4096
+ *   LW_ERR_DEVICE       (create) no such device, or one whose workgroups have less than 64 KiB of LDS (the device is asked)
+ *   LW_ERR_CAPACITY     n_frames[i] or fill_to[i] > frame_capacity, ch == 0 or > 255, F == 0 or > 65535, a buffer that 64 bits of
+ *                       bytes cannot address, more than 2^24 - 1 workgroups (tiles * line groups) in a channel; (window) t >= T */
+#define LW_SLIDE_MAX_WINDOW 2048
+typedef struct lw_slide lw_slide;
+typedef struct {
+	uint32_t cmn_window, min_cmn_window;
+	int32_t center, norm_vars;
+} lw_slide_params;
+lw_slide *lw_slide_create(int device, const lw_slide_params *p, int *err);
+void lw_slide_destroy(lw_slide *sl);
+int lw_slide_rows(lw_slide *sl, uint32_t ch, uint32_t F, const void *d_src, void *d_dst, size_t n_rows, size_t frame_capacity,
+		const uint64_t *n_frames, const uint64_t *fill_to, void *hip_stream);
+int lw_slide_window(const lw_slide *sl, uint64_t t, uint64_t T, uint64_t *start, uint64_t *end);
+uint32_t lw_slide_tile_frames(const lw_slide *sl);
+int lw_slide_set_tile_frames(lw_slide *sl, uint32_t tile);
+int lw_slide_last_launches(const lw_slide *sl);
+
+/* ---- frame decisions and frame selection ------------------------------------------------------------------------------------
+ * Shortening feature rows by a mask on the GPU, as a pass of its own (k_select): Kaldi's select-voiced-frames for ANY mask -- an
+ * energy VAD's, a neural VAD's, a silence trim.  Source and destination are f32 [row][ch][F][frame_capacity], the layout of every
+ * stage before it, with the SAME frame_capacity, so no count can overflow a line; the mask is uint8 [row][ch][frame_capacity], one
+ * decision per frame of a row and channel (any non-zero byte keeps the frame).  Row i has T = n_frames[i] frames.  For each row
+ * and channel:
+ *   the kept frames are those t < T with mask[t] != 0, in ascending order: t_0 < .. < t_(K-1);
+ *   element j < K of destination line f is a BIT COPY of element t_j of source line f (NaN payloads included);
+ *   positions [K, max(T, fill_to[row])) of every destination line receive +0.0.
+ * Every position below max(T, fill_to[row]) is therefore written exactly once, and nothing else of d_dst is written.  Nothing of
+ * d_src or d_mask at or beyond T is read.  d_counts, when given, receives K as one uint64 per row and channel, [n_rows][ch], rows
+ * with T == 0 included.  Any overlap of the buffers is the caller's error.  Integer arithmetic only: there is no order to specify.
+ * The channels of a row may end up with different lengths: [B][C][F][cap] viewed as [B * C][1][F][cap] is the same memory, and the
+ * counts read as [B * C] are the next pass's n_frames.
+ *
+ * lw_select_rows: n_frames and fill_to (may be NULL: nothing is filled) are HOST arrays, copied during the call.  Asynchronous on
+ * hip_stream; calls on one object may be queued back to back.  TWO kernel launches per 65535 rows: the kept frames of every tile
+ * of lw_select_tile_frames frames (1024) of every row and channel are counted into a list the object owns; then every workgroup
+ * adds up the list in front of its tile, compacts its tile's kept frames in LDS by an integer prefix sum, copies them for up to 16
+ * lines (coalesced writes, a monotone gather of reads) and zeroes its share of the tail.  The count launch is left out when no
+ * row has a frame; with nothing to write there is no launch, and d_counts is zeroed by a memset on the stream.  No atomics, no
+ * workgroup waits on another.  A workgroup needs 9280 bytes of LDS.  lw_select_set_tile_frames: a test's handle on the seams, a
+ * multiple of 256 in 256 .. 2048.  lw_select_last_launches: the kernels the last accepted call queued, -1 = no call yet.
+ * Refusals, decided on the host before anything is queued:
+ *   LW_ERR_NULL_ARG     se NULL, n_frames NULL with rows, d_src or d_mask NULL with frames to read, d_dst NULL with elements to write
+ *   LW_ERR_UNSUPPORTED  (set_tile_frames) a tile that is no multiple of 256 in 256 .. 2048
+ *   LW_ERR_DEVICE       (create) no such device, or one whose workgroups have less LDS than the kernel needs (the device is asked)
+ *   LW_ERR_CAPACITY     n_frames[i] or fill_to[i] > frame_capacity, ch == 0 or > 255, F == 0 or > 65535, a buffer that 64 bits of
+ *                       bytes cannot address, more than 2^24 - 1 workgroups (tiles * groups of 16 lines) in a channel */
+typedef struct lw_select lw_select;
+lw_select *lw_select_create(int device, int *err);
+void lw_select_destroy(lw_select *se);
+int lw_select_rows(lw_select *se, uint32_t ch, uint32_t F, const void *d_src, const uint8_t *d_mask, void *d_dst, uint64_t *d_counts,
+		size_t n_rows, size_t frame_capacity, const uint64_t *n_frames, const uint64_t *fill_to, void *hip_stream);
+uint32_t lw_select_tile_frames(const lw_select *se);
+int lw_select_set_tile_frames(lw_select *se, uint32_t tile);
+int lw_select_last_launches(const lw_select *se);
+
 /* ---- staging ring (BASELINE north_star: "pinned hipMemcpyAsync staging ring so entropy decode of packet N+1 overlaps
  * GPU synthesis of packet N") ------------------------------------------------------------------------------------------
  * A ring of `slots` staging slots on the decoder's device; a slot = one batch object (pinned records + device mirror), a device

@@ -78,6 +78,10 @@ class PackParams(C.Structure):
                 ("pad", C.c_float), ("reserved", C.c_uint32)]
 
 
+class SlideParams(C.Structure):
+    _fields_ = [("cmn_window", C.c_uint32), ("min_cmn_window", C.c_uint32), ("center", C.c_int32), ("norm_vars", C.c_int32)]
+
+
 class OggPacket(C.Structure):
     _fields_ = [("data", C.c_void_p), ("len", C.c_size_t), ("stream_serial", C.c_uint32), ("absgp_page", C.c_uint64),
                 ("first_in_stream", C.c_uint8), ("last_in_stream", C.c_uint8), ("first_in_page", C.c_uint8),
@@ -233,6 +237,21 @@ SYMBOLS = {
     "lw_pack_rows": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_void_p]),
     "lw_pack_last_launches": (C.c_int, [C.c_void_p]),
+    "lw_slide_create": (C.c_void_p, [C.c_int, C.POINTER(SlideParams), intp]),
+    "lw_slide_destroy": (None, [C.c_void_p]),
+    "lw_slide_rows": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
+                                C.c_void_p]),
+    "lw_slide_window": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "lw_slide_tile_frames": (C.c_uint32, [C.c_void_p]),
+    "lw_slide_set_tile_frames": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "lw_slide_last_launches": (C.c_int, [C.c_void_p]),
+    "lw_select_create": (C.c_void_p, [C.c_int, intp]),
+    "lw_select_destroy": (None, [C.c_void_p]),
+    "lw_select_rows": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lw_select_tile_frames": (C.c_uint32, [C.c_void_p]),
+    "lw_select_set_tile_frames": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "lw_select_last_launches": (C.c_int, [C.c_void_p]),
     "lw_ring_create": (C.c_void_p, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, intp]),
     "lw_ring_destroy": (None, [C.c_void_p]),
     "lw_ring_stage": (C.c_int, [C.c_void_p, C.POINTER(Packet), C.c_size_t, C.c_int]),

@@ -1028,6 +1028,198 @@ class Normalize:
         return (out, stats) if want_stats else out
 
 
+SLIDE_MAX_WINDOW = 2048                                   # LW_SLIDE_MAX_WINDOW
+
+
+def _slide_params(cmn_window, min_cmn_window, center, norm_vars):
+    """(cmn_window, min_cmn_window, center, norm_vars) as integers, or ValueError for what lw_slide_create refuses"""
+    for v, what in ((cmn_window, "cmn_window"), (min_cmn_window, "min_cmn_window")):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError("%s=%r: an integer" % (what, v))
+    if not 1 <= min_cmn_window <= cmn_window <= SLIDE_MAX_WINDOW:
+        raise ValueError("1 <= min_cmn_window <= cmn_window <= %d, not %r and %r" % (SLIDE_MAX_WINDOW, min_cmn_window, cmn_window))
+    for v, what in ((center, "center"), (norm_vars, "norm_vars")):
+        if not isinstance(v, (bool, np.bool_, int, np.integer)) or v not in (0, 1):
+            raise ValueError("%s=%r: True or False" % (what, v))
+    return int(cmn_window), int(min_cmn_window), int(bool(center)), int(bool(norm_vars))
+
+
+def _row_counts(v, n_rows, what):
+    """one non-negative count per row as uint64, from a list, an array or a tensor"""
+    counts = [int(c) for c in (v.tolist() if hasattr(v, "tolist") else v)]
+    if len(counts) != n_rows or any(c < 0 for c in counts):
+        raise ValueError("%s= needs one non-negative entry per row" % what)
+    return np.asarray(counts, np.uint64)
+
+
+def _row_fill(fill_to, n_rows):
+    """None, or one non-negative count per row as uint64 from one count for all rows or one per row"""
+    if fill_to is None:
+        return None
+    fill = fill_to.tolist() if hasattr(fill_to, "tolist") else fill_to
+    fill = [int(fill)] * n_rows if isinstance(fill, (int, np.integer)) else [int(v) for v in fill]
+    if len(fill) != n_rows or any(v < 0 for v in fill):
+        raise ValueError("fill_to= needs one non-negative count, or one per row")
+    return np.asarray(fill, np.uint64)
+
+
+class SlidingCMVN:
+    """lw_slide: Kaldi's apply-cmvn-sliding over feature rows [rows][C][F][capacity] on the GPU (k_slide), by the rule of
+    include/lewton_amd.h ("sliding-window normalisation of feature rows"), a contract on bits with a fixed summation order: every
+    frame minus the mean of a window of cmn_window frames around it (center) or of the cmn_window + 1 frames up to it, and with
+    norm_vars divided by the window's deviation.  The arguments have torchaudio.functional.sliding_window_cmn's names and
+    defaults; the x-vector recipes use SlidingCMVN(300, 100, center=True).  Parameter errors are ValueError and need no GPU; the
+    object itself lives on cuda:device."""
+
+    def __init__(self, cmn_window=600, min_cmn_window=100, center=False, norm_vars=False, device=0):
+        W, m, c, nv = _slide_params(cmn_window, min_cmn_window, center, norm_vars)
+        self.cmn_window, self.min_cmn_window, self.center, self.norm_vars, self.device = W, m, bool(c), bool(nv), device
+        _gpu()
+        err = C.c_int(0)
+        p = N.SlideParams(W, m, c, nv)
+        self._h = N.lw_slide_create(device, C.byref(p), C.byref(err))
+        if not self._h:
+            if err.value in (N.ERR_UNSUPPORTED, N.ERR_NULL_ARG):
+                raise ValueError("lw_slide_create refused the parameters")
+            raise RuntimeError("lw_slide_create failed (%d): %s" % (err.value, N.device_error()))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            N.lw_slide_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        if N is not None and getattr(N, "lw_slide_destroy", None) is not None:  # not during interpreter shutdown
+            self.close()
+
+    def window(self, t, T):
+        """rule 1 on the host (lw_slide_window): (start, end) of the window of frame t of a line of T frames"""
+        s, e = C.c_uint64(0), C.c_uint64(0)
+        if not 0 <= t < T or N.lw_slide_window(self._h, int(t), int(T), C.byref(s), C.byref(e)):
+            raise ValueError("window(%r, %r): 0 <= t < T" % (t, T))
+        return s.value, e.value
+
+    @property
+    def tile_frames(self):
+        """frames of a line a workgroup owns (lw_slide_tile_frames)"""
+        return N.lw_slide_tile_frames(self._h)
+
+    def set_tile_frames(self, m):
+        """a test's handle on the seams (lw_slide_set_tile_frames): a multiple of 16 in 16 .. 4096; the bits do not depend on it"""
+        if N.lw_slide_set_tile_frames(self._h, int(m)):
+            raise ValueError("tile_frames=%r: a multiple of 16 in 16 .. 4096" % (m,))
+
+    def last_launches(self):
+        """kernels the last call queued: 1 per 65535 rows, 0 when nothing was to be written; -1: no call yet"""
+        return N.lw_slide_last_launches(self._h)
+
+    def run(self, feats, frames, out=None, fill_to=None, stream=None):
+        """lw_slide_rows: frames[i] frames of every line of row i of feats (float32 [rows][C][F][capacity]) -> the same positions of
+        out (None: a zeroed tensor of feats' shape; never feats itself: neighbours are read, there is no in-place form).  fill_to:
+        None, one count for all rows or one per row -- positions [frames[i], fill_to[i]) of every line receive 0.  Nothing else of
+        out is written.  stream: a hipStream_t value; None = torch's current stream on the object's device.  Asynchronous; returns
+        out."""
+        torch = _gpu()
+        if out is None:
+            out = torch.zeros_like(feats)
+        for t, what in ((feats, "feats"), (out, "out")):
+            if t.dtype != torch.float32 or t.device.type != "cuda" or t.device.index != self.device or not t.is_contiguous() or t.dim() != 4:
+                raise ValueError("%s must be a contiguous float32 tensor [rows][C][F][capacity] on cuda:%d" % (what, self.device))
+        if tuple(out.shape) != tuple(feats.shape):
+            raise ValueError("out must have feats' shape %r, not %r" % (tuple(feats.shape), tuple(out.shape)))
+        if out.data_ptr() == feats.data_ptr() and feats.numel():
+            raise ValueError("out must not be feats: the pass has no in-place form")
+        n_rows, ch, F, cap = feats.shape
+        counts, fill = _row_counts(frames, n_rows, "frames"), _row_fill(fill_to, n_rows)
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream or None
+        rc = N.lw_slide_rows(self._h, ch, F, C.c_void_p(feats.data_ptr()), C.c_void_p(out.data_ptr()), n_rows, cap,
+                             counts.ctypes.data_as(C.c_void_p), None if fill is None else fill.ctypes.data_as(C.c_void_p), stream)
+        if rc in (N.ERR_NULL_ARG, N.ERR_CAPACITY, N.ERR_UNSUPPORTED):
+            raise ValueError("lw_slide_rows refused the call (%d)" % rc)
+        if rc:
+            raise RuntimeError("lw_slide_rows: %d %s" % (rc, N.device_error()))
+        return out
+
+
+class SelectFrames:
+    """lw_select: keeps the frames of feature rows [rows][C][F][capacity] that a mask marks and moves them to the front of every
+    line on the GPU (k_select), by the rule of include/lewton_amd.h ("frame decisions and frame selection"): Kaldi's
+    select-voiced-frames for any mask -- an energy VAD's, a neural VAD's, a silence trim.  Bit copies; the rest of every line up to
+    max(frames, fill_to) is zeroed.  The kept counts stay on the device: the chain's next pass takes HOST counts, so the caller's
+    counts.cpu() is the ONE synchronisation of the step.  Channels of a row may end up with different lengths: [B][C][F][cap]
+    viewed as [B * C][1][F][cap] is the same memory, and counts.reshape(B * C) are the frames of its rows.  Parameter errors are
+    ValueError and need no GPU; the object itself lives on cuda:device."""
+
+    def __init__(self, device=0):
+        if isinstance(device, (bool, np.bool_)) or not isinstance(device, (int, np.integer)) or device < 0:
+            raise ValueError("device=%r: a device number" % (device,))
+        self.device = int(device)
+        _gpu()
+        err = C.c_int(0)
+        self._h = N.lw_select_create(self.device, C.byref(err))
+        if not self._h:
+            raise RuntimeError("lw_select_create failed (%d): %s" % (err.value, N.device_error()))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            N.lw_select_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        if N is not None and getattr(N, "lw_select_destroy", None) is not None:  # not during interpreter shutdown
+            self.close()
+
+    @property
+    def tile_frames(self):
+        """frames of a tile (lw_select_tile_frames)"""
+        return N.lw_select_tile_frames(self._h)
+
+    def set_tile_frames(self, m):
+        """a test's handle on the seams (lw_select_set_tile_frames): a multiple of 256 in 256 .. 2048; the result does not depend on it"""
+        if N.lw_select_set_tile_frames(self._h, int(m)):
+            raise ValueError("tile_frames=%r: a multiple of 256 in 256 .. 2048" % (m,))
+
+    def last_launches(self):
+        """kernels the last call queued: 2 per 65535 rows, 1 where no row has a frame, 0 when nothing was to be written; -1: no
+        call yet"""
+        return N.lw_select_last_launches(self._h)
+
+    def run(self, feats, frames, mask, out=None, fill_to=None, stream=None):
+        """lw_select_rows: of the frames[i] frames of row i of feats (float32 [rows][C][F][capacity]), those whose mask (torch.bool or
+        uint8 [rows][C][capacity]) is set -> the front of every line of out (None: a zeroed tensor of feats' shape; never feats
+        itself), K of them per row and channel; positions [K, max(frames[i], fill_to[i])) of every line receive 0.  fill_to: None,
+        one count for all rows or one per row.  Nothing else of out is written.  stream: a hipStream_t value; None = torch's
+        current stream on the object's device.  Asynchronous; returns (out, counts), counts a torch.int64 [rows][C] tensor ON THE
+        DEVICE that holds K once the stream has reached it."""
+        torch = _gpu()
+        if out is None:
+            out = torch.zeros_like(feats)
+        for t, what in ((feats, "feats"), (out, "out")):
+            if t.dtype != torch.float32 or t.device.type != "cuda" or t.device.index != self.device or not t.is_contiguous() or t.dim() != 4:
+                raise ValueError("%s must be a contiguous float32 tensor [rows][C][F][capacity] on cuda:%d" % (what, self.device))
+        if tuple(out.shape) != tuple(feats.shape):
+            raise ValueError("out must have feats' shape %r, not %r" % (tuple(feats.shape), tuple(out.shape)))
+        if out.data_ptr() == feats.data_ptr() and feats.numel():
+            raise ValueError("out must not be feats: the pass has no in-place form")
+        n_rows, ch, F, cap = feats.shape
+        if (mask.dtype not in (torch.bool, torch.uint8) or mask.device != feats.device or not mask.is_contiguous() or
+                tuple(mask.shape) != (n_rows, ch, cap)):
+            raise ValueError("mask must be a contiguous bool or uint8 tensor %r on feats' device" % ((n_rows, ch, cap),))
+        counts, fill = _row_counts(frames, n_rows, "frames"), _row_fill(fill_to, n_rows)
+        kept = torch.empty((n_rows, ch), dtype=torch.int64, device=feats.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream or None
+        rc = N.lw_select_rows(self._h, ch, F, C.c_void_p(feats.data_ptr()), C.c_void_p(mask.data_ptr()), C.c_void_p(out.data_ptr()),
+                              C.c_void_p(kept.data_ptr()), n_rows, cap, counts.ctypes.data_as(C.c_void_p),
+                              None if fill is None else fill.ctypes.data_as(C.c_void_p), stream)
+        if rc in (N.ERR_NULL_ARG, N.ERR_CAPACITY, N.ERR_UNSUPPORTED):
+            raise ValueError("lw_select_rows refused the call (%d)" % rc)
+        if rc:
+            raise RuntimeError("lw_select_rows: %d %s" % (rc, N.device_error()))
+        return out, kept
+
+
 CEP_MAX_IN, CEP_MAX_OUT, CEP_MAX_WIDTH = 256, 256, 16     # LW_CEP_MAX_IN, LW_CEP_MAX_OUT, LW_CEP_MAX_WIDTH
 
 
