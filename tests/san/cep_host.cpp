@@ -13,8 +13,6 @@
 //                                   elements behind a 16-byte boundary and have a guarded front.  "RC rc", "LAUNCHES n", "TILE n"
 #include "../../include/lewton_amd.h"
 
-#include <sanitizer/asan_interface.h>
-
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -22,18 +20,12 @@
 #include <vector>
 
 #include "hip_standins.inc"
+#include "kernel_host.hpp"
 
 #define LW_CEP_HOST 1
 #include "../../lewton_amd/csrc/lw_kernels_cep.hip"
 
-static int g_launches = 0;
-static std::vector<std::pair<const LwCepRow *, uint32_t>> g_rows; // what each launch was given, looked at again at the end
-static bool g_run = true;
-
-bool lw_hip_ok(hipError_t e, const char *) // (lw_runtime.cpp's, without its thread-local text)
-{
-	return e == hipSuccess;
-}
+static LaunchLog<LwCepRow> g_log;
 
 // one group of one workgroup, as lw_cp_group runs it on the device
 template <int G>
@@ -65,15 +57,12 @@ static void group(const LwCepArgs &a, const LwCpTile &t, const float *mt, const 
 
 hipError_t lw_launch_cep(const LwCepArgs &a, const float *mt, const float *src, float *dst, uint32_t tiles, uint32_t n_rows, hipStream_t)
 {
-	g_launches++;
-	g_rows.emplace_back(a.rows + a.row0, n_rows);
+	g_log.launch(a.rows + a.row0, n_rows);
 	const LwCepPlan p = lw_cep_plan(a.n_out, a.order, a.width);
 	if (!a.rows || n_rows == 0 || n_rows > 65535u || tiles == 0 || !dst || (a.identity ? a.n_in != a.n_out : !mt) || p.tile != a.plan.tile ||
-			p.halo != a.plan.halo || p.group != a.plan.group || p.lds != a.plan.lds || a.mt_stride < ((a.n_out + 31u) & ~31u)) {
-		printf("BAD arguments\n");
-		exit(3);
-	}
-	if (!g_run)
+			p.halo != a.plan.halo || p.group != a.plan.group || p.lds != a.plan.lds || a.mt_stride < ((a.n_out + 31u) & ~31u))
+		bad("arguments");
+	if (!g_log.run)
 		return hipSuccess;
 	float *lds = (float *)malloc(a.plan.lds ? a.plan.lds : 1); // exact size: one float beyond the images is a report
 	for (uint32_t bz = 0; bz < n_rows; bz++)
@@ -98,40 +87,7 @@ hipError_t lw_launch_cep(const LwCepArgs &a, const float *mt, const float *src, 
 	return hipSuccess;
 }
 
-static const uint32_t SENT = 0x7fc0dead; // a NaN with a payload
-
-// A buffer of exactly n elements that starts SHIFT elements behind a 16-byte boundary.  Its END is the allocation's end: one
-// element beyond it is an ASan report.  In FRONT of it lie 32 + 4 SHIFT bytes of the same allocation: they hold a sentinel and are
-// poisoned by hand down to the last 8-byte granule ASan can express; guard_intact() finds a store into what poisoning cannot cover
-static const uint32_t FRONT = 0x7fc0f00du;
-struct Guarded {
-	char *base = nullptr;
-	float *at = nullptr;
-};
-
-static Guarded shifted(size_t n, unsigned shift)
-{
-	Guarded g;
-	const size_t front = 32 + 4 * (size_t)(shift & 3u);
-	g.base = (char *)malloc(front + n * 4);
-	if (!g.base || ((uintptr_t)g.base & 15u))
-		exit(2);
-	g.at = (float *)(g.base + front);
-	for (size_t i = 0; i < front; i += 4)
-		memcpy(g.base + i, &FRONT, 4);
-	ASAN_POISON_MEMORY_REGION(g.base, front & ~(size_t)7);
-	return g;
-}
-
-static bool guard_intact(const Guarded &g)
-{
-	const size_t front = (size_t)((char *)g.at - g.base);
-	ASAN_UNPOISON_MEMORY_REGION(g.base, front);
-	for (size_t i = 0; i < front; i += 4)
-		if (memcmp(g.base + i, &FRONT, 4))
-			return false;
-	return true;
-}
+static const uint32_t SENT = SENT_DEAD;
 
 int main(int argc, char **argv)
 {
@@ -184,12 +140,11 @@ int main(int argc, char **argv)
 		const size_t ns = rows * ch * n_in * cap, nd = rows * ch * n_out * (1 + order) * cap;
 		std::vector<uint64_t> cnt(rows + 1), fill_to(rows + 1);
 		std::vector<float> m((size_t)n_out * n_in);
-		const Guarded gs = shifted(ns, (unsigned)atoi(argv[11])), gd = shifted(nd, (unsigned)atoi(argv[12]));
-		FILE *f = fopen(argv[13], "rb");
-		if (!f || fread(cnt.data(), 8, rows, f) != rows || fread(fill_to.data(), 8, rows, f) != rows || fread(m.data(), 4, m.size(), f) != m.size() ||
-				fread(gs.at, 4, ns, f) != ns)
-			return 2;
-		fclose(f);
+		const Guarded gs = shifted(4 * ns, 4u * (unsigned)atoi(argv[11])), gd = shifted(4 * nd, 4u * (unsigned)atoi(argv[12]));
+		{
+			File in(argv[13], "rb");
+			in.get(cnt.data(), rows), in.get(fill_to.data(), rows), in.get(m.data(), m.size()), in.get(gs.as<float>(), ns);
+		}
 		lw_cep *cp = lw_cep_create(0, n_in, n_out, identity ? nullptr : m.data(), order, width, &err);
 		if (!cp)
 			return 2;
@@ -200,20 +155,14 @@ int main(int argc, char **argv)
 			if (lw_cep_matrix(cp, nullptr) != m.size() || lw_cep_matrix(cp, back.data()) != m.size() || memcmp(&back.back(), &SENT, 4))
 				return 3;
 		}
-		for (size_t i = 0; i < nd; i++)
-			memcpy(gd.at + i, &SENT, 4);
+		fill32(gd.at, nd, SENT);
 		const int rc = lw_cep_rows(cp, ch, gs.at, gd.at, rows, cap, cnt.data(), fill ? fill_to.data() : nullptr, nullptr);
-		printf("RC %d\nLAUNCHES %d\nTILE %u\n", rc, g_launches, lw_cep_tile_frames(cp));
-		if (rc == LW_OK && lw_cep_last_launches(cp) != g_launches)
+		printf("RC %d\nLAUNCHES %d\nTILE %u\n", rc, g_log.launches, lw_cep_tile_frames(cp));
+		if (rc == LW_OK && lw_cep_last_launches(cp) != g_log.launches)
 			return 3;
-		f = fopen(argv[14], "wb");
-		if (!f || fwrite(gd.at, 4, nd, f) != nd)
-			return 2;
-		fclose(f);
-		if (!guard_intact(gs) || !guard_intact(gd)) {
-			printf("BAD a store in front of a buffer\n");
-			return 3;
-		}
+		File(argv[14], "wb").put(gd.as<float>(), nd);
+		if (!guard_intact(gs) || !guard_intact(gd))
+			bad("a store in front of a buffer");
 		free(gs.base), free(gd.base);
 		lw_cep_destroy(cp);
 		return 0;
@@ -226,7 +175,7 @@ int main(int argc, char **argv)
 	const size_t cap = 300;
 	std::vector<float> src(3 * 2 * 5 * cap, 0.25f), dst(3 * 2 * 9 * cap, 0.0f);
 	uint64_t cnt[3] = {300, 0, 4}, fill[3] = {300, 3, 2};
-	g_run = false;
+	g_log.run = false;
 	if (mode == "two") {
 		uint64_t cnt_b[3] = {1, 257, 3};
 		int rc = lw_cep_rows(cp, 2, src.data(), dst.data(), 3, cap, cnt, fill, nullptr);
@@ -234,13 +183,7 @@ int main(int argc, char **argv)
 		cnt[0] = 1, fill[1] = 7; // the first call has copied its arrays: the caller's are free
 		rc = lw_cep_rows(cp, 2, src.data(), dst.data(), 3, cap, cnt_b, nullptr, nullptr);
 		printf("RC %d LAST %d\n", rc, lw_cep_last_launches(cp));
-		for (const auto &g : g_rows) { // queued work reads its records later: they must still be there after the calls behind it
-			printf("ROWS");
-			for (uint32_t i = 0; i < g.second; i++)
-				printf(" %llu/%llu", (unsigned long long)g.first[i].n, (unsigned long long)g.first[i].fill_end);
-			printf("\n");
-		}
-		printf("LAUNCHES %d\n", g_launches);
+		g_log.print([](const LwCepRow &r) { printf(" %llu/%llu", (unsigned long long)r.n, (unsigned long long)r.fill_end); });
 	} else if (mode == "refuse" && argc >= 3) {
 		const std::string cs = argv[2];
 		uint32_t ch = 2;
@@ -286,7 +229,7 @@ int main(int argc, char **argv)
 		} else if (cs != "ok")
 			return 2;
 		const int rc = lw_cep_rows(h, ch, s, d, rows, c, n, fl, nullptr);
-		printf("RC %d\nLAUNCHES %d\nLAST %d\n", rc, g_launches, lw_cep_last_launches(other ? other : cp));
+		printf("RC %d\nLAUNCHES %d\nLAST %d\n", rc, g_log.launches, lw_cep_last_launches(other ? other : cp));
 		lw_cep_destroy(other);
 	} else {
 		return 2;

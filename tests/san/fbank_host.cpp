@@ -28,16 +28,12 @@
 #include <vector>
 
 #include "hip_standins.inc"
+#include "kernel_host.hpp"
 
 #define LW_SPEC_HOST 1
 #include "../../lewton_amd/csrc/lw_kernels_spec.hip"
 
-static int g_launches = 0;
-
-bool lw_hip_ok(hipError_t e, const char *) // (lw_runtime.cpp's, without its thread-local text)
-{
-	return e == hipSuccess;
-}
+static LaunchLog<LwSpecRow> g_log;
 
 static void run_tile(const LwSpecArgs &a, uint32_t bx, uint32_t by, uint32_t bz)
 {
@@ -106,12 +102,10 @@ static void run_tile(const LwSpecArgs &a, uint32_t bx, uint32_t by, uint32_t bz)
 
 hipError_t lw_launch_spec(const LwSpecArgs &a, int route, uint32_t tiles, uint32_t ch, uint32_t n_rows, hipStream_t)
 {
-	g_launches++;
+	g_log.launch();
 	if (!a.rows || !a.basis || (a.n_mels && !a.fb) || route != LW_SP_ROUTE_FMA || ch == 0 || n_rows > 65535u || a.k_pad % LW_SP_KT || a.mel_pad % 32u ||
-			a.pad_mode > 2u || (a.span && (a.span != (LW_SP_TF - 1u) * a.hop + a.win_length || !lw_spec_span_fits(a.hop, a.win_length)))) {
-		printf("BAD arguments\n");
-		exit(3);
-	}
+			a.pad_mode > 2u || (a.span && (a.span != (LW_SP_TF - 1u) * a.hop + a.win_length || !lw_spec_span_fits(a.hop, a.win_length))))
+		bad("arguments");
 	for (uint32_t bz = 0; bz < n_rows; bz++)
 		for (uint32_t by = 0; by < ch; by++)
 			for (uint32_t bx = 0; bx < tiles; bx++)
@@ -128,30 +122,6 @@ static lw_spec_params params(char **v)
 	p.preemphasis = strtod(v[9], nullptr), p.scale = strtod(v[10], nullptr); // ("nan" and "inf" are read as such)
 	return p;
 }
-
-static std::vector<float> read_f32(const char *path)
-{
-	FILE *f = fopen(path, "rb");
-	if (!f)
-		exit(2);
-	fseek(f, 0, SEEK_END);
-	std::vector<float> v((size_t)ftell(f) / 4);
-	fseek(f, 0, SEEK_SET);
-	if (fread(v.data(), 4, v.size(), f) != v.size())
-		exit(2);
-	fclose(f);
-	return v;
-}
-
-static void write_f32(const char *path, const float *p, size_t n)
-{
-	FILE *f = fopen(path, "wb");
-	if (!f || fwrite(p, 4, n, f) != n)
-		exit(2);
-	fclose(f);
-}
-
-static const uint32_t SENT = 0x7fc0deadu; // a NaN with a payload
 
 int main(int argc, char **argv)
 {
@@ -196,7 +166,7 @@ int main(int argc, char **argv)
 		p.n_mels = (uint32_t)strtoul(rest[0], nullptr, 10);
 		std::vector<float> fb;
 		if (p.n_mels) {
-			fb = read_f32(rest[1]);
+			fb = slurp_f32(rest[1]);
 			if (fb.size() != (size_t)p.n_mels * (p.n_fft / 2 + 1))
 				return 2;
 			p.fb = fb.data();
@@ -210,7 +180,7 @@ int main(int argc, char **argv)
 		for (int i = 6; i < n_rest; i++)
 			len.push_back(strtoull(rest[i], nullptr, 10));
 		const size_t rows = len.size(), cap = (size_t)*std::max_element(len.begin(), len.end()) + 3;
-		const std::vector<float> in = read_f32(rest[4]);
+		const std::vector<float> in = slurp_f32(rest[4]);
 		if (in.size() != rows * ch * cap)
 			return 2;
 		float *src = (float *)malloc(in.size() * 4); // exact size: an index beyond the buffer is an ASan report
@@ -223,11 +193,10 @@ int main(int argc, char **argv)
 			most = std::max(most, lw_spec_frames(sp, l));
 		const size_t F = lw_spec_features(sp), fcap = (size_t)most + 1, dn = (rows + 1) * ch * F * fcap;
 		float *dst = (float *)malloc(dn * 4);
-		for (size_t i = 0; i < dn; i++)
-			memcpy(dst + i, &SENT, 4);
+		fill32(dst, dn, SENT_DEAD);
 		const int rc = lw_spec_rows(sp, itl ? LW_FMT_F32_INTERLEAVED : LW_FMT_F32_PLANAR, ch, src, rows, cap, len.data(), nullptr, dst, rows + 1, fcap, nullptr);
-		printf("RC %d\nF %zu %zu\nLAUNCHES %d\n", rc, F, fcap, g_launches);
-		write_f32(rest[5], dst, dn);
+		printf("RC %d\nF %zu %zu\nLAUNCHES %d\n", rc, F, fcap, g_log.launches);
+		File(rest[5], "wb").put(dst, dn);
 		free(src), free(dst);
 		lw_spec_destroy(sp);
 		return 0;
@@ -240,7 +209,7 @@ int main(int argc, char **argv)
 		std::vector<float> b(lw_spec_basis(sp, nullptr));
 		if (b.size() != (size_t)2 * p.win_length * lw_spec_bins(sp) || lw_spec_basis(sp, b.data()) != b.size())
 			return 3;
-		write_f32(rest[0], b.data(), b.size());
+		File(rest[0], "wb").put(b.data(), b.size());
 	} else if (mode == "frames" && n_rest >= 2) {
 		const bool snip = p.framing == LW_SPEC_FRAMES_KALDI_SNIP;
 		for (uint64_t len = strtoull(rest[0], nullptr, 10); len <= strtoull(rest[1], nullptr, 10); len++) {
@@ -264,7 +233,7 @@ int main(int argc, char **argv)
 		const size_t cap = (size_t)std::max(len[0], len[1]), fcap = (size_t)std::max(lw_spec_frames(sp, len[0]), lw_spec_frames(sp, len[1])), F = lw_spec_features(sp);
 		std::vector<float> x(2 * cap, 0.5f), y(2 * F * fcap + 1, 0.0f);
 		const int rc = lw_spec_rows(sp, LW_FMT_F32_PLANAR, 1, x.data(), 2, cap, len, nullptr, y.data(), 2, fcap, nullptr);
-		printf("RC %d\nLAUNCHES %d\n", rc, g_launches);
+		printf("RC %d\nLAUNCHES %d\n", rc, g_log.launches);
 	} else if (mode == "padmode" && n_rest >= 1) {
 		const int rc = lw_spec_set_pad_mode(sp, atoi(rest[0]));
 		printf("RC %d MODE %d\n", rc, lw_spec_pad_mode(sp));

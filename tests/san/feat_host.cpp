@@ -13,8 +13,6 @@
 //                                   SHIFT elements behind a 16-byte boundary and have a guarded front.  "RC rc", "LAUNCHES n"
 #include "../../include/lewton_amd.h"
 
-#include <sanitizer/asan_interface.h>
-
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -23,28 +21,19 @@
 #include <vector>
 
 #include "hip_standins.inc"
+#include "kernel_host.hpp"
 
 #define LW_FEAT_HOST 1
 #include "../../lewton_amd/csrc/lw_kernels_feat.hip"
 
-static int g_launches = 0;
-static std::vector<std::pair<const LwFeatRow *, uint32_t>> g_rows; // what each launch was given, looked at again at the end
-static bool g_run = true;
-
-bool lw_hip_ok(hipError_t e, const char *) // (lw_runtime.cpp's, without its thread-local text)
-{
-	return e == hipSuccess;
-}
+static LaunchLog<LwFeatRow> g_log;
 
 static void check(const LwFeatArgs &a, uint32_t n_rows, bool fin)
 {
-	g_launches++;
-	g_rows.emplace_back(a.rows + a.row0, n_rows);
+	g_log.launch(a.rows + a.row0, n_rows);
 	if (!a.rows || n_rows == 0 || n_rows > 65535u || !a.plan.tiles || !a.plan.per_wave || (uint64_t)a.plan.runs_per_line * a.F != a.plan.runs ||
-			(uint64_t)a.plan.tiles * a.plan.per_wave * LW_FT_WAVES < a.plan.runs || (!a.final && !a.part) || (fin && a.final)) {
-		printf("BAD arguments\n");
-		exit(3);
-	}
+			(uint64_t)a.plan.tiles * a.plan.per_wave * LW_FT_WAVES < a.plan.runs || (!a.final && !a.part) || (fin && a.final))
+		bad("arguments");
 }
 
 static int32_t wg_max(const std::vector<int32_t> &keys)
@@ -58,7 +47,7 @@ static int32_t wg_max(const std::vector<int32_t> &keys)
 hipError_t lw_launch_feat_log(const LwFeatArgs &a, uint32_t n_rows, hipStream_t)
 {
 	check(a, n_rows, false);
-	if (!g_run)
+	if (!g_log.run)
 		return hipSuccess;
 	std::vector<int32_t> keys(LW_FT_THREADS);
 	for (uint32_t bz = 0; bz < n_rows; bz++)
@@ -77,7 +66,7 @@ hipError_t lw_launch_feat_log(const LwFeatArgs &a, uint32_t n_rows, hipStream_t)
 hipError_t lw_launch_feat_fin(const LwFeatArgs &a, uint32_t n_rows, hipStream_t)
 {
 	check(a, n_rows, true);
-	if (!g_run)
+	if (!g_log.run)
 		return hipSuccess;
 	std::vector<int32_t> keys(LW_FT_THREADS);
 	for (uint32_t bz = 0; bz < n_rows; bz++)
@@ -94,47 +83,12 @@ hipError_t lw_launch_feat_fin(const LwFeatArgs &a, uint32_t n_rows, hipStream_t)
 	return hipSuccess;
 }
 
-static const uint32_t SENT = 0x7fc0dead; // a NaN with a payload
+static const uint32_t SENT = SENT_DEAD;
 
 static lw_feat *make(char **v, int *err, int device = 0)
 {
 	lw_feat_params p{atoi(v[0]), atoi(v[1]), strtof(v[2], nullptr), strtof(v[3], nullptr), strtof(v[4], nullptr), strtof(v[5], nullptr)};
 	return lw_feat_create(device, std::string(v[0]) == "null" ? nullptr : &p, err);
-}
-
-// A buffer of exactly n elements that starts SHIFT elements behind a 16-byte boundary.  Its END is the allocation's end: one
-// element beyond it is an ASan report.  In FRONT of it lie 32 + 4 SHIFT bytes of the same allocation (malloc returns 16-byte
-// boundaries): they hold the sentinel and are poisoned by hand down to the last 8-byte granule ASan can express, so a 16-byte
-// access that began before the first line -- the head group of a line that starts off a boundary -- is a report as well, and
-// guard_intact() finds a store into what poisoning cannot cover
-static const uint32_t FRONT = 0x7fc0f00du;
-struct Guarded {
-	char *base = nullptr;
-	float *at = nullptr;
-};
-
-static Guarded shifted(size_t n, unsigned shift)
-{
-	Guarded g;
-	const size_t front = 32 + 4 * (size_t)(shift & 3u);
-	g.base = (char *)malloc(front + n * 4);
-	if (!g.base || ((uintptr_t)g.base & 15u))
-		exit(2);
-	g.at = (float *)(g.base + front);
-	for (size_t i = 0; i < front; i += 4)
-		memcpy(g.base + i, &FRONT, 4);
-	ASAN_POISON_MEMORY_REGION(g.base, front & ~(size_t)7);
-	return g;
-}
-
-static bool guard_intact(const Guarded &g)
-{
-	const size_t front = (size_t)((char *)g.at - g.base);
-	ASAN_UNPOISON_MEMORY_REGION(g.base, front);
-	for (size_t i = 0; i < front; i += 4)
-		if (memcmp(g.base + i, &FRONT, 4))
-			return false;
-	return true;
 }
 
 int main(int argc, char **argv)
@@ -148,22 +102,10 @@ int main(int argc, char **argv)
 		lw_feat *ft = lw_feat_create(0, &p, &err);
 		if (!ft)
 			return 2;
-		FILE *f = fopen(argv[3], "rb");
-		if (!f)
-			return 2;
-		fseek(f, 0, SEEK_END);
-		const size_t n = (size_t)ftell(f) / 4;
-		fseek(f, 0, SEEK_SET);
-		std::vector<float> x(n + 1);
-		if (fread(x.data(), 4, n, f) != n)
-			return 2;
-		fclose(f);
-		for (size_t i = 0; i < n; i++)
-			x[i] = lw_feat_log(ft, x[i]);
-		f = fopen(argv[4], "wb");
-		if (!f || fwrite(x.data(), 4, n, f) != n)
-			return 2;
-		fclose(f);
+		std::vector<float> x = slurp_f32(argv[3]);
+		for (auto &v : x)
+			v = lw_feat_log(ft, v);
+		File(argv[4], "wb").put(x.data(), x.size());
 		lw_feat_destroy(ft);
 		return 0;
 	}
@@ -185,29 +127,25 @@ int main(int argc, char **argv)
 		const int scope = atoi(argv[3]);
 		const size_t n = rows * ch * F * cap, nm = rows * (scope == LW_FEAT_SCOPE_CHANNEL ? ch : 1);
 		std::vector<uint64_t> nf(rows + 1), ft_to(rows + 1);
-		const Guarded gs = shifted(n, (unsigned)atoi(argv[15])), gd = inplace ? gs : shifted(n, (unsigned)atoi(argv[16])), gm = shifted(nm, 0);
-		float *src = gs.at, *dst = gd.at, *mx = gm.at;
-		FILE *f = fopen(argv[17], "rb");
-		if (!f || fread(nf.data(), 8, rows, f) != rows || fread(ft_to.data(), 8, rows, f) != rows || fread(src, 4, n, f) != n)
-			return 2;
-		fclose(f);
-		if (!inplace)
-			for (size_t i = 0; i < n; i++)
-				memcpy(dst + i, &SENT, 4);
-		for (size_t i = 0; i < nm; i++)
-			memcpy(mx + i, &SENT, 4);
-		const int rc = lw_feat_rows(ft, ch, F, src, dst, rows, cap, nf.data(), fill ? ft_to.data() : nullptr, want_max ? mx : nullptr, nullptr);
-		printf("RC %d\nLAUNCHES %d\n", rc, g_launches);
-		if (rc == LW_OK && lw_feat_last_launches(ft) != g_launches)
-			return 3;
-		f = fopen(argv[18], "wb");
-		if (!f || fwrite(dst, 4, n, f) != n || fwrite(mx, 4, nm, f) != nm)
-			return 2;
-		fclose(f);
-		if (!guard_intact(gs) || !guard_intact(gd) || !guard_intact(gm)) {
-			printf("BAD a store in front of a buffer\n");
-			return 3;
+		const Guarded gs = shifted(4 * n, 4u * (unsigned)atoi(argv[15])), gd = inplace ? gs : shifted(4 * n, 4u * (unsigned)atoi(argv[16])), gm = shifted(4 * nm, 0);
+		float *src = gs.as<float>(), *dst = gd.as<float>(), *mx = gm.as<float>();
+		{
+			File in(argv[17], "rb");
+			in.get(nf.data(), rows), in.get(ft_to.data(), rows), in.get(src, n);
 		}
+		if (!inplace)
+			fill32(dst, n, SENT);
+		fill32(mx, nm, SENT);
+		const int rc = lw_feat_rows(ft, ch, F, src, dst, rows, cap, nf.data(), fill ? ft_to.data() : nullptr, want_max ? mx : nullptr, nullptr);
+		printf("RC %d\nLAUNCHES %d\n", rc, g_log.launches);
+		if (rc == LW_OK && lw_feat_last_launches(ft) != g_log.launches)
+			return 3;
+		{
+			File out(argv[18], "wb");
+			out.put(dst, n), out.put(mx, nm);
+		}
+		if (!guard_intact(gs) || !guard_intact(gd) || !guard_intact(gm))
+			bad("a store in front of a buffer");
 		free(gs.base), free(gm.base);
 		if (!inplace)
 			free(gd.base);
@@ -222,7 +160,7 @@ int main(int argc, char **argv)
 	const size_t cap = 9;
 	std::vector<float> buf(3 * 2 * 5 * cap, 0.25f), mx(3, 0.0f);
 	uint64_t nf[3] = {9, 0, 4}, fill[3] = {9, 3, 2};
-	g_run = false;
+	g_log.run = false;
 	if (mode == "two") {
 		uint64_t nf_b[3] = {1, 2, 3};
 		int rc = lw_feat_rows(ft, 2, 5, buf.data(), buf.data(), 3, cap, nf, fill, nullptr, nullptr);
@@ -230,13 +168,7 @@ int main(int argc, char **argv)
 		nf[0] = 1, fill[1] = 7; // the first call has copied its arrays: the caller's are free
 		rc = lw_feat_rows(ft, 2, 5, buf.data(), buf.data(), 3, cap, nf_b, nullptr, nullptr, nullptr);
 		printf("RC %d LAST %d\n", rc, lw_feat_last_launches(ft));
-		for (const auto &g : g_rows) { // queued work reads its records later: they must still be there after the calls behind it
-			printf("ROWS");
-			for (uint32_t i = 0; i < g.second; i++)
-				printf(" %llu/%llu", (unsigned long long)g.first[i].n_frames, (unsigned long long)g.first[i].fill_end);
-			printf("\n");
-		}
-		printf("LAUNCHES %d\n", g_launches);
+		g_log.print([](const LwFeatRow &r) { printf(" %llu/%llu", (unsigned long long)r.n_frames, (unsigned long long)r.fill_end); });
 	} else if (mode == "refuse" && argc >= 3) {
 		const std::string cs = argv[2];
 		uint32_t ch = 2, F = 5;
@@ -283,7 +215,7 @@ int main(int argc, char **argv)
 		else if (cs != "ok")
 			return 2;
 		const int rc = lw_feat_rows(h, ch, F, s, d, rows, c, n, fl, m, nullptr);
-		printf("RC %d\nLAUNCHES %d\nLAST %d\n", rc, g_launches, lw_feat_last_launches(ft));
+		printf("RC %d\nLAUNCHES %d\nLAST %d\n", rc, g_log.launches, lw_feat_last_launches(ft));
 	} else {
 		return 2;
 	}

@@ -17,19 +17,8 @@
 #include <vector>
 
 #include "hip_standins.inc"
-
-static std::vector<uint8_t> slurp(const char *path)
-{
-	std::vector<uint8_t> data;
-	FILE *f = fopen(path, "rb");
-	if (!f)
-		return data;
-	uint8_t buf[65536];
-	for (size_t k; (k = fread(buf, 1, sizeof buf, f)) > 0;)
-		data.insert(data.end(), buf, buf + k);
-	fclose(f);
-	return data;
-}
+#define KERNEL_HOST_NO_HIP_OK 1 // (lw_runtime.cpp is linked)
+#include "kernel_host.hpp"
 
 static std::vector<std::vector<uint8_t>> split_packets(const std::vector<uint8_t> &d)
 {

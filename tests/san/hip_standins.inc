@@ -1,7 +1,10 @@
-// Stand-ins for the HIP runtime and the kernel launchers, for GPU-less harnesses of the product's HOST code
-// (tools/micro/batch_host_bench.cpp, tests/san/ogg_stream_host.cpp): device memory = calloc, copies = memcpy, kernels =
-// no-ops, so everything the host decides (statuses, sample counts, offsets, staging records, container logic) is real
-// and every sample value is zero.  Test infrastructure only -- never linked into liblewton_amd.so.
+// Stand-ins for the HIP runtime and the kernel launchers, for GPU-less harnesses of the product's HOST code: device memory =
+// calloc, copies = memcpy, kernels = no-ops, so everything the host decides (statuses, sample counts, offsets, staging records,
+// container logic) is real and every sample value is zero.  Included by tools/micro/batch_host_bench.cpp and by every program of
+// tests/san/ that links product sources which call HIP (all but stage_host.cpp, which keeps books of its own stand-ins, and the
+// programs without HIP code: dev_entropy_host, host_fuzz, ogg_fuzz).  The programs that run a KERNEL source on the CPU supply
+// that pass's launcher themselves and put kernel_host.hpp on top of this file.  Test infrastructure only -- never linked into
+// liblewton_amd.so.
 #include "../../lewton_amd/csrc/lw_fast.hpp"
 #include "../../lewton_amd/csrc/lw_kernels.hpp"
 

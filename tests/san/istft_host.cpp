@@ -23,17 +23,12 @@
 #include <vector>
 
 #include "hip_standins.inc"
+#include "kernel_host.hpp"
 
 #define LW_ISTFT_HOST 1
 #include "../../lewton_amd/csrc/lw_kernels_istft.hip"
 
-static int g_launches = 0;
-static bool g_run = true;
-
-bool lw_hip_ok(hipError_t e, const char *) // (lw_runtime.cpp's, without its thread-local text)
-{
-	return e == hipSuccess;
-}
+static LaunchLog<LwIstftRow> g_log;
 
 static void run_tile(const LwIstftArgs &a, uint32_t bx, uint32_t by, uint32_t bz)
 {
@@ -69,13 +64,11 @@ static void run_tile(const LwIstftArgs &a, uint32_t bx, uint32_t by, uint32_t bz
 
 hipError_t lw_launch_istft(const LwIstftArgs &a, int route, uint32_t tiles, uint32_t ch, uint32_t n_rows, hipStream_t)
 {
-	g_launches++;
+	g_log.launch();
 	if (!a.rows || !a.table || !a.w2 || (route != 0 && route != 1) || ch == 0 || n_rows > 65535u || a.l_pad % LW_IS_KT || tiles > LW_IS_MAX_TILES ||
-			a.m == 0 || (uint64_t)a.m * a.hop > LW_IS_SPAN_MAX || a.m + (a.win_length + a.hop - 1u) / a.hop > LW_IS_TF) {
-		printf("BAD arguments\n");
-		exit(3);
-	}
-	if (!g_run)
+			a.m == 0 || (uint64_t)a.m * a.hop > LW_IS_SPAN_MAX || a.m + (a.win_length + a.hop - 1u) / a.hop > LW_IS_TF)
+		bad("arguments");
+	if (!g_log.run)
 		return hipSuccess;
 	for (uint32_t bz = 0; bz < n_rows; bz++)
 		for (uint32_t by = 0; by < ch; by++)
@@ -108,7 +101,7 @@ static bool list(const char *s, std::vector<uint64_t> &out)
 	return true;
 }
 
-static const uint32_t SENT = 0x7fc00abcu; // a NaN with a payload
+static const uint32_t SENT = SENT_ABC;
 
 int main(int argc, char **argv)
 {
@@ -135,14 +128,8 @@ int main(int argc, char **argv)
 		if (g.size() != (size_t)p.lines * u32(argv[3]) || w2.size() != u32(argv[3]) || lw_istft_basis(is, g.data()) != g.size() ||
 				lw_istft_window2(is, w2.data()) != w2.size())
 			return 3;
-		FILE *f = fopen(argv[7], "wb");
-		if (!f || fwrite(g.data(), 4, g.size(), f) != g.size())
-			return 2;
-		fclose(f);
-		f = fopen(argv[8], "wb");
-		if (!f || fwrite(w2.data(), 8, w2.size(), f) != w2.size())
-			return 2;
-		fclose(f);
+		File(argv[7], "wb").put(g.data(), g.size());
+		File(argv[8], "wb").put(w2.data(), w2.size());
 		lw_istft_destroy(is);
 		return 0;
 	}
@@ -187,12 +174,8 @@ int main(int argc, char **argv)
 			return 3;
 		const size_t sn = rows * ch * 2 * lw_istft_bins(is) * fcap, dn = ndst * ch * dcap;
 		float *src = (float *)malloc(sn ? sn * 4 : 4), *dst = (float *)malloc(dn ? dn * 4 : 4); // exact sizes: one element beyond is an ASan report
-		FILE *f = fopen(argv[14], "rb");
-		if (!f || fread(src, 4, sn, f) != sn)
-			return 2;
-		fclose(f);
-		for (size_t i = 0; i < dn; i++)
-			memcpy(dst + i, &SENT, 4);
+		File(argv[14], "rb").get(src, sn);
+		fill32(dst, dn, SENT);
 		std::vector<uint64_t> frames, map64, lens;
 		list(argv[16], frames);
 		const bool has_map = list(argv[17], map64), has_len = list(argv[18], lens);
@@ -201,13 +184,10 @@ int main(int argc, char **argv)
 			return 2;
 		const int rc = lw_istft_rows(is, ch, src, rows, fcap, frames.data(), has_map ? map.data() : nullptr, has_len ? lens.data() : nullptr, fmt, dst, ndst,
 				dcap, nullptr);
-		printf("RC %d\nM %u\nLAUNCHES %d\n", rc, lw_istft_tile_frames(is), g_launches);
-		if (rc == LW_OK && g_launches && lw_istft_last_route(is) != 1)
+		printf("RC %d\nM %u\nLAUNCHES %d\n", rc, lw_istft_tile_frames(is), g_log.launches);
+		if (rc == LW_OK && g_log.launches && lw_istft_last_route(is) != 1)
 			return 3;
-		f = fopen(argv[15], "wb");
-		if (!f || fwrite(dst, 4, dn, f) != dn)
-			return 2;
-		fclose(f);
+		File(argv[15], "wb").put(dst, dn);
 		free(src), free(dst);
 		lw_istft_destroy(is);
 		return 0;
@@ -221,8 +201,7 @@ int main(int argc, char **argv)
 		return 2;
 	const size_t fcap = 9, dcap = 40;
 	std::vector<float> src(3 * 2 * 18 * fcap, 0.25f), dst(4 * 2 * dcap);
-	for (auto &v : dst)
-		memcpy(&v, &SENT, 4);
+	fill32(dst.data(), dst.size(), SENT);
 	uint64_t frames[3] = {9, 0, 5}, lens[3] = {32, 7, 40};
 	uint32_t map[3] = {2, 0, 3};
 	const std::string cs = argv[2];
@@ -271,7 +250,7 @@ int main(int argc, char **argv)
 		fc = (size_t)1 << 62, frames[0] = frames[2] = 0;
 	else if (cs == "bad_route" || cs == "bad_m" || cs == "bad_m0") {
 		rc = cs == "bad_route" ? lw_istft_set_route(is, 2) : lw_istft_set_tile_frames(is, cs == "bad_m" ? lw_istft_tile_frames(is) + 1 : 0);
-		printf("RC %d\nLAUNCHES %d\nWRITTEN 0\n", rc, g_launches);
+		printf("RC %d\nLAUNCHES %d\nWRITTEN 0\n", rc, g_log.launches);
 		lw_istft_destroy(is);
 		return 0;
 	} else if (cs != "ok" && cs != "ok_natural")
@@ -282,7 +261,7 @@ int main(int argc, char **argv)
 	size_t written = 0;
 	for (auto &v : dst)
 		written += memcmp(&v, &SENT, 4) != 0;
-	printf("RC %d\nLAUNCHES %d\nWRITTEN %zu\n", rc, g_launches, written);
+	printf("RC %d\nLAUNCHES %d\nWRITTEN %zu\n", rc, g_log.launches, written);
 	lw_istft_destroy(is);
 	return 0;
 }

@@ -15,8 +15,6 @@
 //                                   "RC rc", "LAUNCHES n"
 #include "../../include/lewton_amd.h"
 
-#include <sanitizer/asan_interface.h>
-
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -25,34 +23,25 @@
 #include <vector>
 
 #include "hip_standins.inc"
+#include "kernel_host.hpp"
 
 #define LW_NORM_HOST 1
 #include "../../lewton_amd/csrc/lw_kernels_norm.hip"
 
-static int g_launches = 0;
-static std::vector<std::pair<const LwNormRow *, uint32_t>> g_rows; // what each launch was given, looked at again at the end
-static bool g_run = true;
-
-bool lw_hip_ok(hipError_t e, const char *) // (lw_runtime.cpp's, without its thread-local text)
-{
-	return e == hipSuccess;
-}
+static LaunchLog<LwNormRow> g_log;
 
 static void check(const LwNormArgs &a, uint32_t n_rows, bool ok)
 {
-	g_launches++;
-	g_rows.emplace_back(a.rows + a.row0, n_rows);
-	if (!a.rows || n_rows == 0 || n_rows > 65535u || (uint64_t)a.plan.scopes * a.plan.scope_lines != (uint64_t)a.ch * a.F || !ok) {
-		printf("BAD arguments\n");
-		exit(3);
-	}
+	g_log.launch(a.rows + a.row0, n_rows);
+	if (!a.rows || n_rows == 0 || n_rows > 65535u || (uint64_t)a.plan.scopes * a.plan.scope_lines != (uint64_t)a.ch * a.F || !ok)
+		bad("arguments");
 }
 
 hipError_t lw_launch_norm_sum(const LwNormArgs &a, uint32_t n_rows, hipStream_t)
 {
 	check(a, n_rows, !a.plain && a.src && a.part && a.plan.sum_chunks && a.plan.sum_per_wave &&
 			(uint64_t)a.plan.sum_tiles * a.plan.sum_per_wave * LW_NM_WAVES >= (uint64_t)a.ch * a.F * a.plan.sum_chunks);
-	if (!g_run)
+	if (!g_log.run)
 		return hipSuccess;
 	for (uint32_t bz = 0; bz < n_rows; bz++)
 		for (uint32_t bx = 0; bx < a.plan.sum_tiles; bx++)
@@ -64,7 +53,7 @@ hipError_t lw_launch_norm_sum(const LwNormArgs &a, uint32_t n_rows, hipStream_t)
 hipError_t lw_launch_norm_fold(const LwNormArgs &a, uint32_t n_rows, hipStream_t)
 {
 	check(a, n_rows, a.sc && (a.plan.fold_wave || (a.scratch && a.plan.fold_scratch)));
-	if (!g_run)
+	if (!g_log.run)
 		return hipSuccess;
 	for (uint32_t bz = 0; bz < n_rows; bz++) {
 		if (a.plan.fold_wave) {
@@ -91,7 +80,7 @@ hipError_t lw_launch_norm_apply(const LwNormArgs &a, uint32_t n_rows, hipStream_
 {
 	check(a, n_rows, (a.plain || a.sc) && a.plan.tiles && a.plan.per_wave && (uint64_t)a.plan.runs_per_line * a.F == a.plan.runs &&
 			(uint64_t)a.plan.tiles * a.plan.per_wave * LW_NM_WAVES >= a.plan.runs);
-	if (!g_run)
+	if (!g_log.run)
 		return hipSuccess;
 	for (uint32_t bz = 0; bz < n_rows; bz++)
 		for (uint32_t by = 0; by < a.ch; by++)
@@ -104,48 +93,13 @@ hipError_t lw_launch_norm_apply(const LwNormArgs &a, uint32_t n_rows, hipStream_
 	return hipSuccess;
 }
 
-static const uint32_t SENT = 0x7fc0dead; // a NaN with a payload
+static const uint32_t SENT = SENT_DEAD;
 
 static lw_norm *make(const char *center, const char *scale, const char *scope, const char *reserved, const char *eps, const char *target, int *err,
 		int device = 0)
 {
 	lw_norm_params p{atoi(center), atoi(scale), atoi(scope), atoi(reserved), strtod(eps, nullptr), strtod(target, nullptr)};
 	return lw_norm_create(device, std::string(center) == "null" ? nullptr : &p, err);
-}
-
-// A buffer of exactly n elements that starts SHIFT elements behind a 16-byte boundary.  Its END is the allocation's end: one
-// element beyond it is an ASan report.  In FRONT of it lie 32 + 4 SHIFT bytes of the same allocation (malloc returns 16-byte
-// boundaries): they hold the sentinel and are poisoned by hand down to the last 8-byte granule ASan can express, so a 16-byte
-// access that began before the first line -- the head group of a line that starts off a boundary -- is a report as well, and
-// guard_intact() finds a store into what poisoning cannot cover
-static const uint32_t FRONT = 0x7fc0f00du;
-struct Guarded {
-	char *base = nullptr;
-	float *at = nullptr;
-};
-
-static Guarded shifted(size_t n, unsigned shift)
-{
-	Guarded g;
-	const size_t front = 32 + 4 * (size_t)(shift & 3u);
-	g.base = (char *)malloc(front + n * 4);
-	if (!g.base || ((uintptr_t)g.base & 15u))
-		exit(2);
-	g.at = (float *)(g.base + front);
-	for (size_t i = 0; i < front; i += 4)
-		memcpy(g.base + i, &FRONT, 4);
-	ASAN_POISON_MEMORY_REGION(g.base, front & ~(size_t)7);
-	return g;
-}
-
-static bool guard_intact(const Guarded &g)
-{
-	const size_t front = (size_t)((char *)g.at - g.base);
-	ASAN_UNPOISON_MEMORY_REGION(g.base, front);
-	for (size_t i = 0; i < front; i += 4)
-		if (memcmp(g.base + i, &FRONT, 4))
-			return false;
-	return true;
 }
 
 int main(int argc, char **argv)
@@ -158,25 +112,22 @@ int main(int argc, char **argv)
 		lw_norm *nm = make(argv[2], argv[3], "0", "0", argv[4], argv[5], &err);
 		if (!nm)
 			return 2;
-		FILE *f = fopen(argv[6], "rb");
+		File in(argv[6], "rb");
 		uint64_t k = 0;
-		if (!f || fread(&k, 8, 1, f) != 1)
-			return 2;
+		in.get(&k, 1);
 		std::vector<double> s1(k), s2(k), m(k), g(k);
 		std::vector<uint64_t> cnt(k);
 		std::vector<float> pk(k);
-		if (fread(s1.data(), 8, k, f) != k || fread(s2.data(), 8, k, f) != k || fread(cnt.data(), 8, k, f) != k || fread(pk.data(), 4, k, f) != k)
-			return 2;
-		fclose(f);
+		in.get(s1.data(), k), in.get(s2.data(), k), in.get(cnt.data(), k), in.get(pk.data(), k);
+		in.close();
 		for (uint64_t i = 0; i < k; i++)
 			if (lw_norm_scalars(nm, s1[i], s2[i], pk[i], cnt[i], &m[i], &g[i]) != LW_OK)
 				return 3;
 		if (lw_norm_scalars(nullptr, 0, 0, 0, 1, &m[0], &g[0]) != LW_ERR_NULL_ARG || lw_norm_scalars(nm, 0, 0, 0, 1, nullptr, &g[0]) != LW_ERR_NULL_ARG)
 			return 3;
-		f = fopen(argv[7], "wb");
-		if (!f || fwrite(m.data(), 8, k, f) != k || fwrite(g.data(), 8, k, f) != k)
-			return 2;
-		fclose(f);
+		File out(argv[7], "wb");
+		out.put(m.data(), k), out.put(g.data(), k);
+		out.close();
 		lw_norm_destroy(nm);
 		return 0;
 	}
@@ -198,29 +149,28 @@ int main(int argc, char **argv)
 		const bool inplace = atoi(argv[11]) != 0, want_stats = atoi(argv[12]) != 0, fill = atoi(argv[13]) != 0;
 		const size_t n = rows * ch * F * cap, ns = 2 * rows * (scope == LW_NORM_SCOPE_ROW ? 1 : scope == LW_NORM_SCOPE_CHANNEL ? ch : ch * F);
 		std::vector<uint64_t> cnt(rows + 1), fill_to(rows + 1);
-		const Guarded gs = shifted(n, (unsigned)atoi(argv[14])), gd = inplace ? gs : shifted(n, (unsigned)atoi(argv[15]));
-		float *src = gs.at, *dst = gd.at;
+		const Guarded gs = shifted(4 * n, 4u * (unsigned)atoi(argv[14])), gd = inplace ? gs : shifted(4 * n, 4u * (unsigned)atoi(argv[15]));
+		float *src = gs.as<float>(), *dst = gd.as<float>();
 		double *stats = (double *)malloc(ns * 8); // exact size: one double beyond it is a report
-		FILE *f = fopen(argv[16], "rb");
-		if (!stats || !f || fread(cnt.data(), 8, rows, f) != rows || fread(fill_to.data(), 8, rows, f) != rows || fread(src, 4, n, f) != n)
+		if (!stats)
 			return 2;
-		fclose(f);
+		{
+			File in(argv[16], "rb");
+			in.get(cnt.data(), rows), in.get(fill_to.data(), rows), in.get(src, n);
+		}
 		if (!inplace)
-			for (size_t i = 0; i < n; i++)
-				memcpy(dst + i, &SENT, 4);
+			fill32(dst, n, SENT);
 		memset(stats, 0xee, ns * 8);
 		const int rc = lw_norm_rows(nm, ch, F, src, dst, rows, cap, cnt.data(), fill ? fill_to.data() : nullptr, want_stats ? stats : nullptr, nullptr);
-		printf("RC %d\nLAUNCHES %d\n", rc, g_launches);
-		if (rc == LW_OK && lw_norm_last_launches(nm) != g_launches)
+		printf("RC %d\nLAUNCHES %d\n", rc, g_log.launches);
+		if (rc == LW_OK && lw_norm_last_launches(nm) != g_log.launches)
 			return 3;
-		f = fopen(argv[17], "wb");
-		if (!f || fwrite(dst, 4, n, f) != n || fwrite(stats, 8, ns, f) != ns)
-			return 2;
-		fclose(f);
-		if (!guard_intact(gs) || !guard_intact(gd)) {
-			printf("BAD a store in front of a buffer\n");
-			return 3;
+		{
+			File out(argv[17], "wb");
+			out.put(dst, n), out.put(stats, ns);
 		}
+		if (!guard_intact(gs) || !guard_intact(gd))
+			bad("a store in front of a buffer");
 		free(gs.base), free(stats);
 		if (!inplace)
 			free(gd.base);
@@ -236,7 +186,7 @@ int main(int argc, char **argv)
 	std::vector<float> buf(3 * 2 * 5 * cap, 0.25f);
 	std::vector<double> stats(3 * 2 * 2, 0.0);
 	uint64_t cnt[3] = {300, 0, 4}, fill[3] = {300, 3, 2};
-	g_run = false;
+	g_log.run = false;
 	if (mode == "two") {
 		uint64_t cnt_b[3] = {1, 257, 3};
 		int rc = lw_norm_rows(nm, 2, 5, buf.data(), buf.data(), 3, cap, cnt, fill, nullptr, nullptr);
@@ -244,13 +194,7 @@ int main(int argc, char **argv)
 		cnt[0] = 1, fill[1] = 7; // the first call has copied its arrays: the caller's are free
 		rc = lw_norm_rows(nm, 2, 5, buf.data(), buf.data(), 3, cap, cnt_b, nullptr, nullptr, nullptr);
 		printf("RC %d LAST %d\n", rc, lw_norm_last_launches(nm));
-		for (const auto &g : g_rows) { // queued work reads its records later: they must still be there after the calls behind it
-			printf("ROWS");
-			for (uint32_t i = 0; i < g.second; i++)
-				printf(" %llu/%llu/%u", (unsigned long long)g.first[i].n, (unsigned long long)g.first[i].fill_end, g.first[i].chunks);
-			printf("\n");
-		}
-		printf("LAUNCHES %d\n", g_launches);
+		g_log.print([](const LwNormRow &r) { printf(" %llu/%llu/%u", (unsigned long long)r.n, (unsigned long long)r.fill_end, r.chunks); });
 	} else if (mode == "refuse" && argc >= 3) {
 		const std::string cs = argv[2];
 		uint32_t ch = 2, F = 5;
@@ -309,7 +253,7 @@ int main(int argc, char **argv)
 		} else if (cs != "ok")
 			return 2;
 		const int rc = lw_norm_rows(h, ch, F, s, d, rows, c, n, fl, st, nullptr);
-		printf("RC %d\nLAUNCHES %d\nLAST %d\n", rc, g_launches, lw_norm_last_launches(plain ? plain : nm));
+		printf("RC %d\nLAUNCHES %d\nLAST %d\n", rc, g_log.launches, lw_norm_last_launches(plain ? plain : nm));
 		lw_norm_destroy(plain);
 	} else {
 		return 2;

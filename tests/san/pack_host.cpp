@@ -16,8 +16,6 @@
 //                                   and have a guarded front.  "RC rc", "LAUNCHES n", "TILE n", "VEC v" (the last launch's)
 #include "../../include/lewton_amd.h"
 
-#include <sanitizer/asan_interface.h>
-
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -26,19 +24,13 @@
 #include <vector>
 
 #include "hip_standins.inc"
+#include "kernel_host.hpp"
 
 #define LW_PACK_HOST 1
 #include "../../lewton_amd/csrc/lw_kernels_pack.hip"
 
-static int g_launches = 0;
+static LaunchLog<LwPackRow> g_log;
 static uint32_t g_vec = 0;
-static std::vector<std::pair<const LwPackRow *, uint32_t>> g_rows; // what each launch was given, looked at again at the end
-static bool g_run = true;
-
-bool lw_hip_ok(hipError_t e, const char *) // (lw_runtime.cpp's, without its thread-local text)
-{
-	return e == hipSuccess;
-}
 
 // one workgroup, as lw_pk_block runs it on the device
 template <int E>
@@ -62,17 +54,14 @@ static void block(const LwPackArgs &a, const LwPkTile &t, const uint32_t *src, v
 
 hipError_t lw_launch_pack(const LwPackArgs &a, const float *src, void *dst, uint8_t *mask, uint32_t tiles, uint32_t n_rows, hipStream_t)
 {
-	g_launches++;
+	g_log.launch(a.rows + a.row0, n_rows);
 	g_vec = a.vec;
-	g_rows.emplace_back(a.rows + a.row0, n_rows);
 	const LwPackPlan p = lw_pack_plan(a.F, a.W, a.stride);
 	const uint32_t E = a.dtype == LW_PK_F32 ? 4u : 8u;
 	if (!a.rows || n_rows == 0 || n_rows > 65535u || tiles == 0 || tiles > LW_PK_MAX_TILES || !dst || a.D != a.W * a.F || p.tile != a.plan.tile ||
-			p.pitch != a.plan.pitch || p.lines != a.plan.lines || p.lds != a.plan.lds || (a.vec && (a.F % E || ((uintptr_t)dst & 15u)))) {
-		printf("BAD arguments\n");
-		exit(3);
-	}
-	if (!g_run)
+			p.pitch != a.plan.pitch || p.lines != a.plan.lines || p.lds != a.plan.lds || (a.vec && (a.F % E || ((uintptr_t)dst & 15u))))
+		bad("arguments");
+	if (!g_log.run)
 		return hipSuccess;
 	uint32_t *img = (uint32_t *)malloc(a.plan.lds); // exact size: one dword beyond the image is a report
 	for (uint32_t bz = 0; bz < n_rows; bz++)
@@ -93,36 +82,6 @@ hipError_t lw_launch_pack(const LwPackArgs &a, const float *src, void *dst, uint
 			}
 	free(img);
 	return hipSuccess;
-}
-
-// A buffer of exactly `bytes` bytes that starts OFF bytes behind a 16-byte boundary.  Its END is the allocation's end: one byte
-// beyond it is an ASan report.  In FRONT of it lie 32 + OFF bytes of the same allocation: they hold a sentinel and are poisoned by
-// hand down to the last 8-byte granule ASan can express; guard_intact() finds a store into what poisoning cannot cover
-struct Guarded {
-	char *base = nullptr, *at = nullptr;
-};
-
-static Guarded shifted(size_t bytes, unsigned off)
-{
-	Guarded g;
-	const size_t front = 32 + (size_t)(off & 15u);
-	g.base = (char *)malloc(front + bytes);
-	if (!g.base || ((uintptr_t)g.base & 15u))
-		exit(2);
-	g.at = g.base + front;
-	memset(g.base, 0x5a, front);
-	ASAN_POISON_MEMORY_REGION(g.base, front & ~(size_t)7);
-	return g;
-}
-
-static bool guard_intact(const Guarded &g)
-{
-	const size_t front = (size_t)(g.at - g.base);
-	ASAN_UNPOISON_MEMORY_REGION(g.base, front);
-	for (size_t i = 0; i < front; i++)
-		if (g.base[i] != 0x5a)
-			return false;
-	return true;
 }
 
 static lw_pack_params params(char **v) // F LEFT RIGHT STRIDE EDGE DTYPE
@@ -176,23 +135,14 @@ int main(int argc, char **argv)
 		lw_pack_params p{};
 		p.F = 1, p.stride = 1, p.dtype = atoi(argv[2]);
 		lw_pack *pk = lw_pack_create(0, &p, nullptr, nullptr, &err);
-		FILE *f = fopen(argv[3], "rb");
-		if (!pk || !f)
+		if (!pk)
 			return 2;
-		fseek(f, 0, SEEK_END);
-		const size_t n = (size_t)ftell(f) / 4;
-		fseek(f, 0, SEEK_SET);
-		std::vector<float> x(n);
+		const std::vector<float> x = slurp_f32(argv[3]);
+		const size_t n = x.size();
 		std::vector<uint32_t> y(n);
-		if (fread(x.data(), 4, n, f) != n)
-			return 2;
-		fclose(f);
 		for (size_t i = 0; i < n; i++)
 			y[i] = lw_pack_convert(pk, x[i]);
-		f = fopen(argv[4], "wb");
-		if (!f || fwrite(y.data(), 4, n, f) != n)
-			return 2;
-		fclose(f);
+		File(argv[4], "wb").put(y.data(), n);
 		lw_pack_destroy(pk);
 		return 0;
 	}
@@ -205,34 +155,30 @@ int main(int argc, char **argv)
 		std::vector<uint64_t> cnt(rows + 1), fill_to(rows + 1);
 		std::vector<float> shift(D), scale(D);
 		const Guarded gs = shifted(ns, (unsigned)atoi(argv[16])), gd = shifted(nd, (unsigned)atoi(argv[17])), gm = shifted(nm, 3);
-		FILE *f = fopen(argv[18], "rb");
-		if (!f || fread(cnt.data(), 8, rows, f) != rows || fread(fill_to.data(), 8, rows, f) != rows || fread(shift.data(), 4, D, f) != D ||
-				fread(scale.data(), 4, D, f) != D || fread(&p.pad, 4, 1, f) != 1 || fread(gs.at, 1, ns, f) != ns)
-			return 2;
-		fclose(f);
+		{
+			File in(argv[18], "rb");
+			in.get(cnt.data(), rows), in.get(fill_to.data(), rows), in.get(shift.data(), D), in.get(scale.data(), D), in.get(&p.pad, 1);
+			in.get(gs.at, ns);
+		}
 		lw_pack *pk = lw_pack_create(0, &p, sh ? shift.data() : nullptr, sc ? scale.data() : nullptr, &err);
 		if (!pk)
 			return 2;
 		std::fill(shift.begin(), shift.end(), 0.0f), std::fill(scale.begin(), scale.end(), 0.0f); // copied at creation: the caller's are free
 		if (es == 4)
-			for (size_t i = 0; i < nd / 4; i++)
-				((uint32_t *)gd.at)[i] = 0x7fc0deadu;
+			fill32(gd.at, nd / 4, SENT_DEAD);
 		else
-			for (size_t i = 0; i < nd / 2; i++)
-				((uint16_t *)gd.at)[i] = 0x7fadu;
+			fill16(gd.at, nd / 2, SENT_HALF);
 		memset(gm.at, 0xa5, nm);
 		const int rc = lw_pack_rows(pk, ch, gs.at, gd.at, rows, cap, ocap, cnt.data(), fill ? fill_to.data() : nullptr, mk ? (uint8_t *)gm.at : nullptr, nullptr);
-		printf("RC %d\nLAUNCHES %d\nTILE %u\nVEC %u\n", rc, g_launches, lw_pack_tile_frames(pk), g_vec);
-		if (rc == LW_OK && lw_pack_last_launches(pk) != g_launches)
+		printf("RC %d\nLAUNCHES %d\nTILE %u\nVEC %u\n", rc, g_log.launches, lw_pack_tile_frames(pk), g_vec);
+		if (rc == LW_OK && lw_pack_last_launches(pk) != g_log.launches)
 			return 3;
-		f = fopen(argv[19], "wb");
-		if (!f || fwrite(gd.at, 1, nd, f) != nd || fwrite(gm.at, 1, nm, f) != nm)
-			return 2;
-		fclose(f);
-		if (!guard_intact(gs) || !guard_intact(gd) || !guard_intact(gm)) {
-			printf("BAD a store in front of a buffer\n");
-			return 3;
+		{
+			File out(argv[19], "wb");
+			out.put(gd.at, nd), out.put(gm.at, nm);
 		}
+		if (!guard_intact(gs) || !guard_intact(gd) || !guard_intact(gm))
+			bad("a store in front of a buffer");
 		free(gs.base), free(gd.base), free(gm.base);
 		lw_pack_destroy(pk);
 		return 0;
@@ -248,7 +194,7 @@ int main(int argc, char **argv)
 	std::vector<uint16_t> dst(3 * 2 * ocap * 35, 0);
 	std::vector<uint8_t> msk(3 * ocap, 0);
 	uint64_t cnt[3] = {300, 0, 4}, fill[3] = {60, 3, 0};
-	g_run = false;
+	g_log.run = false;
 	if (mode == "two") {
 		uint64_t cnt_b[3] = {1, 257, 13};
 		int rc = lw_pack_rows(pk, 2, src.data(), dst.data(), 3, cap, ocap, cnt, fill, msk.data(), nullptr);
@@ -256,13 +202,7 @@ int main(int argc, char **argv)
 		cnt[0] = 1, fill[1] = 7; // the first call has copied its arrays: the caller's are free
 		rc = lw_pack_rows(pk, 2, src.data(), dst.data(), 3, cap, ocap, cnt_b, nullptr, nullptr, nullptr);
 		printf("RC %d LAST %d\n", rc, lw_pack_last_launches(pk));
-		for (const auto &g : g_rows) { // queued work reads its records later: they must still be there after the calls behind it
-			printf("ROWS");
-			for (uint32_t i = 0; i < g.second; i++)
-				printf(" %llu/%llu/%llu", (unsigned long long)g.first[i].n, (unsigned long long)g.first[i].n_out, (unsigned long long)g.first[i].fill_end);
-			printf("\n");
-		}
-		printf("LAUNCHES %d\n", g_launches);
+		g_log.print([](const LwPackRow &r) { printf(" %llu/%llu/%llu", (unsigned long long)r.n, (unsigned long long)r.n_out, (unsigned long long)r.fill_end); });
 	} else if (mode == "refuse" && argc >= 3) {
 		const std::string cs = argv[2];
 		uint32_t ch = 2;
@@ -314,7 +254,7 @@ int main(int argc, char **argv)
 		} else if (cs != "ok")
 			return 2;
 		const int rc = lw_pack_rows(h, ch, s, d, rows, c, oc, n, fl, msk.data(), nullptr);
-		printf("RC %d\nLAUNCHES %d\nLAST %d\n", rc, g_launches, lw_pack_last_launches(other ? other : pk));
+		printf("RC %d\nLAUNCHES %d\nLAST %d\n", rc, g_log.launches, lw_pack_last_launches(other ? other : pk));
 		lw_pack_destroy(other);
 	} else {
 		return 2;

@@ -21,13 +21,12 @@
 #include <vector>
 
 #include "hip_standins.inc"
+#include "kernel_host.hpp"
 
 #define LW_RESAMPLE_HOST 1
 #include "../../lewton_amd/csrc/lw_kernels_resample.hip"
 
-static int g_launches = 0;
-static std::vector<std::pair<const LwResampleRow *, uint32_t>> g_rows; // what each launch was given, looked at again at the end
-static bool g_run = true;
+static LaunchLog<LwResampleRow> g_log;
 static std::vector<std::pair<uint32_t, uint32_t>> g_tiles; // (tile0, tiles) of each launch
 
 template <int ROUTE, int J> static void run_tile(const LwResampleArgs &a, const LwResamplePlan &p, uint32_t bx, uint32_t by, uint32_t bz)
@@ -45,21 +44,13 @@ template <int ROUTE, int J> static void run_tile(const LwResampleArgs &a, const 
 	free(lds);
 }
 
-bool lw_hip_ok(hipError_t e, const char *) // (lw_runtime.cpp's, without its thread-local text)
-{
-	return e == hipSuccess;
-}
-
 hipError_t lw_launch_resample(const LwResampleArgs &a, const LwResamplePlan &p, uint32_t tiles, uint32_t ch, uint32_t n_rows, hipStream_t)
 {
-	g_launches++;
-	g_rows.emplace_back(a.rows + a.row0, n_rows);
+	g_log.launch(a.rows + a.row0, n_rows);
 	g_tiles.emplace_back(a.tile0, tiles);
-	if (!a.rows || !a.taps || p.lds_floats > LW_RS_LDS_FLOATS || p.blocks != a.blocks || ch == 0 || n_rows > 65535u || tiles > LW_RS_MAX_TILES) {
-		printf("BAD arguments\n");
-		exit(3);
-	}
-	if (!g_run)
+	if (!a.rows || !a.taps || p.lds_floats > LW_RS_LDS_FLOATS || p.blocks != a.blocks || ch == 0 || n_rows > 65535u || tiles > LW_RS_MAX_TILES)
+		bad("arguments");
+	if (!g_log.run)
 		return hipSuccess;
 	for (uint32_t bz = 0; bz < n_rows; bz++)
 		for (uint32_t by = 0; by < ch; by++)
@@ -116,7 +107,7 @@ static float fold(const std::vector<float> &taps, uint32_t orig, uint32_t new_, 
 
 static const uint32_t PAIRS[][2] = {{44100, 16000}, {48000, 16000}, {44100, 48000}, {16000, 44100}, {22050, 44100}, {48000, 44100},
 	{2000, 1}, {16000, 16000}}; // the last two: the all-global route and the copy
-static const uint32_t SENT = 0x7fc00abcu; // a NaN with a payload
+static const uint32_t SENT = SENT_ABC;
 
 static int kernel_cases(unsigned seed, int cases)
 {
@@ -129,10 +120,8 @@ static int kernel_cases(unsigned seed, int cases)
 		const bool big = pair[0] == 2000;
 		int err = 0;
 		lw_resampler *rs = lw_resampler_create(0, pair[0], pair[1], window || big ? (big ? 6 : 16) : 6, 0.99, big ? 0 : window, 14.769656459379492, &err);
-		if (!rs) {
-			printf("BAD create %d\n", err);
-			return 3;
-		}
+		if (!rs)
+			bad("create %d", err);
 		uint32_t orig, new_, W, K;
 		lw_resampler_geometry(rs, &orig, &new_, &W, &K);
 		std::vector<float> taps(lw_resampler_taps(rs, nullptr));
@@ -168,12 +157,7 @@ static int kernel_cases(unsigned seed, int cases)
 		// exact-size buffers: one element beyond either is an ASan report
 		const size_t sn = (size_t)rows * ch * scap, dn = (size_t)(rows + extra) * ch * dcap;
 		float *src = (float *)malloc(sn * 4), *dst = (float *)malloc(dn * 4), *want = (float *)malloc(dn * 4);
-		for (size_t i = 0; i < sn; i++)
-			memcpy(src + i, &SENT, 4);
-		for (size_t i = 0; i < dn; i++) {
-			memcpy(dst + i, &SENT, 4);
-			memcpy(want + i, &SENT, 4);
-		}
+		fill32(src, sn, SENT), fill32(dst, dn, SENT), fill32(want, dn, SENT);
 		std::uniform_real_distribution<float> uni(-1.0f, 1.0f);
 		for (uint32_t r = 0; r < rows; r++)
 			for (uint32_t q = 0; q < ch; q++) {
@@ -199,10 +183,8 @@ static int kernel_cases(unsigned seed, int cases)
 		if (rc != LW_OK)
 			return 3;
 		for (size_t i = 0; i < dn; i++)
-			if (bits(dst[i]) != bits(want[i])) {
-				printf("BAD element %zu: %08x, expected %08x\n", i, bits(dst[i]), bits(want[i]));
-				return 3;
-			}
+			if (bits(dst[i]) != bits(want[i]))
+				bad("element %zu: %08x, expected %08x", i, bits(dst[i]), bits(want[i]));
 		free(src), free(dst), free(want);
 		lw_resampler_destroy(rs);
 		done++;
@@ -236,10 +218,7 @@ int main(int argc, char **argv)
 			std::vector<float> taps(lw_resampler_taps(rs, nullptr));
 			if (taps.size() != (size_t)new_ * K || lw_resampler_taps(rs, taps.data()) != taps.size())
 				return 3;
-			FILE *f = fopen(argv[8], "wb");
-			if (!f || fwrite(taps.data(), 4, taps.size(), f) != taps.size())
-				return 2;
-			fclose(f);
+			File(argv[8], "wb").put(taps.data(), taps.size());
 		} else if (mode == "outlen") {
 			for (int i = 8; i < argc; i++) {
 				const uint64_t len = strtoull(argv[i], nullptr, 10);
@@ -292,20 +271,14 @@ int main(int argc, char **argv)
 	uint64_t len[3] = {1000, 0, 441};
 	uint32_t map[3] = {2, 0, 3};
 	if (mode == "two") {
-		g_run = false;
+		g_log.run = false;
 		uint64_t len_b[3] = {7, 8, 9};
 		int rc = lw_resample_rows(rs, LW_FMT_F32_PLANAR, 2, src.data(), 3, scap, len, map, dst.data(), 4, dcap, nullptr);
 		printf("RC %d\n", rc);
 		len[0] = 1; // the first call has copied its lengths: the caller's are free
 		rc = lw_resample_rows(rs, LW_FMT_F32_INTERLEAVED, 2, src.data(), 3, scap, len_b, nullptr, dst.data(), 4, dcap, nullptr);
 		printf("RC %d\n", rc);
-		for (const auto &g : g_rows) { // queued work reads its records later: they must still be there after the calls behind it
-			printf("ROWS");
-			for (uint32_t i = 0; i < g.second; i++)
-				printf(" %llu/%llu/%llu", (unsigned long long)g.first[i].len, (unsigned long long)g.first[i].out_len, (unsigned long long)g.first[i].dst_row);
-			printf("\n");
-		}
-		printf("LAUNCHES %d\n", g_launches);
+		g_log.print([](const LwResampleRow &r) { printf(" %llu/%llu/%llu", (unsigned long long)r.len, (unsigned long long)r.out_len, (unsigned long long)r.dst_row); });
 	} else if (mode == "refuse" && argc >= 3) {
 		const std::string cs = argv[2];
 		int fmt = LW_FMT_F32_PLANAR;
@@ -348,14 +321,14 @@ int main(int argc, char **argv)
 			map[1] = 3; // the row without samples names a row another one has
 		else if (cs == "ok_many_tiles") {
 			// one row of 2^37 outputs: more tiles than one launch holds, whatever the plan's tile (nothing runs here, no sample is touched)
-			g_run = false;
+			g_log.run = false;
 			dc = (size_t)1 << 37, len[0] = sc = ((size_t)1 << 37) / 160 * 441, len[1] = len[2] = 0;
 		} else if (cs != "ok" && cs != "ok_exact")
 			return 2;
 		if (cs == "ok_exact")
 			dc = 363, sc = 1000;
 		const int rc = lw_resample_rows(h, fmt, ch, s, 3, sc, l, mp, d, n_dst, dc, nullptr);
-		printf("RC %d\nLAUNCHES %d\n", rc, g_launches);
+		printf("RC %d\nLAUNCHES %d\n", rc, g_log.launches);
 		if (cs == "ok_many_tiles") {
 			uint32_t orig, new_, hw, k;
 			lw_resampler_geometry(rs, &orig, &new_, &hw, &k);

@@ -19,6 +19,8 @@
 #include <vector>
 
 #include "hip_standins.inc"
+#define KERNEL_HOST_NO_HIP_OK 1 // (lw_runtime.cpp is linked)
+#include "kernel_host.hpp"
 
 static uint64_t g_src_elems = 0, g_dst_elems = 0;
 static int g_rows_launches = 0;
@@ -31,32 +33,15 @@ hipError_t lw_launch_rows(const void *d_src, void *d_dst, const LwRowSeg *d_segs
 		g_fail_rows_launch = false;
 		return hipErrorLaunchFailure;
 	}
-	if (!d_src || !d_dst || (elem_size != 2 && elem_size != 4)) {
-		printf("BAD arguments\n");
-		exit(3);
-	}
+	if (!d_src || !d_dst || (elem_size != 2 && elem_size != 4))
+		bad("arguments");
 	for (uint32_t i = 0; i < n_segs; i++) {
 		const LwRowSeg &s = d_segs[i]; // (device memory = calloc here, filled by the hipMemcpyAsync stand-in)
 		printf("S %u %u %llu\n", s.src_elem, s.count, (unsigned long long)s.dst_elem);
-		if (s.count == 0 || (uint64_t)s.src_elem + s.count > g_src_elems || s.dst_elem + s.count > g_dst_elems || s.dst_elem + s.count < s.dst_elem) {
-			printf("BAD piece %u\n", i);
-			exit(3);
-		}
+		if (s.count == 0 || (uint64_t)s.src_elem + s.count > g_src_elems || s.dst_elem + s.count > g_dst_elems || s.dst_elem + s.count < s.dst_elem)
+			bad("piece %u", i);
 	}
 	return hipSuccess;
-}
-
-static std::vector<uint8_t> slurp(const char *path)
-{
-	std::vector<uint8_t> data;
-	FILE *f = fopen(path, "rb");
-	if (!f)
-		return data;
-	uint8_t buf[65536];
-	for (size_t k; (k = fread(buf, 1, sizeof buf, f)) > 0;)
-		data.insert(data.end(), buf, buf + k);
-	fclose(f);
-	return data;
 }
 
 static std::vector<std::vector<uint8_t>> split_packets(const std::vector<uint8_t> &d)

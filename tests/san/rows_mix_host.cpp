@@ -25,6 +25,8 @@
 #include <vector>
 
 #include "hip_standins.inc"
+#define KERNEL_HOST_NO_HIP_OK 1 // (lw_runtime.cpp is linked)
+#include "kernel_host.hpp"
 
 static uint64_t g_src_elems = 0, g_rows = 0;
 static int g_mix_launches = 0, g_rows_launches = 0;
@@ -46,10 +48,8 @@ hipError_t lw_launch_rows_mix(const void *d_src, void *d_dst, const LwRowMixPiec
 		g_fail_mix_launch = false;
 		return hipErrorLaunchFailure;
 	}
-	if (!d_src || !d_dst || !d_pieces || !d_coef || (elem_size != 2 && elem_size != 4) || out_ch == 0 || out_ch > LW_ROWS_MIX_MAX_OUT || in_ch == 0) {
-		printf("BAD arguments\n");
-		exit(3);
-	}
+	if (!d_src || !d_dst || !d_pieces || !d_coef || (elem_size != 2 && elem_size != 4) || out_ch == 0 || out_ch > LW_ROWS_MIX_MAX_OUT || in_ch == 0)
+		bad("arguments");
 	printf("M %u %u %llu %d", out_ch, in_ch, (unsigned long long)row_capacity, interleaved ? 1 : 0);
 	for (uint32_t k = 0; k < out_ch * in_ch; k++) { // (device memory = calloc here, filled by the hipMemcpyAsync stand-in)
 		uint32_t bits;
@@ -67,25 +67,10 @@ hipError_t lw_launch_rows_mix(const void *d_src, void *d_dst, const LwRowMixPiec
 		const uint64_t src_end = interleaved ? p.src_elem + n * in_ch : p.src_elem + (uint64_t)(in_ch - 1) * p.src_stride + n;
 		const uint64_t dst_end = interleaved ? p.dst_elem + n * out_ch : p.dst_elem + (uint64_t)(out_ch - 1) * row_capacity + n;
 		if (n == 0 || n > LW_ROWS_MIX_PIECE || src_end > g_src_elems || dst_end > dst_elems || dst_end < p.dst_elem ||
-				(interleaved ? p.src_stride != 1 : p.src_stride < n)) {
-			printf("BAD piece %u\n", i);
-			exit(3);
-		}
+				(interleaved ? p.src_stride != 1 : p.src_stride < n))
+			bad("piece %u", i);
 	}
 	return hipSuccess;
-}
-
-static std::vector<uint8_t> slurp(const char *path)
-{
-	std::vector<uint8_t> data;
-	FILE *f = fopen(path, "rb");
-	if (!f)
-		return data;
-	uint8_t buf[65536];
-	for (size_t k; (k = fread(buf, 1, sizeof buf, f)) > 0;)
-		data.insert(data.end(), buf, buf + k);
-	fclose(f);
-	return data;
 }
 
 static std::vector<std::vector<uint8_t>> split_packets(const std::vector<uint8_t> &d)

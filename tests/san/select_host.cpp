@@ -19,8 +19,6 @@
 //                                   kept whole, so the kept frames land from position BASE on.  OUT: f32 [F][KEEP], then u64 K
 #include "../../include/lewton_amd.h"
 
-#include <sanitizer/asan_interface.h>
-
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -28,27 +26,19 @@
 #include <vector>
 
 #include "hip_standins.inc"
+#include "kernel_host.hpp"
 
 #define LW_SELECT_HOST 1
 #include "../../lewton_amd/csrc/lw_kernels_select.hip"
 
-static int g_launches = 0;
-static std::vector<std::pair<const LwSelectRow *, uint32_t>> g_rows; // what each k_select launch was given, looked at again at the end
-static bool g_run = true;
+static LaunchLog<LwSelectRow> g_log; // (the records of the k_select launches)
 static uint64_t g_from_frame = 0; // far: the tiles in front of this frame are not run and count as kept whole
-
-bool lw_hip_ok(hipError_t e, const char *) // (lw_runtime.cpp's, without its thread-local text)
-{
-	return e == hipSuccess;
-}
 
 static void check(const LwSelectArgs &a, uint32_t n_rows)
 {
 	if (!a.rows || !a.tile_counts || n_rows == 0 || n_rows > 65535u || !lw_select_tile_ok(a.tile) || a.tiles == 0 ||
-			a.groups != (a.F + LW_SE_LINES - 1u) / LW_SE_LINES || (uint64_t)a.tiles * a.groups > LW_SE_MAX_TILES) {
-		printf("BAD arguments\n");
-		exit(3);
-	}
+			a.groups != (a.F + LW_SE_LINES - 1u) / LW_SE_LINES || (uint64_t)a.tiles * a.groups > LW_SE_MAX_TILES)
+		bad("arguments");
 }
 
 #define LANES(stmt) \
@@ -57,13 +47,11 @@ static void check(const LwSelectArgs &a, uint32_t n_rows)
 
 hipError_t lw_launch_select_count(const LwSelectArgs &a, const uint8_t *mask, uint32_t n_rows, hipStream_t)
 {
-	g_launches++;
+	g_log.launch();
 	check(a, n_rows);
-	if (!mask) {
-		printf("BAD arguments\n");
-		exit(3);
-	}
-	if (!g_run)
+	if (!mask)
+		bad("arguments");
+	if (!g_log.run)
 		return hipSuccess;
 	LwSeLds *l = (LwSeLds *)malloc(sizeof(LwSeLds));
 	for (uint32_t bz = 0; bz < n_rows; bz++)
@@ -88,10 +76,9 @@ hipError_t lw_launch_select_count(const LwSelectArgs &a, const uint8_t *mask, ui
 
 hipError_t lw_launch_select(const LwSelectArgs &a, const uint32_t *src, const uint8_t *mask, uint32_t *dst, uint32_t n_rows, hipStream_t)
 {
-	g_launches++;
-	g_rows.emplace_back(a.rows + a.row0, n_rows);
+	g_log.launch(a.rows + a.row0, n_rows);
 	check(a, n_rows);
-	if (!g_run)
+	if (!g_log.run)
 		return hipSuccess;
 	LwSeLds *l = (LwSeLds *)malloc(sizeof(LwSeLds));
 	for (uint32_t bz = 0; bz < n_rows; bz++)
@@ -120,36 +107,6 @@ hipError_t lw_launch_select(const LwSelectArgs &a, const uint32_t *src, const ui
 			}
 	free(l);
 	return hipSuccess;
-}
-
-// A buffer of exactly `bytes` bytes that starts OFF bytes behind a 16-byte boundary.  Its END is the allocation's end: one byte
-// beyond it is an ASan report.  In FRONT of it lie 32 + OFF bytes of the same allocation: they hold a sentinel and are poisoned by
-// hand down to the last 8-byte granule ASan can express; guard_intact() finds a store into what poisoning cannot cover
-struct Guarded {
-	char *base = nullptr, *at = nullptr;
-};
-
-static Guarded shifted(size_t bytes, unsigned off)
-{
-	Guarded g;
-	const size_t front = 32 + (size_t)(off & 15u);
-	g.base = (char *)malloc(front + bytes);
-	if (!g.base || ((uintptr_t)g.base & 15u))
-		exit(2);
-	g.at = g.base + front;
-	memset(g.base, 0x5a, front);
-	ASAN_POISON_MEMORY_REGION(g.base, front & ~(size_t)7);
-	return g;
-}
-
-static bool guard_intact(const Guarded &g)
-{
-	const size_t front = (size_t)(g.at - g.base);
-	ASAN_UNPOISON_MEMORY_REGION(g.base, front);
-	for (size_t i = 0; i < front; i++)
-		if (g.base[i] != 0x5a)
-			return false;
-	return true;
 }
 
 int main(int argc, char **argv)
@@ -186,30 +143,26 @@ int main(int argc, char **argv)
 		const size_t nm = rows * ch * cap, nb = nm * F * 4, nc = rows * ch * 8;
 		std::vector<uint64_t> cnt(rows + 1), fill_to(rows + 1);
 		const Guarded gs = shifted(nb, (unsigned)atoi(argv[9])), gd = shifted(nb, (unsigned)atoi(argv[10])), gm = shifted(nm, 3), gc = shifted(nc, 8);
-		FILE *f = fopen(argv[11], "rb");
-		if (!f || fread(cnt.data(), 8, rows, f) != rows || fread(fill_to.data(), 8, rows, f) != rows || fread(gm.at, 1, nm, f) != nm ||
-				fread(gs.at, 1, nb, f) != nb)
-			return 2;
-		fclose(f);
+		{
+			File in(argv[11], "rb");
+			in.get(cnt.data(), rows), in.get(fill_to.data(), rows), in.get(gm.at, nm), in.get(gs.at, nb);
+		}
 		lw_select *se = lw_select_create(0, &err);
 		if (!se || lw_select_set_tile_frames(se, tile) != LW_OK)
 			return 2;
-		for (size_t i = 0; i < nb / 4; i++)
-			((uint32_t *)gd.at)[i] = 0x7fc0deadu;
+		fill32(gd.at, nb / 4, SENT_DEAD);
 		memset(gc.at, 0xee, nc);
 		const int rc = lw_select_rows(se, ch, F, gs.at, (const uint8_t *)gm.at, gd.at, want_counts ? (uint64_t *)gc.at : nullptr, rows, cap, cnt.data(),
 				fill ? fill_to.data() : nullptr, nullptr);
-		printf("RC %d\nLAUNCHES %d\nTILE %u\n", rc, g_launches, lw_select_tile_frames(se));
-		if (rc == LW_OK && lw_select_last_launches(se) != g_launches)
+		printf("RC %d\nLAUNCHES %d\nTILE %u\n", rc, g_log.launches, lw_select_tile_frames(se));
+		if (rc == LW_OK && lw_select_last_launches(se) != g_log.launches)
 			return 3;
-		f = fopen(argv[12], "wb");
-		if (!f || fwrite(gd.at, 1, nb, f) != nb || fwrite(gc.at, 1, nc, f) != nc)
-			return 2;
-		fclose(f);
-		if (!guard_intact(gs) || !guard_intact(gd) || !guard_intact(gm) || !guard_intact(gc)) {
-			printf("BAD a store in front of a buffer\n");
-			return 3;
+		{
+			File out(argv[12], "wb");
+			out.put(gd.at, nb), out.put(gc.at, nc);
 		}
+		if (!guard_intact(gs) || !guard_intact(gd) || !guard_intact(gm) || !guard_intact(gc))
+			bad("a store in front of a buffer");
 		free(gs.base), free(gd.base), free(gm.base), free(gc.base);
 		lw_select_destroy(se);
 		return 0;
@@ -219,12 +172,13 @@ int main(int argc, char **argv)
 		const uint64_t base = strtoull(argv[4], nullptr, 10), keep = strtoull(argv[5], nullptr, 10), T = base + keep;
 		std::vector<uint8_t> m((size_t)keep);
 		std::vector<float> x((size_t)(F * keep)), y((size_t)(F * keep));
-		FILE *f = fopen(argv[6], "rb");
-		if (base % tile || !f || fread(m.data(), 1, m.size(), f) != m.size() || fread(x.data(), 4, x.size(), f) != x.size())
+		if (base % tile)
 			return 2;
-		fclose(f);
-		for (auto &v : y)
-			memcpy(&v, "\xad\xde\xc0\x7f", 4);
+		{
+			File in(argv[6], "rb");
+			in.get(m.data(), m.size()), in.get(x.data(), x.size());
+		}
+		fill32(y.data(), y.size(), SENT_DEAD);
 		lw_select *se = lw_select_create(0, &err);
 		if (!se || lw_select_set_tile_frames(se, tile) != LW_OK)
 			return 2;
@@ -240,14 +194,14 @@ int main(int argc, char **argv)
 			else if (K != K0)
 				return 3;
 		}
-		printf("RC %d\nLAUNCHES %d\n", rc, g_launches);
+		printf("RC %d\nLAUNCHES %d\n", rc, g_log.launches);
 		if (K < base)
 			return 3;
 		K -= base;
-		f = fopen(argv[7], "wb");
-		if (!f || fwrite(y.data(), 4, y.size(), f) != y.size() || fwrite(&K, 8, 1, f) != 1)
-			return 2;
-		fclose(f);
+		{
+			File out(argv[7], "wb");
+			out.put(y.data(), y.size()), out.put(&K, 1);
+		}
 		lw_select_destroy(se);
 		return 0;
 	}
@@ -260,7 +214,7 @@ int main(int argc, char **argv)
 	std::vector<uint8_t> msk(3 * 2 * cap, 1);
 	std::vector<uint64_t> counts(3 * 2, 77);
 	uint64_t cnt[3] = {3000, 0, 4}, fill[3] = {3000, 3, 0};
-	g_run = false;
+	g_log.run = false;
 	if (mode == "two") {
 		uint64_t cnt_b[3] = {1, 257, 13};
 		int rc = lw_select_rows(se, 2, 5, src.data(), msk.data(), dst.data(), counts.data(), 3, cap, cnt, fill, nullptr);
@@ -268,13 +222,7 @@ int main(int argc, char **argv)
 		cnt[0] = 1, fill[1] = 7; // the first call has copied its arrays: the caller's are free
 		rc = lw_select_rows(se, 2, 5, src.data(), msk.data(), dst.data(), nullptr, 3, cap, cnt_b, nullptr, nullptr);
 		printf("RC %d LAST %d\n", rc, lw_select_last_launches(se));
-		for (const auto &g : g_rows) { // queued work reads its records later: they must still be there after the calls behind it
-			printf("ROWS");
-			for (uint32_t i = 0; i < g.second; i++)
-				printf(" %llu/%llu", (unsigned long long)g.first[i].n, (unsigned long long)g.first[i].fill_end);
-			printf("\n");
-		}
-		printf("LAUNCHES %d\n", g_launches);
+		g_log.print([](const LwSelectRow &r) { printf(" %llu/%llu", (unsigned long long)r.n, (unsigned long long)r.fill_end); });
 	} else if (mode == "refuse" && argc >= 3) {
 		const std::string cs = argv[2];
 		uint32_t ch = 2, F = 5;
@@ -323,7 +271,7 @@ int main(int argc, char **argv)
 		else if (cs != "ok")
 			return 2;
 		const int rc = lw_select_rows(h, ch, F, s, mk, d, counts.data(), rows, c, n, fl, nullptr);
-		printf("RC %d\nLAUNCHES %d\nLAST %d\n", rc, g_launches, lw_select_last_launches(se));
+		printf("RC %d\nLAUNCHES %d\nLAST %d\n", rc, g_log.launches, lw_select_last_launches(se));
 		printf("COUNTS");
 		for (uint64_t v : counts)
 			printf(" %llu", (unsigned long long)v);

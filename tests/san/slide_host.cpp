@@ -20,8 +20,6 @@
 //                                   (sentinel where nothing ran).  BASE is past 2^32: the offsets of a tile far up a row.
 #include "../../include/lewton_amd.h"
 
-#include <sanitizer/asan_interface.h>
-
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -30,19 +28,13 @@
 #include <vector>
 
 #include "hip_standins.inc"
+#include "kernel_host.hpp"
 
 #define LW_SLIDE_HOST 1
 #include "../../lewton_amd/csrc/lw_kernels_slide.hip"
 
-static int g_launches = 0;
-static std::vector<std::pair<const LwSlideRow *, uint32_t>> g_rows; // what each launch was given, looked at again at the end
-static bool g_run = true;
+static LaunchLog<LwSlideRow> g_log;
 static uint64_t g_from_frame = 0; // far: only tiles that start at or beyond this frame are run
-
-bool lw_hip_ok(hipError_t e, const char *) // (lw_runtime.cpp's, without its thread-local text)
-{
-	return e == hipSuccess;
-}
 
 template <bool NV>
 static void block(const LwSlideArgs &a, const LwSlTile &t, const float *src, float *dst, double *bs, float *xf)
@@ -63,16 +55,13 @@ static void block(const LwSlideArgs &a, const LwSlTile &t, const float *src, flo
 
 hipError_t lw_launch_slide(const LwSlideArgs &a, const float *src, float *dst, uint32_t tiles, uint32_t n_rows, hipStream_t)
 {
-	g_launches++;
-	g_rows.emplace_back(a.rows + a.row0, n_rows);
+	g_log.launch(a.rows + a.row0, n_rows);
 	LwSlidePlan p;
 	if (!a.rows || n_rows == 0 || n_rows > 65535u || tiles == 0 || !dst || !lw_slide_plan(a.F, a.W, a.plan.tile, p) || p.cols != a.plan.cols ||
 			p.pitch != a.plan.pitch || p.nb != a.plan.nb || p.lines != a.plan.lines || p.lds != a.plan.lds || p.lds > LW_SL_LDS_BUDGET ||
-			a.groups != (a.F + p.lines - 1u) / p.lines || (uint64_t)tiles * a.groups > LW_SL_MAX_TILES) {
-		printf("BAD arguments\n");
-		exit(3);
-	}
-	if (!g_run)
+			a.groups != (a.F + p.lines - 1u) / p.lines || (uint64_t)tiles * a.groups > LW_SL_MAX_TILES)
+		bad("arguments");
+	if (!g_log.run)
 		return hipSuccess;
 	double *bs = (double *)malloc(a.plan.lds); // exact size: one dword beyond the image is a report
 	float *xf = (float *)(bs + 2u * a.plan.lines * a.plan.nb);
@@ -84,10 +73,8 @@ hipError_t lw_launch_slide(const LwSlideArgs &a, const float *src, float *dst, u
 				LwSlTile t;
 				if (!lw_sl_tile(a, bx, by, bz, t))
 					continue;
-				if (t.len > a.plan.cols) {
-					printf("BAD a span of %u frames in an image of %u\n", t.len, a.plan.cols);
-					exit(3);
-				}
+				if (t.len > a.plan.cols)
+					bad("a span of %u frames in an image of %u", t.len, a.plan.cols);
 				if (a.norm_vars)
 					block<true>(a, t, src, dst, bs, xf);
 				else
@@ -95,36 +82,6 @@ hipError_t lw_launch_slide(const LwSlideArgs &a, const float *src, float *dst, u
 			}
 	free(bs);
 	return hipSuccess;
-}
-
-// A buffer of exactly `bytes` bytes that starts OFF bytes behind a 16-byte boundary.  Its END is the allocation's end: one byte
-// beyond it is an ASan report.  In FRONT of it lie 32 + OFF bytes of the same allocation: they hold a sentinel and are poisoned by
-// hand down to the last 8-byte granule ASan can express; guard_intact() finds a store into what poisoning cannot cover
-struct Guarded {
-	char *base = nullptr, *at = nullptr;
-};
-
-static Guarded shifted(size_t bytes, unsigned off)
-{
-	Guarded g;
-	const size_t front = 32 + (size_t)(off & 15u);
-	g.base = (char *)malloc(front + bytes);
-	if (!g.base || ((uintptr_t)g.base & 15u))
-		exit(2);
-	g.at = g.base + front;
-	memset(g.base, 0x5a, front);
-	ASAN_POISON_MEMORY_REGION(g.base, front & ~(size_t)7);
-	return g;
-}
-
-static bool guard_intact(const Guarded &g)
-{
-	const size_t front = (size_t)(g.at - g.base);
-	ASAN_UNPOISON_MEMORY_REGION(g.base, front);
-	for (size_t i = 0; i < front; i++)
-		if (g.base[i] != 0x5a)
-			return false;
-	return true;
 }
 
 static lw_slide_params params(char **v) // W MIN CENTER NORM_VARS
@@ -200,27 +157,21 @@ int main(int argc, char **argv)
 		const size_t nb = rows * ch * F * cap * 4;
 		std::vector<uint64_t> cnt(rows + 1), fill_to(rows + 1);
 		const Guarded gs = shifted(nb, (unsigned)atoi(argv[12])), gd = shifted(nb, (unsigned)atoi(argv[13]));
-		FILE *f = fopen(argv[14], "rb");
-		if (!f || fread(cnt.data(), 8, rows, f) != rows || fread(fill_to.data(), 8, rows, f) != rows || fread(gs.at, 1, nb, f) != nb)
-			return 2;
-		fclose(f);
+		{
+			File in(argv[14], "rb");
+			in.get(cnt.data(), rows), in.get(fill_to.data(), rows), in.get(gs.at, nb);
+		}
 		lw_slide *sl = lw_slide_create(0, &p, &err);
 		if (!sl || lw_slide_set_tile_frames(sl, tile) != LW_OK)
 			return 2;
-		for (size_t i = 0; i < nb / 4; i++)
-			((uint32_t *)gd.at)[i] = 0x7fc0deadu;
+		fill32(gd.at, nb / 4, SENT_DEAD);
 		const int rc = lw_slide_rows(sl, ch, F, gs.at, gd.at, rows, cap, cnt.data(), fill ? fill_to.data() : nullptr, nullptr);
-		printf("RC %d\nLAUNCHES %d\nTILE %u\n", rc, g_launches, lw_slide_tile_frames(sl));
-		if (rc == LW_OK && lw_slide_last_launches(sl) != g_launches)
+		printf("RC %d\nLAUNCHES %d\nTILE %u\n", rc, g_log.launches, lw_slide_tile_frames(sl));
+		if (rc == LW_OK && lw_slide_last_launches(sl) != g_log.launches)
 			return 3;
-		f = fopen(argv[15], "wb");
-		if (!f || fwrite(gd.at, 1, nb, f) != nb)
-			return 2;
-		fclose(f);
-		if (!guard_intact(gs) || !guard_intact(gd)) {
-			printf("BAD a store in front of a buffer\n");
-			return 3;
-		}
+		File(argv[15], "wb").put(gd.at, nb);
+		if (!guard_intact(gs) || !guard_intact(gd))
+			bad("a store in front of a buffer");
 		free(gs.base), free(gd.base);
 		lw_slide_destroy(sl);
 		return 0;
@@ -230,12 +181,8 @@ int main(int argc, char **argv)
 		const uint32_t tile = (uint32_t)atoi(argv[6]), F = (uint32_t)atoi(argv[7]);
 		const uint64_t base = strtoull(argv[8], nullptr, 10), keep = strtoull(argv[9], nullptr, 10), T = base + keep;
 		std::vector<float> x((size_t)(F * keep)), y((size_t)(F * keep));
-		FILE *f = fopen(argv[10], "rb");
-		if (!f || fread(x.data(), 4, x.size(), f) != x.size())
-			return 2;
-		fclose(f);
-		for (auto &v : y)
-			memcpy(&v, "\xad\xde\xc0\x7f", 4);
+		File(argv[10], "rb").get(x.data(), x.size());
+		fill32(y.data(), y.size(), SENT_DEAD);
 		// line g of the row starts g * T elements behind line 0, so only its last `keep` frames are backed by memory: one buffer per
 		// line would be needed for F > 1 with capacity T, so the row has capacity T and the lines are run ONE per call, each with
 		// its pointer moved `base` frames in front of its data
@@ -249,11 +196,8 @@ int main(int argc, char **argv)
 			const uintptr_t s = (uintptr_t)(x.data() + (size_t)g * keep) - (uintptr_t)base * 4u, d = (uintptr_t)(y.data() + (size_t)g * keep) - (uintptr_t)base * 4u;
 			rc = lw_slide_rows(sl, 1, 1, (const void *)s, (void *)d, 1, (size_t)T, &T, nullptr, nullptr);
 		}
-		printf("RC %d\nLAUNCHES %d\nFROM %llu\n", rc, g_launches, (unsigned long long)(g_from_frame - base));
-		f = fopen(argv[11], "wb");
-		if (!f || fwrite(y.data(), 4, y.size(), f) != y.size())
-			return 2;
-		fclose(f);
+		printf("RC %d\nLAUNCHES %d\nFROM %llu\n", rc, g_log.launches, (unsigned long long)(g_from_frame - base));
+		File(argv[11], "wb").put(y.data(), y.size());
 		lw_slide_destroy(sl);
 		return 0;
 	}
@@ -266,7 +210,7 @@ int main(int argc, char **argv)
 	const size_t cap = 700;
 	std::vector<float> src(3 * 2 * 5 * cap, 0.25f), dst(3 * 2 * 5 * cap, 0.0f);
 	uint64_t cnt[3] = {700, 0, 4}, fill[3] = {700, 3, 0};
-	g_run = false;
+	g_log.run = false;
 	if (mode == "two") {
 		uint64_t cnt_b[3] = {1, 257, 13};
 		int rc = lw_slide_rows(sl, 2, 5, src.data(), dst.data(), 3, cap, cnt, fill, nullptr);
@@ -274,13 +218,7 @@ int main(int argc, char **argv)
 		cnt[0] = 1, fill[1] = 7; // the first call has copied its arrays: the caller's are free
 		rc = lw_slide_rows(sl, 2, 5, src.data(), dst.data(), 3, cap, cnt_b, nullptr, nullptr);
 		printf("RC %d LAST %d\n", rc, lw_slide_last_launches(sl));
-		for (const auto &g : g_rows) { // queued work reads its records later: they must still be there after the calls behind it
-			printf("ROWS");
-			for (uint32_t i = 0; i < g.second; i++)
-				printf(" %llu/%llu", (unsigned long long)g.first[i].n, (unsigned long long)g.first[i].fill_end);
-			printf("\n");
-		}
-		printf("LAUNCHES %d\n", g_launches);
+		g_log.print([](const LwSlideRow &r) { printf(" %llu/%llu", (unsigned long long)r.n, (unsigned long long)r.fill_end); });
 	} else if (mode == "refuse" && argc >= 3) {
 		const std::string cs = argv[2];
 		uint32_t ch = 2, F = 5;
@@ -328,7 +266,7 @@ int main(int argc, char **argv)
 		else if (cs != "ok")
 			return 2;
 		const int rc = lw_slide_rows(h, ch, F, s, d, rows, c, n, fl, nullptr);
-		printf("RC %d\nLAUNCHES %d\nLAST %d\n", rc, g_launches, lw_slide_last_launches(sl));
+		printf("RC %d\nLAUNCHES %d\nLAST %d\n", rc, g_log.launches, lw_slide_last_launches(sl));
 		for (float v : dst)
 			if (v != 0.0f)
 				return 3; // (nothing runs in this mode; a refusal has written nothing either way)

@@ -16,14 +16,10 @@
 #include <vector>
 
 #include "hip_standins.inc"
+#include "kernel_host.hpp"
 
 #define LW_SPEC_HOST 1
 #include "../../lewton_amd/csrc/lw_kernels_spec.hip"
-
-bool lw_hip_ok(hipError_t e, const char *)
-{
-	return e == hipSuccess;
-}
 
 static void run_tile(const LwSpecArgs &a, uint32_t bx, uint32_t by, uint32_t bz)
 {
@@ -65,10 +61,8 @@ static void run_tile(const LwSpecArgs &a, uint32_t bx, uint32_t by, uint32_t bz)
 
 hipError_t lw_launch_spec(const LwSpecArgs &a, int route, uint32_t tiles, uint32_t ch, uint32_t n_rows, hipStream_t)
 {
-	if (!a.rows || !a.basis || a.n_mels || a.remove_dc || a.energy || a.output > 1u || (route != 0 && route != 1) || a.k_pad % LW_SP_KT) {
-		printf("BAD arguments\n");
-		exit(3);
-	}
+	if (!a.rows || !a.basis || a.n_mels || a.remove_dc || a.energy || a.output > 1u || (route != 0 && route != 1) || a.k_pad % LW_SP_KT)
+		bad("arguments");
 	for (uint32_t bz = 0; bz < n_rows; bz++)
 		for (uint32_t by = 0; by < ch; by++)
 			for (uint32_t bx = 0; bx < tiles; bx++)
@@ -80,8 +74,6 @@ static uint32_t u32(const char *s)
 {
 	return (uint32_t)strtoul(s, nullptr, 10);
 }
-
-static const uint32_t SENT = 0x7fc00abcu;
 
 int main(int argc, char **argv)
 {
@@ -116,34 +108,21 @@ int main(int argc, char **argv)
 	}
 	if (!sp || lw_spec_set_pad_mode(sp, pad) != LW_OK || lw_spec_set_route(sp, LW_SP_ROUTE_FMA) != LW_OK)
 		return 2;
-	FILE *f = fopen(argv[9], "rb");
-	if (!f)
-		return 2;
-	fseek(f, 0, SEEK_END);
-	const size_t n = (size_t)ftell(f) / 4;
-	fseek(f, 0, SEEK_SET);
+	const std::vector<float> in = slurp_f32(argv[9]);
+	const size_t n = in.size();
 	float *x = (float *)malloc(n ? n * 4 : 4); // an exact-size source
-	if (fread(x, 4, n, f) != n)
-		return 2;
-	fclose(f);
+	std::copy(in.begin(), in.end(), x);
 	const uint64_t len = n, frames = lw_spec_frames(sp, len);
 	const uint32_t F = lw_spec_features(sp);
 	const size_t fcap = frames + 1, dn = (size_t)F * fcap;
 	float *y = (float *)malloc(dn * 4); // ... and destination
-	for (size_t i = 0; i < dn; i++)
-		memcpy(y + i, &SENT, 4);
+	fill32(y, dn, SENT_ABC);
 	const int rc = lw_spec_rows(sp, LW_FMT_F32_PLANAR, 1, x, 1, n, &len, nullptr, y, 1, fcap, nullptr);
 	printf("RC %d\nF %u %llu\n", rc, F, (unsigned long long)frames);
-	f = fopen(argv[10], "wb");
-	if (!f || fwrite(y, 4, dn, f) != dn)
-		return 2;
-	fclose(f);
+	File(argv[10], "wb").put(y, dn);
 	std::vector<float> b(lw_spec_basis(sp, nullptr));
 	lw_spec_basis(sp, b.data());
-	f = fopen(argv[11], "wb");
-	if (!f || fwrite(b.data(), 4, b.size(), f) != b.size())
-		return 2;
-	fclose(f);
+	File(argv[11], "wb").put(b.data(), b.size());
 	free(x), free(y);
 	lw_spec_destroy(sp);
 	return 0;

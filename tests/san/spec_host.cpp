@@ -23,19 +23,13 @@
 #include <vector>
 
 #include "hip_standins.inc"
+#include "kernel_host.hpp"
 
 #define LW_SPEC_HOST 1
 #include "../../lewton_amd/csrc/lw_kernels_spec.hip"
 
-static int g_launches = 0;
-static std::vector<std::pair<const LwSpecRow *, uint32_t>> g_rows; // what each launch was given, looked at again at the end
-static bool g_run = true;
+static LaunchLog<LwSpecRow> g_log;
 static std::vector<std::pair<uint32_t, uint32_t>> g_tiles; // (tile0, tiles) of each launch
-
-bool lw_hip_ok(hipError_t e, const char *) // (lw_runtime.cpp's, without its thread-local text)
-{
-	return e == hipSuccess;
-}
 
 static void run_tile(const LwSpecArgs &a, uint32_t bx, uint32_t by, uint32_t bz)
 {
@@ -80,15 +74,12 @@ static void run_tile(const LwSpecArgs &a, uint32_t bx, uint32_t by, uint32_t bz)
 
 hipError_t lw_launch_spec(const LwSpecArgs &a, int route, uint32_t tiles, uint32_t ch, uint32_t n_rows, hipStream_t)
 {
-	g_launches++;
-	g_rows.emplace_back(a.rows + a.row0, n_rows);
+	g_log.launch(a.rows + a.row0, n_rows);
 	g_tiles.emplace_back(a.tile0, tiles);
 	if (!a.rows || !a.basis || (a.n_mels && !a.fb) || (route != 0 && route != 1) || ch == 0 || n_rows > 65535u || a.k_pad % LW_SP_KT || a.mel_pad % 32u ||
-			tiles > LW_SP_MAX_TILES) {
-		printf("BAD arguments\n");
-		exit(3);
-	}
-	if (!g_run)
+			tiles > LW_SP_MAX_TILES)
+		bad("arguments");
+	if (!g_log.run)
 		return hipSuccess;
 	for (uint32_t bz = 0; bz < n_rows; bz++)
 		for (uint32_t by = 0; by < ch; by++)
@@ -148,7 +139,7 @@ static void frame_features(const Shape &s, const std::vector<float> &basis, cons
 	}
 }
 
-static const uint32_t SENT = 0x7fc00abcu; // a NaN with a payload
+static const uint32_t SENT = SENT_ABC;
 
 // the shapes every suite lists, then random ones
 static const Shape LISTED[] = {{400, 400, 160, 0, 1, 80}, {512, 400, 160, 0, 1, 80}, {16, 16, 4, 1, 0, 0}, {25, 25, 7, 0, 1, 0}, {64, 64, 100, 0, 1, 1},
@@ -180,10 +171,8 @@ static int kernel_cases(unsigned seed, int cases)
 			v = rnd(0, 2) == 0 ? 0.0f : std::fabs(uni(rng)) * 0.05f;
 		int err = 0;
 		lw_spec *sp = lw_spec_create(0, s.n_fft, s.win, s.hop, s.window, s.center, s.n_mels, s.n_mels ? fb.data() : nullptr, &err);
-		if (!sp) {
-			printf("BAD create %d\n", err);
-			return 3;
-		}
+		if (!sp)
+			bad("create %d", err);
 		if (lw_spec_set_route(sp, LW_SP_ROUTE_FMA) != LW_OK) // the route this program has
 			return 3;
 		std::vector<float> basis(lw_spec_basis(sp, nullptr));
@@ -223,12 +212,7 @@ static int kernel_cases(unsigned seed, int cases)
 		// exact-size buffers: one element beyond either is an ASan report
 		const size_t sn = (size_t)rows * ch * scap, dn = (size_t)(rows + extra) * ch * F * fcap;
 		float *src = (float *)malloc(sn * 4), *dst = (float *)malloc(dn * 4), *want = (float *)malloc(dn * 4);
-		for (size_t i = 0; i < sn; i++)
-			memcpy(src + i, &SENT, 4);
-		for (size_t i = 0; i < dn; i++) {
-			memcpy(dst + i, &SENT, 4);
-			memcpy(want + i, &SENT, 4);
-		}
+		fill32(src, sn, SENT), fill32(dst, dn, SENT), fill32(want, dn, SENT);
 		std::vector<float> P, out;
 		for (uint32_t r = 0; r < rows; r++)
 			for (uint32_t q = 0; q < ch; q++) {
@@ -255,10 +239,8 @@ static int kernel_cases(unsigned seed, int cases)
 		if (rc != LW_OK)
 			return 3;
 		for (size_t i = 0; i < dn; i++)
-			if (bits(dst[i]) != bits(want[i])) {
-				printf("BAD element %zu: %08x, expected %08x\n", i, bits(dst[i]), bits(want[i]));
-				return 3;
-			}
+			if (bits(dst[i]) != bits(want[i]))
+				bad("element %zu: %08x, expected %08x", i, bits(dst[i]), bits(want[i]));
 		free(src), free(dst), free(want);
 		lw_spec_destroy(sp);
 		done++;
@@ -295,10 +277,7 @@ int main(int argc, char **argv)
 			std::vector<float> b(lw_spec_basis(sp, nullptr));
 			if (b.size() != (size_t)2 * win * p.bins || lw_spec_basis(sp, b.data()) != b.size())
 				return 3;
-			FILE *f = fopen(argv[7], "wb");
-			if (!f || fwrite(b.data(), 4, b.size(), f) != b.size())
-				return 2;
-			fclose(f);
+			File(argv[7], "wb").put(b.data(), b.size());
 		} else if (mode == "frames") {
 			for (int i = 7; i < argc; i++) {
 				const uint64_t len = strtoull(argv[i], nullptr, 10);
@@ -317,24 +296,15 @@ int main(int argc, char **argv)
 				printf("I %llu %lld\n", (unsigned long long)frame, (long long)(lw_sp_index(a, t, (uint32_t)(frame % LW_SP_TF), 0) - (int64_t)p.offset));
 			}
 		} else {
-			FILE *f = fopen(argv[7], "rb");
-			if (!f)
-				return 2;
-			fseek(f, 0, SEEK_END);
-			const size_t n = (size_t)ftell(f) / 4;
-			fseek(f, 0, SEEK_SET);
-			float *x = (float *)malloc(n ? n * 4 : 4);
-			if (fread(x, 4, n, f) != n)
-				return 2;
-			fclose(f);
+			const std::vector<float> in = slurp_f32(argv[7]);
+			const size_t n = in.size();
+			float *x = (float *)malloc(n ? n * 4 : 4); // an exact-size source
+			std::copy(in.begin(), in.end(), x);
 			const uint64_t len = n, frames = lw_spec_frames(sp, len);
 			std::vector<float> y((size_t)p.bins * frames + 1, 0.0f);
 			const int rc = lw_spec_rows(sp, LW_FMT_F32_PLANAR, 1, x, 1, n, &len, nullptr, y.data(), 1, frames, nullptr);
 			printf("RC %d\nF %u %llu\n", rc, p.bins, (unsigned long long)frames);
-			f = fopen(argv[8], "wb");
-			if (!f || fwrite(y.data(), 4, (size_t)p.bins * frames, f) != (size_t)p.bins * frames)
-				return 2;
-			fclose(f);
+			File(argv[8], "wb").put(y.data(), (size_t)p.bins * frames);
 			free(x);
 		}
 		lw_spec_destroy(sp);
@@ -351,20 +321,14 @@ int main(int argc, char **argv)
 	uint64_t len[3] = {1000, 0, 441};
 	uint32_t map[3] = {2, 0, 3};
 	if (mode == "two") {
-		g_run = false;
+		g_log.run = false;
 		uint64_t len_b[3] = {7, 8, 159};
 		int rc = lw_spec_rows(sp, LW_FMT_F32_PLANAR, 2, src.data(), 3, scap, len, map, dst.data(), 4, fcap, nullptr);
 		printf("RC %d\n", rc);
 		len[0] = 1; // the first call has copied its lengths: the caller's are free
 		rc = lw_spec_rows(sp, LW_FMT_F32_INTERLEAVED, 2, src.data(), 3, scap, len_b, nullptr, dst.data(), 4, fcap, nullptr);
 		printf("RC %d\n", rc);
-		for (const auto &g : g_rows) { // queued work reads its records later: they must still be there after the calls behind it
-			printf("ROWS");
-			for (uint32_t i = 0; i < g.second; i++)
-				printf(" %llu/%llu/%llu", (unsigned long long)g.first[i].len, (unsigned long long)g.first[i].n_frames, (unsigned long long)g.first[i].dst_row);
-			printf("\n");
-		}
-		printf("LAUNCHES %d\n", g_launches);
+		g_log.print([](const LwSpecRow &r) { printf(" %llu/%llu/%llu", (unsigned long long)r.len, (unsigned long long)r.n_frames, (unsigned long long)r.dst_row); });
 	} else if (mode == "refuse" && argc >= 3) {
 		const std::string cs = argv[2];
 		int fmt = LW_FMT_F32_PLANAR;
@@ -375,7 +339,7 @@ int main(int argc, char **argv)
 		const uint32_t *mp = map;
 		size_t n_dst = 4, sc = scap, fc = fcap;
 		lw_spec *h = sp;
-		g_run = false;
+		g_log.run = false;
 		if (cs == "null_sp")
 			h = nullptr;
 		else if (cs == "null_len")
@@ -407,7 +371,7 @@ int main(int argc, char **argv)
 		else if (cs == "row_twice_empty")
 			map[1] = 3; // the row without samples names a row another one has
 		else if (cs == "bad_route") {
-			printf("RC %d\nLAUNCHES %d\n", lw_spec_set_route(sp, 2), g_launches);
+			printf("RC %d\nLAUNCHES %d\n", lw_spec_set_route(sp, 2), g_log.launches);
 			lw_spec_destroy(sp);
 			return 0;
 		} else if (cs == "ok_many_tiles") {
@@ -420,7 +384,7 @@ int main(int argc, char **argv)
 		if (cs == "ok_route1" && lw_spec_set_route(sp, 1) != LW_OK)
 			return 3;
 		const int rc = lw_spec_rows(h, fmt, ch, s, 3, sc, l, mp, d, n_dst, fc, nullptr);
-		printf("RC %d\nLAUNCHES %d\n", rc, g_launches);
+		printf("RC %d\nLAUNCHES %d\n", rc, g_log.launches);
 		if (cs == "ok_many_tiles")
 			for (const auto &g : g_tiles)
 				printf("TILES %u %u\n", g.first, g.second);

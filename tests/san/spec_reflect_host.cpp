@@ -24,16 +24,12 @@
 #include <vector>
 
 #include "hip_standins.inc"
+#include "kernel_host.hpp"
 
 #define LW_SPEC_HOST 1
 #include "../../lewton_amd/csrc/lw_kernels_spec.hip"
 
-static int g_launches = 0;
-
-bool lw_hip_ok(hipError_t e, const char *) // (lw_runtime.cpp's, without its thread-local text)
-{
-	return e == hipSuccess;
-}
+static LaunchLog<LwSpecRow> g_log;
 
 static void run_tile(const LwSpecArgs &a, uint32_t bx, uint32_t by, uint32_t bz)
 {
@@ -66,11 +62,9 @@ static void run_tile(const LwSpecArgs &a, uint32_t bx, uint32_t by, uint32_t bz)
 
 hipError_t lw_launch_spec(const LwSpecArgs &a, int route, uint32_t tiles, uint32_t ch, uint32_t n_rows, hipStream_t)
 {
-	g_launches++;
-	if (!a.rows || !a.basis || a.n_mels || route != LW_SP_ROUTE_FMA || ch == 0 || n_rows > 65535u || a.k_pad % LW_SP_KT) {
-		printf("BAD arguments\n");
-		exit(3);
-	}
+	g_log.launch();
+	if (!a.rows || !a.basis || a.n_mels || route != LW_SP_ROUTE_FMA || ch == 0 || n_rows > 65535u || a.k_pad % LW_SP_KT)
+		bad("arguments");
 	for (uint32_t bz = 0; bz < n_rows; bz++)
 		for (uint32_t by = 0; by < ch; by++)
 			for (uint32_t bx = 0; bx < tiles; bx++)
@@ -114,7 +108,7 @@ int main(int argc, char **argv)
 		const size_t cap = (size_t)std::max(len[0], len[1]), fcap = (size_t)lw_spec_frames(sp, cap);
 		std::vector<float> x(2 * cap, 0.5f), y(2 * (size_t)lw_spec_bins(sp) * fcap, 0.0f);
 		const int rc = lw_spec_rows(sp, LW_FMT_F32_PLANAR, 1, x.data(), 2, cap, len, nullptr, y.data(), 2, fcap, nullptr);
-		printf("RC %d\nLAUNCHES %d\n", rc, g_launches);
+		printf("RC %d\nLAUNCHES %d\n", rc, g_log.launches);
 		lw_spec_destroy(sp);
 		return 0;
 	}
@@ -123,10 +117,9 @@ int main(int argc, char **argv)
 		if (!sp)
 			return 3;
 		std::vector<float> b(lw_spec_basis(sp, nullptr));
-		FILE *f = fopen(argv[6], "wb");
-		if (lw_spec_basis(sp, b.data()) != b.size() || !f || fwrite(b.data(), 4, b.size(), f) != b.size())
+		if (lw_spec_basis(sp, b.data()) != b.size())
 			return 2;
-		fclose(f);
+		File(argv[6], "wb").put(b.data(), b.size());
 		lw_spec_destroy(sp);
 		return 0;
 	}
@@ -134,16 +127,10 @@ int main(int argc, char **argv)
 		lw_spec *sp = lw_spec_create(0, n_fft, win, hop, atoi(argv[5]), 1, 0, nullptr, &err);
 		if (!sp || lw_spec_set_route(sp, LW_SP_ROUTE_FMA) != LW_OK)
 			return 3;
-		FILE *f = fopen(argv[7], "rb");
-		if (!f)
-			return 2;
-		fseek(f, 0, SEEK_END);
-		const size_t n = (size_t)ftell(f) / 4;
-		fseek(f, 0, SEEK_SET);
+		const std::vector<float> in = slurp_f32(argv[7]);
+		const size_t n = in.size();
 		float *x = (float *)malloc(n ? n * 4 : 4); // exact size: a reflected index outside [0, len) is an ASan report
-		if (fread(x, 4, n, f) != n)
-			return 2;
-		fclose(f);
+		std::copy(in.begin(), in.end(), x);
 		const uint64_t len = n, frames = lw_spec_frames(sp, len);
 		const size_t B = lw_spec_bins(sp);
 		float *y = (float *)malloc(B * frames ? B * frames * 4 : 4);
@@ -156,10 +143,7 @@ int main(int argc, char **argv)
 			rc = lw_spec_rows(sp, LW_FMT_F32_PLANAR, 1, x, 1, n, &len, nullptr, y, 1, frames, nullptr);
 		}
 		printf("RC %d\nF %zu %llu\n", rc, B, (unsigned long long)frames);
-		f = fopen(argv[8], "wb");
-		if (!f || fwrite(y, 4, B * frames, f) != B * frames)
-			return 2;
-		fclose(f);
+		File(argv[8], "wb").put(y, B * frames);
 		free(x), free(y);
 		lw_spec_destroy(sp);
 		return 0;

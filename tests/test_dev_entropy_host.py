@@ -8,20 +8,18 @@ import subprocess
 
 import pytest
 
+import host_harness as H
 from common import HOST_SETUPS, ROOT
+from host_harness import CS
 from lewton_amd import streamgen as sg
 
-CS = os.path.join(ROOT, "lewton_amd", "csrc")
 SRC = [os.path.join(ROOT, "tests", "san", "dev_entropy_host.cpp")] + [
     os.path.join(CS, n) for n in ("lw_dev_entropy.cpp", "lw_entropy.cpp", "lw_headers.cpp")]
 
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("deventropy") / "dev_entropy_host")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-ffp-contract=off", "-DLW_CHECK_NARROW"] + SRC + ["-o", exe])
-    return exe
+    return H.build(tmp_path_factory, "dev_entropy_host", SRC)
 
 
 def _case(path, setup, pattern, count, **kw):

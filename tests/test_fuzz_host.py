@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import host_harness as H
 from common import FLOOR0_SETUPS, HOST_SETUPS, ROOT, oracle_headers, po, sg
 from lewton_amd import audio, header
 
@@ -51,9 +52,7 @@ def test_host_stage_under_sanitizers(tmp_path):
     exe = tmp_path / "host_fuzz"
     src = os.path.join(ROOT, "tests", "san", "host_fuzz.cpp")
     csrc = os.path.join(ROOT, "lewton_amd", "csrc")
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off", "-DLW_CHECK_NARROW",
-           src, os.path.join(csrc, "lw_headers.cpp"), os.path.join(csrc, "lw_entropy.cpp"), "-o", str(exe)]
-    subprocess.check_call(cmd)
+    H.compile_to(str(exe), [src, os.path.join(csrc, "lw_headers.cpp"), os.path.join(csrc, "lw_entropy.cpp")])
     cases = _cases(5, n_setup_mut=12, n_packet_mut=6)
     blob = bytearray(struct.pack("<I", len(cases)))
     for idp, stp, pks in cases:
@@ -136,8 +135,7 @@ def test_ogg_demultiplexer_under_sanitizers(tmp_path):
     from lewton_amd import ogg
     exe = tmp_path / "ogg_fuzz"
     src = os.path.join(ROOT, "tests", "san", "ogg_fuzz.cpp")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DLW_CHECK_NARROW", src,
-                           "-o", str(exe)])
+    H.compile_to(str(exe), [src])
     rng = np.random.default_rng(31)
     a, b = ogg.PageWriter(21, 9), ogg.PageWriter(22, 2)
     for w, n in ((a, 60), (b, 25)):
@@ -265,9 +263,7 @@ def test_degenerate_setups_under_sanitizers(tmp_path):
     exe = tmp_path / "host_fuzz"
     src = os.path.join(ROOT, "tests", "san", "host_fuzz.cpp")
     csrc = os.path.join(ROOT, "lewton_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-ffp-contract=off", "-DLW_CHECK_NARROW", src, os.path.join(csrc, "lw_headers.cpp"), os.path.join(csrc, "lw_entropy.cpp"),
-                           "-o", str(exe)])
+    H.compile_to(str(exe), [src, os.path.join(csrc, "lw_headers.cpp"), os.path.join(csrc, "lw_entropy.cpp")])
     cases = []
     for name, setup in sorted(_degenerate_setups().items()):
         idp, _cmt, stp = setup.headers()

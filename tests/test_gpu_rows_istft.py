@@ -4,18 +4,13 @@
 The cases are in tests/rows_istft_gpu_cases.py and run ONCE, with pytest, in a process of their own that imports torch first
 (tests/test_gpu_rows.py says why).  Each test below stands for one group of cases of that run (a function of the cases file with
 all its parameters): every case of the group must have passed, and at least one must exist.  No case may skip."""
-import os
-import subprocess
-import sys
-import xml.etree.ElementTree as ET
-
 import pytest
 
-from common import ROOT
+import gpu_child
 
 pytestmark = pytest.mark.gpu
 
-CASES = os.path.join(ROOT, "tests", "rows_istft_gpu_cases.py")
+CASES = "rows_istft_gpu_cases.py"
 GROUPS = ["test_route_0_is_route_1_is_the_model", "test_two_tile_sizes_give_the_same_bits",
           "test_special_values_reach_exactly_the_samples_the_model_says", "test_a_dst_row_permutation_with_a_gap",
           "test_two_objects_queued_back_to_back_on_a_side_stream", "test_refusals_on_the_gpu_write_nothing",
@@ -24,17 +19,7 @@ GROUPS = ["test_route_0_is_route_1_is_the_model", "test_two_tile_sizes_give_the_
 
 @pytest.fixture(scope="module")
 def child(tmp_path_factory):
-    xml = str(tmp_path_factory.mktemp("rows_istft_gpu") / "cases.xml")
-    r = subprocess.run([sys.executable, "-m", "pytest", CASES, "-m", "gpu", "-q", "-rs", "-p", "no:cacheprovider", "--junitxml", xml],
-                       cwd=ROOT, capture_output=True, text=True, timeout=900)
-    print(r.stdout[-6000:])
-    assert os.path.exists(xml), (r.returncode, r.stdout[-3000:], r.stderr[-3000:])
-    groups = {}
-    for tc in ET.parse(xml).getroot().iter("testcase"):
-        name = tc.get("name")
-        bad = [(e.tag, (e.get("message") or "")[:300], (e.text or "")[-3000:]) for e in tc if e.tag in ("failure", "error", "skipped")]
-        groups.setdefault(name.split("[")[0], []).append((name, bad))
-    return groups
+    return gpu_child.run_cases(tmp_path_factory, CASES, "rows_istft_gpu")
 
 
 def test_every_group_of_the_cases_file_is_listed(child):
@@ -43,7 +28,4 @@ def test_every_group_of_the_cases_file_is_listed(child):
 
 @pytest.mark.parametrize("group", GROUPS)
 def test_rows_istft(child, group):
-    cases = child.get(group, [])
-    assert cases, "no case of %s ran" % group
-    failed = [(name, bad) for name, bad in cases if bad]               # a skip counts as a failure here
-    assert not failed, "\n".join("%s: %s\n%s" % (name, bad[0][1], bad[0][2]) for name, bad in failed)
+    gpu_child.check_group(child, group)

@@ -6,18 +6,13 @@ The cases are in tests/rows_large_gpu_cases.py and run ONCE, with pytest, in a p
 (tests/test_gpu_rows.py says why); that process allocates its 38.7 GB of device memory once.  Each test below stands for one group
 of cases of that run (a function of the cases file with all its parameters): every case of the group must have passed, and at
 least one must exist.  No case may skip: too little free device memory is a failure here."""
-import os
-import subprocess
-import sys
-import xml.etree.ElementTree as ET
-
 import pytest
 
-from common import ROOT
+import gpu_child
 
 pytestmark = pytest.mark.gpu
 
-CASES = os.path.join(ROOT, "tests", "rows_large_gpu_cases.py")
+CASES = "rows_large_gpu_cases.py"
 GROUPS = ["test_k_cep_past_2_to_the_32", "test_k_norm_past_2_to_the_32", "test_k_feat_past_2_to_the_32", "test_k_spec_past_2_to_the_32",
           "test_k_resample_past_2_to_the_32", "test_k_rows_mix_past_2_to_the_32", "test_resample_65540_rows", "test_spec_65540_rows",
           "test_feat_65540_rows", "test_norm_65540_rows", "test_norm_65540_rows_workgroup_fold", "test_cep_65540_rows"]
@@ -25,17 +20,7 @@ GROUPS = ["test_k_cep_past_2_to_the_32", "test_k_norm_past_2_to_the_32", "test_k
 
 @pytest.fixture(scope="module")
 def child(tmp_path_factory):
-    xml = str(tmp_path_factory.mktemp("rows_large_gpu") / "cases.xml")
-    r = subprocess.run([sys.executable, "-m", "pytest", CASES, "-m", "gpu", "-q", "-rs", "-s", "-p", "no:cacheprovider", "--durations=8",
-                        "--junitxml", xml], cwd=ROOT, capture_output=True, text=True, timeout=900)
-    print(r.stdout[-6000:])
-    assert os.path.exists(xml), (r.returncode, r.stdout[-3000:], r.stderr[-3000:])
-    groups = {}
-    for tc in ET.parse(xml).getroot().iter("testcase"):
-        name = tc.get("name")
-        bad = [(e.tag, (e.get("message") or "")[:300], (e.text or "")[-3000:]) for e in tc if e.tag in ("failure", "error", "skipped")]
-        groups.setdefault(name.split("[")[0], []).append((name, bad))
-    return groups
+    return gpu_child.run_cases(tmp_path_factory, CASES, "rows_large_gpu", extra_args=("-s", "--durations=8"))
 
 
 def test_every_group_of_the_cases_file_is_listed(child):
@@ -44,7 +29,4 @@ def test_every_group_of_the_cases_file_is_listed(child):
 
 @pytest.mark.parametrize("group", GROUPS)
 def test_rows_large(child, group):
-    cases = child.get(group, [])
-    assert cases, "no case of %s ran" % group
-    failed = [(name, bad) for name, bad in cases if bad]               # a skip counts as a failure here
-    assert not failed, "\n".join("%s: %s\n%s" % (name, bad[0][1], bad[0][2]) for name, bad in failed)
+    gpu_child.check_group(child, group)

@@ -12,35 +12,20 @@ tests/rows_large_gpu_cases.py took 5.9 s for its 70 cases on the same visit.  Pe
 400_160_mel1_reflect 1.45, 400_160_mel1_zero 1.44 (both routes each; most of it is the model's fmaf emulation on the host);
 k_feat two_launches 0.25, the other four 0.02 to 0.03; k_pack 0.20 and 0.14; k_norm 0.08 to 0.12; k_resample 0.02 to 0.09.  A
 kernel's pass over the 17 GB row is 10 to 80 ms."""
-import os
-import subprocess
-import sys
-import xml.etree.ElementTree as ET
-
 import pytest
 
-from common import ROOT
+import gpu_child
 
 pytestmark = pytest.mark.gpu
 
-CASES = os.path.join(ROOT, "tests", "rows_long_row_gpu_cases.py")
+CASES = "rows_long_row_gpu_cases.py"
 GROUPS = ["test_k_resample_inside_a_row_past_2_to_the_32", "test_k_spec_inside_a_row_past_2_to_the_32", "test_k_feat_inside_a_row_past_2_to_the_32",
           "test_k_norm_inside_a_row_past_2_to_the_32", "test_k_pack_inside_a_row_past_2_to_the_32"]
 
 
 @pytest.fixture(scope="module")
 def child(tmp_path_factory):
-    xml = str(tmp_path_factory.mktemp("rows_long_row_gpu") / "cases.xml")
-    r = subprocess.run([sys.executable, "-m", "pytest", CASES, "-m", "gpu", "-q", "-rs", "-s", "-p", "no:cacheprovider", "--durations=0",
-                        "--junitxml", xml], cwd=ROOT, capture_output=True, text=True, timeout=900)
-    print(r.stdout[-8000:])
-    assert os.path.exists(xml), (r.returncode, r.stdout[-3000:], r.stderr[-3000:])
-    groups = {}
-    for tc in ET.parse(xml).getroot().iter("testcase"):
-        name = tc.get("name")
-        bad = [(e.tag, (e.get("message") or "")[:300], (e.text or "")[-3000:]) for e in tc if e.tag in ("failure", "error", "skipped")]
-        groups.setdefault(name.split("[")[0], []).append((name, bad))
-    return groups
+    return gpu_child.run_cases(tmp_path_factory, CASES, "rows_long_row_gpu", extra_args=("-s", "--durations=0"))
 
 
 def test_every_group_of_the_cases_file_is_listed(child):
@@ -49,7 +34,4 @@ def test_every_group_of_the_cases_file_is_listed(child):
 
 @pytest.mark.parametrize("group", GROUPS)
 def test_rows_long_row(child, group):
-    cases = child.get(group, [])
-    assert cases, "no case of %s ran" % group
-    failed = [(name, bad) for name, bad in cases if bad]               # a skip counts as a failure here
-    assert not failed, "\n".join("%s: %s\n%s" % (name, bad[0][1], bad[0][2]) for name, bad in failed)
+    gpu_child.check_group(child, group)

@@ -5,18 +5,13 @@ k_select) against numpy's boolean indexing, and the chain from samples to frame-
 The cases are in tests/rows_slide_gpu_cases.py and run ONCE, with pytest, in a process of their own that imports torch first
 (tests/test_gpu_rows.py says why).  Each test below stands for one group of cases of that run (a function of the cases file with
 all its parameters): every case of the group must have passed, and at least one must exist.  No case may skip."""
-import os
-import subprocess
-import sys
-import xml.etree.ElementTree as ET
-
 import pytest
 
-from common import ROOT
+import gpu_child
 
 pytestmark = pytest.mark.gpu
 
-CASES = os.path.join(ROOT, "tests", "rows_slide_gpu_cases.py")
+CASES = "rows_slide_gpu_cases.py"
 GROUPS = ["test_k_slide_is_the_model", "test_tile_seams", "test_special_values", "test_rows_and_channels_do_not_leak",
           "test_calls_queued_back_to_back_on_one_stream_and_on_a_side_stream", "test_refusals_are_value_errors",
           "test_against_torchs_cumulative_sums_in_float64", "test_k_select_is_the_model", "test_select_rows_do_not_leak_and_refusals",
@@ -25,17 +20,7 @@ GROUPS = ["test_k_slide_is_the_model", "test_tile_seams", "test_special_values",
 
 @pytest.fixture(scope="module")
 def child(tmp_path_factory):
-    xml = str(tmp_path_factory.mktemp("rows_slide_gpu") / "cases.xml")
-    r = subprocess.run([sys.executable, "-m", "pytest", CASES, "-m", "gpu", "-q", "-rs", "-p", "no:cacheprovider", "--junitxml", xml],
-                       cwd=ROOT, capture_output=True, text=True, timeout=900)
-    print(r.stdout[-6000:])
-    assert os.path.exists(xml), (r.returncode, r.stdout[-3000:], r.stderr[-3000:])
-    groups = {}
-    for tc in ET.parse(xml).getroot().iter("testcase"):
-        name = tc.get("name")
-        bad = [(e.tag, (e.get("message") or "")[:300], (e.text or "")[-3000:]) for e in tc if e.tag in ("failure", "error", "skipped")]
-        groups.setdefault(name.split("[")[0], []).append((name, bad))
-    return groups
+    return gpu_child.run_cases(tmp_path_factory, CASES, "rows_slide_gpu")
 
 
 def test_every_group_of_the_cases_file_is_listed(child):
@@ -44,7 +29,4 @@ def test_every_group_of_the_cases_file_is_listed(child):
 
 @pytest.mark.parametrize("group", GROUPS)
 def test_rows_slide(child, group):
-    cases = child.get(group, [])
-    assert cases, "no case of %s ran" % group
-    failed = [(name, bad) for name, bad in cases if bad]               # a skip counts as a failure here
-    assert not failed, "\n".join("%s: %s\n%s" % (name, bad[0][1], bad[0][2]) for name, bad in failed)
+    gpu_child.check_group(child, group)

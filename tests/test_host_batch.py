@@ -8,11 +8,11 @@ import subprocess
 
 import pytest
 
+import host_harness as H
 from common import ROOT, sg
 
 SRC = [os.path.join(ROOT, "tools", "micro", "batch_host_bench.cpp")] + [
     os.path.join(ROOT, "lewton_amd", "csrc", n) for n in ("lw_runtime.cpp", "lw_batch.cpp", "lw_packet.cpp", "lw_pool.cpp", "lw_dev_entropy.cpp", "lw_entropy.cpp", "lw_headers.cpp", "lw_fast.cpp")]
-HIP_INC = "/opt/rocm/include"
 
 
 def _case(path, setup, pattern, count, **kw):
@@ -29,12 +29,7 @@ def _case(path, setup, pattern, count, **kw):
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    if not os.path.isdir(os.path.join(HIP_INC, "hip")):
-        pytest.skip("HIP headers not installed")
-    exe = str(tmp_path_factory.mktemp("hostbatch") / "batch_host_bench_tsan")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=thread", "-ffp-contract=off", "-DLW_CHECK_NARROW", "-D__HIP_PLATFORM_AMD__",
-                           "-I" + HIP_INC] + SRC + ["-lpthread", "-o", exe])
-    return exe
+    return H.build(tmp_path_factory, "batch_host_bench_tsan", SRC, sanitize="thread")
 
 
 @pytest.mark.parametrize("name,pattern", [("stereo", "L"), ("stereo", "LLSSLSL"), ("surround51", "LLSL"), ("mono_small", "LSSLL"),
@@ -115,9 +110,7 @@ def test_batch_statuses_and_sample_counts_equal_the_oracle(harness, tmp_path, na
 
 @pytest.fixture(scope="module")
 def harness_asan(tmp_path_factory):
-    if not os.path.isdir(os.path.join(HIP_INC, "hip")):
-        pytest.skip("HIP headers not installed")
-    return build_harness_asan(str(tmp_path_factory.mktemp("hostbatch_asan") / "batch_host_bench_asan"))
+    return H.build(tmp_path_factory, "batch_host_bench_asan", SRC)
 
 
 def random_setup_case(harness, seed, case, blocksizes=None, n_streams=6, per=14):
@@ -163,9 +156,7 @@ def random_setup_case(harness, seed, case, blocksizes=None, n_streams=6, per=14)
 
 
 def build_harness_asan(exe):
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off",
-                           "-DLW_CHECK_NARROW", "-D__HIP_PLATFORM_AMD__", "-I" + HIP_INC] + SRC + ["-lpthread", "-o", exe])
-    return exe
+    return H.compile_to(exe, SRC)
 
 
 def test_random_setups_plan_and_statuses_under_asan(harness_asan, tmp_path):

@@ -6,35 +6,27 @@ counts, the same LW_ERR_CAPACITY thresholds, the stream's trimmed last packet); 
 same calls are checked on the GPU (tests/test_gpu_f32_interleaved.py)."""
 import os
 import struct
-import subprocess
 
 import pytest
 
+import host_harness as H
 from common import ROOT, sg
+from host_harness import CS, NULL_ARG
 from test_ogg import _vorbis_stream
 
-CS = os.path.join(ROOT, "lewton_amd", "csrc")
 SRC = [os.path.join(ROOT, "tests", "san", "fmt_host.cpp")] + [
     os.path.join(CS, n) for n in ("lw_ogg.cpp", "lw_shard.cpp", "lw_ring.cpp", "lw_runtime.cpp", "lw_batch.cpp", "lw_packet.cpp",
                                   "lw_pool.cpp", "lw_dev_entropy.cpp", "lw_entropy.cpp", "lw_headers.cpp", "lw_fast.cpp")]
-HIP_INC = "/opt/rocm/include"
-F32_PLANAR, F32_INTERLEAVED, NULL_ARG = 2, 3, 32
+F32_PLANAR, F32_INTERLEAVED = 2, 3
 
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    if not os.path.isdir(os.path.join(HIP_INC, "hip")):
-        pytest.skip("HIP headers not installed")
-    exe = str(tmp_path_factory.mktemp("fmthost") / "fmt_host")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-ffp-contract=off", "-DLW_CHECK_NARROW", "-D__HIP_PLATFORM_AMD__", "-I" + HIP_INC] + SRC + ["-lpthread", "-o", exe])
-    return exe
+    return H.build(tmp_path_factory, "fmt_host", SRC)
 
 
 def _run(exe, path, *args):
-    r = subprocess.run([exe, path] + [str(a) for a in args], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return r.stdout.splitlines()
+    return H.run(exe, path, *args, timeout=300)
 
 
 def _packets_file(tmp_path, setup, pattern, count, seed):

@@ -7,36 +7,27 @@ The models are in tests/kaldi_model.py: the bit model (the contract in numpy, su
 yardstick (Kaldi's published algorithm restated) and the derived bound between the two.  Route 0 and real device memory are checked
 on the GPU (tests/test_gpu_rows_fbank.py)."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import kaldi_model as K
 import spec_model as M
+import host_harness as H
 from common import ROOT
+from host_harness import CAPACITY, CS, UNSUPPORTED
 
-CS = os.path.join(ROOT, "lewton_amd", "csrc")
 SRC = [os.path.join(ROOT, "tests", "san", "fbank_host.cpp"), os.path.join(CS, "lw_spec.cpp")]
-HIP_INC = "/opt/rocm/include"
-OK, NULL_ARG, CAPACITY, UNSUPPORTED = 0, 32, 34, 36
 SENT = 0x7FC0DEAD
 SENT_F = np.array(SENT, np.uint32).view(np.float32)
 
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    assert os.path.isdir(os.path.join(HIP_INC, "hip")), "the CPU suite compiles the host side against the HIP headers"
-    exe = str(tmp_path_factory.mktemp("fbank") / "fbank_host")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-ffp-contract=off", "-DLW_CHECK_NARROW", "-D__HIP_PLATFORM_AMD__", "-I" + HIP_INC] + SRC + ["-lpthread", "-o", exe])
-    return exe
+    return H.build(tmp_path_factory, "fbank_host", SRC)
 
 
-def _run(exe, *args):
-    r = subprocess.run([exe] + [str(a) for a in args], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
-    return r.stdout.splitlines()
+_run = H.run
 
 
 def _p(n_fft, win, hop, window=K.POVEY, center=0, framing=K.SNIP, dc=0, energy=0, reserved=0, c=0.0, scale=1.0):

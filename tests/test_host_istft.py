@@ -7,19 +7,17 @@ The model is the rule of include/lewton_amd.h ("inverse spectral frames of rows"
 float64, the indices in Python integers, the chains with spec_model.fmaf.  What the kernel makes of real device memory, and whether
 the matrix instruction gives the same bits, is checked on the GPU (tests/test_gpu_rows_istft.py)."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import istft_model as IM
 import spec_model as M
+import host_harness as H
 from common import ROOT
+from host_harness import CAPACITY, CS, NULL_ARG, UNSUPPORTED
 
-CS = os.path.join(ROOT, "lewton_amd", "csrc")
 SRC = [os.path.join(ROOT, "tests", "san", "istft_host.cpp"), os.path.join(CS, "lw_istft.cpp")]
-HIP_INC = "/opt/rocm/include"
-OK, NULL_ARG, CAPACITY, UNSUPPORTED = 0, 32, 34, 36
 WINDOWS = {"hann": 0, "rect": 1, "hann_sym": 4}
 SENT = 0x7FC00ABC
 # (n_fft, win_length, hop, window, center): the shapes of the GPU suite
@@ -29,17 +27,10 @@ SHAPES = [(16, 16, 4, "hann", 1), (25, 25, 7, "hann", 1), (32, 20, 5, "hann", 1)
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    assert os.path.isdir(os.path.join(HIP_INC, "hip")), "the CPU suite compiles the host side against the HIP headers"
-    exe = str(tmp_path_factory.mktemp("istfthost") / "istft_host")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-ffp-contract=off", "-DLW_CHECK_NARROW", "-D__HIP_PLATFORM_AMD__", "-I" + HIP_INC] + SRC + ["-lpthread", "-o", exe])
-    return exe
+    return H.build(tmp_path_factory, "istft_host", SRC)
 
 
-def _run(exe, *args):
-    r = subprocess.run([exe] + [str(a) for a in args], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
-    return r.stdout.splitlines()
+_run = H.run
 
 
 def _shape_args(shape):

@@ -5,18 +5,16 @@ planner's offset expressions for the LAST packet of a batch of n worst-case pack
 which every one of them fits its 32-bit field.  Nothing sanitized is loaded into Python."""
 import os
 import struct
-import subprocess
 
 import pytest
 
+import host_harness as H
 from common import FLOOR0_SETUPS, ROOT, SETUPS, sg
+from host_harness import CAPACITY as ERR_CAPACITY, CS
 
-CS = os.path.join(ROOT, "lewton_amd", "csrc")
 SRC = [os.path.join(ROOT, "tests", "san", "limits_host.cpp")] + [
     os.path.join(CS, n) for n in ("lw_shard.cpp", "lw_ring.cpp", "lw_rows.cpp", "lw_runtime.cpp", "lw_batch.cpp", "lw_packet.cpp",
                                   "lw_pool.cpp", "lw_dev_entropy.cpp", "lw_entropy.cpp", "lw_headers.cpp", "lw_fast.cpp")]
-HIP_INC = "/opt/rocm/include"
-ERR_CAPACITY = 34
 U32_MAX = (1 << 32) - 1
 SIZE_MAX = (1 << 64) - 1
 
@@ -29,13 +27,7 @@ LIMIT_SETUPS = {
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    if not os.path.isdir(os.path.join(HIP_INC, "hip")):
-        pytest.skip("HIP headers not installed")
-    exe = str(tmp_path_factory.mktemp("hostlimits") / "limits_host_asan")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-ffp-contract=off", "-DLW_CHECK_NARROW", "-D__HIP_PLATFORM_AMD__", "-I" + HIP_INC] + SRC +
-                          ["-lpthread", "-o", exe])
-    return exe
+    return H.build(tmp_path_factory, "limits_host_asan", SRC)
 
 
 def model_max_packets(ch, bs0, bs1, fstride):
@@ -84,9 +76,7 @@ def _run(harness, tmp_path, setup, with_packet=False):
         with open(pkf, "wb") as f:
             f.write(struct.pack("<I", len(pk)) + bytes(pk))
         args.append(pkf)
-    out = subprocess.run(args, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"), capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
-    return [ln.split() for ln in out.stdout.splitlines()]
+    return [ln.split() for ln in H.run(*args, timeout=300, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))]
 
 
 @pytest.mark.parametrize("name", list(LIMIT_SETUPS))

@@ -9,24 +9,19 @@ import subprocess
 import numpy as np
 import pytest
 
+import host_harness as H
 from common import ROOT
+from host_harness import CS
 from oracle import pyogg
 from test_ogg import GOLDEN, _vorbis_stream
 
-CS = os.path.join(ROOT, "lewton_amd", "csrc")
 SRC = [os.path.join(ROOT, "tests", "san", "ogg_stream_host.cpp")] + [
     os.path.join(CS, n) for n in ("lw_ogg.cpp", "lw_ring.cpp", "lw_runtime.cpp", "lw_batch.cpp", "lw_packet.cpp", "lw_pool.cpp", "lw_dev_entropy.cpp", "lw_entropy.cpp", "lw_headers.cpp", "lw_fast.cpp")]
-HIP_INC = "/opt/rocm/include"
 
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    if not os.path.isdir(os.path.join(HIP_INC, "hip")):
-        pytest.skip("HIP headers not installed")
-    exe = str(tmp_path_factory.mktemp("hostogg") / "ogg_stream_host")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-ffp-contract=off", "-DLW_CHECK_NARROW", "-D__HIP_PLATFORM_AMD__", "-I" + HIP_INC] + SRC + ["-lpthread", "-o", exe])
-    return exe
+    return H.build(tmp_path_factory, "ogg_stream_host", SRC)
 
 
 def _chained():
@@ -58,9 +53,7 @@ def _run(exe, tmp_path, data, *mode, dev_entropy=False, read_ahead=0, go_on=Fals
         env["LW_OSH_READ_AHEAD"] = str(read_ahead)   # lw_ogg_stream_set_read_ahead(s, K, 2) right after the open
     if go_on:
         env["LW_OSH_GO_ON"] = "1"                    # a drain goes on behind a BadAudio packet (trace line P 0 <code> ...)
-    out = subprocess.run([exe, path] + [str(m) for m in mode], capture_output=True, text=True, timeout=300, env=env)
-    assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-4000:]
-    return [l.split() for l in out.stdout.splitlines()]
+    return [l.split() for l in H.run(exe, path, *mode, timeout=300, env=env)]
 
 
 def _gp(v):
@@ -439,12 +432,7 @@ def test_read_ahead_damaged_packets_fail_at_their_call_and_the_stream_goes_on(ha
 
 @pytest.fixture(scope="module")
 def harness_tsan(tmp_path_factory):
-    if not os.path.isdir(os.path.join(HIP_INC, "hip")):
-        pytest.skip("HIP headers not installed")
-    exe = str(tmp_path_factory.mktemp("hostogg_tsan") / "ogg_stream_host_tsan")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=thread", "-ffp-contract=off", "-DLW_CHECK_NARROW", "-D__HIP_PLATFORM_AMD__",
-                           "-I" + HIP_INC] + SRC + ["-lpthread", "-o", exe])
-    return exe
+    return H.build(tmp_path_factory, "ogg_stream_host_tsan", SRC, sanitize="thread")
 
 
 def test_read_ahead_and_look_ahead_under_thread_sanitizer(harness, harness_tsan, tmp_path):

@@ -6,17 +6,15 @@ The model is the rule of include/lewton_amd.h ("resampling rows") evaluated here
 kernel makes of real device memory is checked on the GPU (tests/test_gpu_rows_resample.py)."""
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_harness as H
 from common import ROOT, SETUPS
+from host_harness import CAPACITY, CS, NULL_ARG, UNSUPPORTED
 
-CS = os.path.join(ROOT, "lewton_amd", "csrc")
 SRC = [os.path.join(ROOT, "tests", "san", "resample_host.cpp"), os.path.join(CS, "lw_resample.cpp")]
-HIP_INC = "/opt/rocm/include"
-OK, NULL_ARG, CAPACITY, UNSUPPORTED = 0, 32, 34, 36
 PAIRS = [(44100, 16000), (48000, 16000), (44100, 48000), (16000, 44100), (22050, 44100), (48000, 44100)]
 KAISER_BETA = 14.769656459379492
 FILTERS = {"hann": (6, 0.99, 0, 0.0), "kaiser": (16, 0.99, 1, KAISER_BETA)}          # zeros, rolloff, window, beta
@@ -25,19 +23,11 @@ HALF_WIDTHS = {"hann": [17, 19, 7, 7, 7, 7], "kaiser": [45, 49, 17, 17, 17, 18]}
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    if not os.path.isdir(os.path.join(HIP_INC, "hip")):
-        pytest.skip("HIP headers not installed")
-    exe = str(tmp_path_factory.mktemp("resamplehost") / "resample_host")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-ffp-contract=off", "-DLW_CHECK_NARROW", "-D__HIP_PLATFORM_AMD__", "-I" + HIP_INC] + SRC + ["-lpthread", "-o", exe])
-    return exe
+    return H.build(tmp_path_factory, "resample_host", SRC)
 
 
-def _run(exe, *args, ok=True):
-    r = subprocess.run([exe] + [repr(a) if isinstance(a, float) else str(a) for a in args], capture_output=True, text=True, timeout=300)
-    if ok:
-        assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
-    return r.stdout.splitlines()
+def _run(exe, *args, **kw):
+    return H.run(exe, *args, timeout=300, **kw)
 
 
 def _geometry(in_rate, out_rate, zeros, rolloff):

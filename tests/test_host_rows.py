@@ -6,19 +6,17 @@ the rules of include/lewton_amd.h "stream-major rows"; the pieces must realise e
 piece bound.  What the kernel makes of the list is checked on the GPU (tests/test_gpu_rows.py)."""
 import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_harness as H
 from common import ROOT, SETUPS, sg
+from host_harness import CAPACITY, CS, NULL_ARG, OK, STATE_MISMATCH
 
-CS = os.path.join(ROOT, "lewton_amd", "csrc")
 SRC = [os.path.join(ROOT, "tests", "san", "rows_host.cpp")] + [
     os.path.join(CS, n) for n in ("lw_rows.cpp", "lw_runtime.cpp", "lw_batch.cpp", "lw_packet.cpp", "lw_pool.cpp",
                                   "lw_dev_entropy.cpp", "lw_entropy.cpp", "lw_headers.cpp", "lw_fast.cpp")]
-HIP_INC = "/opt/rocm/include"
-OK, NULL_ARG, CAPACITY, STATE_MISMATCH = 0, 32, 34, 35
 ALL = 0xFFFFFFFF
 PIECE = 2048
 FMTS = {"i16": 0, "i16_interleaved": 1, "f32": 2, "f32_interleaved": 3}
@@ -27,12 +25,7 @@ SHAPES = [("stereo", "LLSSLSL"), ("surround51", "LSSL"), ("mono_small", "SLLS")]
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    if not os.path.isdir(os.path.join(HIP_INC, "hip")):
-        pytest.skip("HIP headers not installed")
-    exe = str(tmp_path_factory.mktemp("rowshost") / "rows_host")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-ffp-contract=off", "-DLW_CHECK_NARROW", "-D__HIP_PLATFORM_AMD__", "-I" + HIP_INC] + SRC + ["-lpthread", "-o", exe])
-    return exe
+    return H.build(tmp_path_factory, "rows_host", SRC)
 
 
 def _packets_file(tmp_path, setup, pattern, count, seed, damage=None):
@@ -47,10 +40,8 @@ def _packets_file(tmp_path, setup, pattern, count, seed, damage=None):
     return path
 
 
-def _run(exe, *args):
-    r = subprocess.run([exe] + [str(a) for a in args], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
-    return r.stdout.splitlines()
+def _run(exe, *args, **kw):
+    return H.run(exe, *args, timeout=300, **kw)
 
 
 def _results(lines):

@@ -8,19 +8,17 @@ What the kernel makes of pieces and matrix is checked on the GPU (tests/test_gpu
 lewton_amd.rows are checked here as well: they need no GPU."""
 import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_harness as H
 from common import ROOT, SETUPS, sg
+from host_harness import CAPACITY, CS, NULL_ARG, OK, STATE_MISMATCH, UNSUPPORTED
 
-CS = os.path.join(ROOT, "lewton_amd", "csrc")
 SRC = [os.path.join(ROOT, "tests", "san", "rows_mix_host.cpp")] + [
     os.path.join(CS, n) for n in ("lw_rows.cpp", "lw_rows_mix.cpp", "lw_runtime.cpp", "lw_batch.cpp", "lw_packet.cpp", "lw_pool.cpp",
                                   "lw_dev_entropy.cpp", "lw_entropy.cpp", "lw_headers.cpp", "lw_fast.cpp")]
-HIP_INC = "/opt/rocm/include"
-OK, NULL_ARG, CAPACITY, STATE_MISMATCH, UNSUPPORTED = 0, 32, 34, 35, 36
 ALL = 0xFFFFFFFF
 PIECE = 512
 FMTS = {"i16": 0, "i16_interleaved": 1, "f32": 2, "f32_interleaved": 3}
@@ -29,12 +27,7 @@ SHAPES = [("stereo", "LLSSLSL"), ("surround51", "LSSL"), ("mono_small", "SLLS")]
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    if not os.path.isdir(os.path.join(HIP_INC, "hip")):
-        pytest.skip("HIP headers not installed")
-    exe = str(tmp_path_factory.mktemp("rowsmixhost") / "rows_mix_host")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-ffp-contract=off", "-DLW_CHECK_NARROW", "-D__HIP_PLATFORM_AMD__", "-I" + HIP_INC] + SRC + ["-lpthread", "-o", exe])
-    return exe
+    return H.build(tmp_path_factory, "rows_mix_host", SRC)
 
 
 def _packets_file(tmp_path, setup, pattern, count, seed):
@@ -47,10 +40,8 @@ def _packets_file(tmp_path, setup, pattern, count, seed):
     return path
 
 
-def _run(exe, *args):
-    r = subprocess.run([exe] + [str(a) for a in args], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
-    return r.stdout.splitlines()
+def _run(exe, *args, **kw):
+    return H.run(exe, *args, timeout=300, **kw)
 
 
 def _results(lines):

@@ -6,18 +6,16 @@ buffers.
 The model is the rule of include/lewton_amd.h ("frame decisions and frame selection") in numpy (tests/select_model.py).  What the
 kernels make of real device memory, LDS and the barriers is checked on the GPU (tests/test_gpu_rows_slide.py)."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import select_model as M
+import host_harness as H
 from common import ROOT
+from host_harness import CAPACITY, CS, DEVICE, NULL_ARG, OK, UNSUPPORTED
 
-CS = os.path.join(ROOT, "lewton_amd", "csrc")
 SRC = [os.path.join(ROOT, "tests", "san", "select_host.cpp"), os.path.join(CS, "lw_select.cpp")]
-HIP_INC = "/opt/rocm/include"
-OK, NULL_ARG, DEVICE, CAPACITY, UNSUPPORTED = 0, 32, 33, 34, 36
 F32 = np.float32
 SENT_COUNT = 0xEEEEEEEEEEEEEEEE
 N, CAP = [1100, 0, 257, 600], 1103                                      # two seams of the default tile's quarter, one of the default
@@ -25,17 +23,10 @@ N, CAP = [1100, 0, 257, 600], 1103                                      # two se
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    assert os.path.isdir(os.path.join(HIP_INC, "hip")), "the CPU suite compiles the host side against the HIP headers"
-    exe = str(tmp_path_factory.mktemp("selecthost") / "select_host")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-ffp-contract=off", "-DLW_CHECK_NARROW", "-D__HIP_PLATFORM_AMD__", "-I" + HIP_INC] + SRC + ["-lpthread", "-o", exe])
-    return exe
+    return H.build(tmp_path_factory, "select_host", SRC)
 
 
-def _run(exe, *args):
-    r = subprocess.run([exe] + [str(a) for a in args], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
-    return r.stdout.splitlines()
+_run = H.run
 
 
 # ---- refusals, and what is queued

@@ -10,23 +10,18 @@ import subprocess
 import numpy as np
 import pytest
 
+import host_harness as H
 from common import ROOT, SETUPS, sg
+from host_harness import CS
 
-CS = os.path.join(ROOT, "lewton_amd", "csrc")
 SRC = [os.path.join(ROOT, "tests", "san", "shard_host.cpp")] + [
     os.path.join(CS, n) for n in ("lw_shard.cpp", "lw_ring.cpp", "lw_runtime.cpp", "lw_batch.cpp", "lw_packet.cpp", "lw_pool.cpp",
                                   "lw_dev_entropy.cpp", "lw_entropy.cpp", "lw_headers.cpp", "lw_fast.cpp")]
-HIP_INC = "/opt/rocm/include"
 
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    if not os.path.isdir(os.path.join(HIP_INC, "hip")):
-        pytest.skip("HIP headers not installed")
-    exe = str(tmp_path_factory.mktemp("hostshard") / "shard_host_tsan")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=thread", "-ffp-contract=off", "-DLW_CHECK_NARROW", "-D__HIP_PLATFORM_AMD__",
-                           "-I" + HIP_INC] + SRC + ["-lpthread", "-o", exe])
-    return exe
+    return H.build(tmp_path_factory, "shard_host_tsan", SRC, sanitize="thread")
 
 
 def _case(path, setup, pattern, count, seed):

@@ -8,18 +8,16 @@ gives the same bits, is checked on the GPU (tests/test_gpu_rows_spec.py)."""
 import ctypes
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import spec_model as M
+import host_harness as H
 from common import ROOT
+from host_harness import CAPACITY, CS, NULL_ARG, UNSUPPORTED
 
-CS = os.path.join(ROOT, "lewton_amd", "csrc")
 SRC = [os.path.join(ROOT, "tests", "san", "spec_host.cpp"), os.path.join(CS, "lw_spec.cpp")]
-HIP_INC = "/opt/rocm/include"
-OK, NULL_ARG, CAPACITY, UNSUPPORTED = 0, 32, 34, 36
 HANN, RECT = 0, 1
 SHAPES = [(400, 400, 160, HANN, 1), (512, 400, 160, HANN, 1), (16, 16, 4, RECT, 0), (25, 25, 7, HANN, 1), (64, 64, 100, HANN, 1),
           (32, 32, 1, HANN, 1), (2048, 2048, 512, HANN, 1), (2048, 1001, 65535, RECT, 0), (2, 1, 1, HANN, 0)]
@@ -73,18 +71,10 @@ def test_fmaf_emulation_is_glibc_fmaf_on_the_ties_the_naive_form_gets_wrong():
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    assert os.path.isdir(os.path.join(HIP_INC, "hip")), "the CPU suite compiles the host side against the HIP headers"
-    exe = str(tmp_path_factory.mktemp("spechost") / "spec_host")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-ffp-contract=off", "-DLW_CHECK_NARROW", "-D__HIP_PLATFORM_AMD__", "-I" + HIP_INC] + SRC + ["-lpthread", "-o", exe])
-    return exe
+    return H.build(tmp_path_factory, "spec_host", SRC)
 
 
-def _run(exe, *args, ok=True):
-    r = subprocess.run([exe] + [str(a) for a in args], capture_output=True, text=True, timeout=600)
-    if ok:
-        assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
-    return r.stdout.splitlines()
+_run = H.run
 
 
 def _model_basis(n_fft, win, window):

@@ -4,19 +4,17 @@ phases for both outputs lane by lane (tests/test_host_spec.py says how).  The co
 themselves; the power of the twin object is fmaf(im, im, re * re) of them; and a params struct with output = 0 is the object
 lw_spec_create makes, byte for byte."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import spec_model as M
 import spec_reflect_model as R
+import host_harness as H
 from common import ROOT
+from host_harness import CS, UNSUPPORTED
 
-CS = os.path.join(ROOT, "lewton_amd", "csrc")
 SRC = [os.path.join(ROOT, "tests", "san", "spec_complex_host.cpp"), os.path.join(CS, "lw_spec.cpp")]
-HIP_INC = "/opt/rocm/include"
-OK, NULL_ARG, UNSUPPORTED = 0, 32, 36
 HANN, RECT = 0, 1
 SENT = 0x7FC00ABC
 # (n_fft, win_length, hop, window, center, pad mode, samples)
@@ -26,17 +24,10 @@ CASES = [(16, 16, 4, HANN, 1, 0, 150), (16, 16, 4, RECT, 0, 0, 150), (25, 25, 7,
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    assert os.path.isdir(os.path.join(HIP_INC, "hip")), "the CPU suite compiles the host side against the HIP headers"
-    exe = str(tmp_path_factory.mktemp("speccomplexhost") / "spec_complex_host")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-ffp-contract=off", "-DLW_CHECK_NARROW", "-D__HIP_PLATFORM_AMD__", "-I" + HIP_INC] + SRC + ["-lpthread", "-o", exe])
-    return exe
+    return H.build(tmp_path_factory, "spec_complex_host", SRC)
 
 
-def _run(exe, *args):
-    r = subprocess.run([exe] + [str(a) for a in args], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
-    return r.stdout.splitlines()
+_run = H.run
 
 
 def _spec(harness, tmp_path, case, x, output):

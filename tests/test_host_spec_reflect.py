@@ -5,36 +5,27 @@ chains), lane by lane over an exact-size row, so a reflected index outside [0, l
 The model: the frames of tests/spec_model.py, uncentred, over the row padded by numpy (tests/spec_reflect_model.py); the reflected
 indices in Python integers.  Route 0 and real device memory are checked on the GPU (tests/test_gpu_rows_feat.py)."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import spec_model as M
 import spec_reflect_model as RM
+import host_harness as H
 from common import ROOT
+from host_harness import CAPACITY, CS, NULL_ARG, UNSUPPORTED
 
-CS = os.path.join(ROOT, "lewton_amd", "csrc")
 SRC = [os.path.join(ROOT, "tests", "san", "spec_reflect_host.cpp"), os.path.join(CS, "lw_spec.cpp")]
-HIP_INC = "/opt/rocm/include"
-OK, NULL_ARG, CAPACITY, UNSUPPORTED = 0, 32, 34, 36
 HANN, RECT = 0, 1
 ZERO, REFLECT = 0, 1
 
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    assert os.path.isdir(os.path.join(HIP_INC, "hip")), "the CPU suite compiles the host side against the HIP headers"
-    exe = str(tmp_path_factory.mktemp("specreflect") / "spec_reflect_host")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-ffp-contract=off", "-DLW_CHECK_NARROW", "-D__HIP_PLATFORM_AMD__", "-I" + HIP_INC] + SRC + ["-lpthread", "-o", exe])
-    return exe
+    return H.build(tmp_path_factory, "spec_reflect_host", SRC)
 
 
-def _run(exe, *args):
-    r = subprocess.run([exe] + [str(a) for a in args], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
-    return r.stdout.splitlines()
+_run = H.run
 
 
 @pytest.mark.parametrize("n_fft", [400, 25, 16, 32, 2048, 2])

@@ -4,31 +4,25 @@ which keep a model of what is in flight: an upload into a slot that queued work 
 harness with a message.  It drives the public entry points only.  The failure paths it covers cannot be reached on a GPU without
 provoking a fault, so this is where they are tested."""
 import os
-import subprocess
 
 import pytest
 
+import host_harness as H
 from common import ROOT
+from host_harness import CS
 
-CS = os.path.join(ROOT, "lewton_amd", "csrc")
 SRC = [os.path.join(ROOT, "tests", "san", "stage_host.cpp")] + [
     os.path.join(CS, n) for n in ("lw_resample.cpp", "lw_spec.cpp", "lw_feat.cpp", "lw_norm.cpp", "lw_cep.cpp")]
-HIP_INC = "/opt/rocm/include"
 ENTRIES = ["resample", "spec", "feat", "norm", "cep"]
 
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    assert os.path.isdir(os.path.join(HIP_INC, "hip")), "the CPU suite compiles the host side against the HIP headers"
-    exe = str(tmp_path_factory.mktemp("stagehost") / "stage_host")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-ffp-contract=off", "-DLW_CHECK_NARROW", "-D__HIP_PLATFORM_AMD__", "-I" + HIP_INC] + SRC + ["-lpthread", "-o", exe])
-    return exe
+    return H.build(tmp_path_factory, "stage_host", SRC)
 
 
 def _run(exe, entry, case):
-    r = subprocess.run([exe, entry, case], capture_output=True, text=True, timeout=300)
-    assert (r.returncode, r.stdout.splitlines()) == (0, ["OK"]), (r.stdout[-2000:], r.stderr[-2000:])
+    assert H.run(exe, entry, case, timeout=300) == ["OK"]
 
 
 @pytest.mark.parametrize("entry", ENTRIES)

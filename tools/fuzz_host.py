@@ -21,7 +21,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from test_fuzz_host import ALL, _mutate, oracle_headers, po, sg  # noqa: E402
-from test_host_ogg import SRC, HIP_INC, _files, _oracle_trace  # noqa: E402
+import host_harness  # noqa: E402
+from test_host_ogg import SRC, _files, _oracle_trace  # noqa: E402
 from lewton_amd import audio, header, ogg  # noqa: E402
 from oracle import pyogg  # noqa: E402
 
@@ -83,8 +84,7 @@ def fix_crcs(d):
 
 with tempfile.TemporaryDirectory() as tmp:
     exe, path = os.path.join(tmp, "ogg_stream_host"), os.path.join(tmp, "in.ogg")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-ffp-contract=off", "-DLW_CHECK_NARROW", "-D__HIP_PLATFORM_AMD__", "-I" + HIP_INC] + SRC + ["-lpthread", "-o", exe])
+    host_harness.compile_to(exe, SRC)
     files = _files()
     names = sorted(files)
     agree = opened = comment_rejects = 0
