@@ -111,6 +111,38 @@ def istft(G, w2, X, n_fft, hop, center, length=None):
     return _cut(v, pad, P, length)
 
 
+def window_rows(G, w2, row, a, b, T, n_fft, hop, center, length, before):
+    """The window form of istft() for ONE row and channel whose lines are +0.0 outside a few windows (tests/sparse_rows.py: row a
+    SparseRow of the 2 B lines, of at least T frames): samples [a, b) of the destination after the call, from `before` float32
+    [b - a].  Only the frames that touch the padded samples [a + pad, b + pad) are ever held; the overlap-add and the envelope of
+    those samples are the complete ascending folds, because every frame that touches one of them is among these"""
+    win_length = np.asarray(G).shape[1]
+    _, o, pad, P, _ = geometry(n_fft, win_length, hop, center, T)
+    assert 0 <= a <= b
+    out = np.array(before, np.float32, copy=True)
+    hi = min(b, int(length))
+    if hi <= a:
+        return out
+    out[:hi - a] = 0.0                                                 # behind what the frames cover
+    p0, p1 = a + pad, min(hi + pad, P)
+    if p1 <= p0:
+        return out
+    t0 = max(0, -(-(p0 - o - win_length + 1) // hop))                  # the first frame with t hop + o + W - 1 >= p0
+    t1 = min(T - 1, (p1 - 1 - o) // hop)                               # the last with t hop + o <= p1 - 1
+    if t1 < t0:
+        return out
+    X = row.clipped(T).take(t0, t1 + 1)
+    base = t0 * hop                                                    # the padded sample at which the local fold starts
+    xh = overlap_add(frame_signals(G, X), n_fft, win_length, hop)
+    env = envelope(w2, t1 + 1 - t0, n_fft, hop)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        v = np.where(env > 1e-11, (xh.astype(np.float64) / env).astype(np.float32), np.float32(0.0)).astype(np.float32)
+    lo, up = max(p0, base), min(p1, base + len(v))
+    if up > lo:
+        out[lo - pad - a:up - pad - a] = v[lo - base:up - base]
+    return out
+
+
 def yardstick(Xc, name, n_fft, win_length, hop, center, length=None):
     """float64 [length] from complex128 [B][T]: irfft, window, overlap-add, division by the envelope; NaN where the envelope is
     not above 1e-11 (where torch.istft raises) and 0 behind what the frames cover"""

@@ -1,5 +1,5 @@
-"""The rows chain past element 2^32 of a tensor and past 65535 rows of a call, on the GPU: k_rows_mix, k_resample, k_spec, k_feat,
-k_norm and k_cep.  The cases of tests/test_gpu_rows_large.py, which runs this file with pytest in a process of its own, torch
+"""The rows chain past element 2^32 of a tensor and past 65535 rows of a call, on the GPU: k_rows_mix, k_resample, k_spec,
+k_spec_complex, k_istft, k_feat, k_norm, k_cep, k_slide, k_select_count and k_select.  The cases of tests/test_gpu_rows_large.py, which runs this file with pytest in a process of its own, torch
 imported first (tests/rows_gpu_cases.py says why).
 
 Part A.  Every kernel forms its addresses from several products (row x row size, channel x channel size, line x line_el, position x
@@ -11,7 +11,8 @@ lengths are a few hundred to a few thousand, the work is tiny, the offsets are h
 destination holds the sentinel 0x7FC0DEAD and the source holds it from each length on; afterwards the live slots equal the model
 bit for bit up to their fill end, everything else is still the sentinel (slot 0 is where a truncated offset lands; it holds other
 data than slot 16 where it is live), and a source that is not the destination is unchanged.  Python integers assert that the last
-live element lies past 2^32, and one past 2^31, so no case can quietly stop crossing.
+live element lies past 2^32, and one past 2^31, so no case can quietly stop crossing.  The byte mask of k_select is a uint8 tensor
+of its own, allocated in the case and freed behind it (4.6 GB for 17 rows of 2^28 + 5 bytes): 43.2 GB of device memory at the peak.
 
 Part B.  Every entry point cuts a call into launches of 65535 rows and hands row0 to the kernel, which adds it to blockIdx.z for the
 row record, the tensor offsets and the per-row scratch.  65 540 rows of a few dozen elements, a dozen of them live on both sides of
@@ -19,8 +20,8 @@ the cut, each with data and a length of its own: the live rows equal the model b
 is still the sentinel (compared on the device).
 
 The models are those of the other cases files (tests/cep_model.py, norm_model.py, feat_model.py, spec_model.py,
-spec_reflect_model.py, the resampler's fold and the mix fold), evaluated over the windows / the live rows only.  No tolerance
-anywhere."""
+spec_reflect_model.py, istft_model.py, slide_model.py, select_model.py, the resampler's fold and the mix fold), evaluated over the
+windows / the live rows only.  No tolerance anywhere."""
 import torch  # noqa: F401  (first: see above)
 
 import math
@@ -33,10 +34,14 @@ import cep_model as CM
 import feat_model as FM
 import norm_model as NM
 import rows_feat_gpu_cases as FC
+import rows_istft_gpu_cases as IC
 import rows_mix_gpu_cases as MX
 import rows_resample_gpu_cases as RC
 import rows_spec_gpu_cases as S
+import select_model as SEL
+import slide_model as SLM
 import spec_model as SM
+import spec_reflect_model as XR
 from common import SETUPS
 from rows_gpu_cases import _Cursor, _oracle_rows, _product, _streams
 
@@ -49,6 +54,7 @@ SENT_I = int(np.array(SENT, np.uint32).view(np.int32))
 CAP = 1 << 28
 ODD = CAP + 5                          # lines start at every residue against 16 bytes
 HALF = 18 * (CAP + 8)                  # elements of one buffer: 18 slots (k_cep's 6 x 3 destination lines) of either capacity
+MASK_BYTES = 17 * ODD                  # the largest mask of a k_select case: uint8 [17][1][2^28 + 5], a tensor of its own per case
 KIND = {None: NM.NONE, "std": NM.STD, "rms": NM.RMS, "peak": NM.PEAK}
 
 
@@ -62,8 +68,8 @@ class _Bufs:
 def bufs():
     """one allocation for the whole file: .a and .b are its halves (source and destination), .big all of it (k_rows_mix)"""
     free, _ = torch.cuda.mem_get_info(0)
-    if free < 2 * HALF * 4 + (4 << 30):
-        pytest.skip("less than %.1f GB of device memory free" % ((2 * HALF * 4 + (4 << 30)) / 1e9))
+    if free < 2 * HALF * 4 + MASK_BYTES + (4 << 30):
+        pytest.skip("less than %.1f GB of device memory free" % ((2 * HALF * 4 + MASK_BYTES + (4 << 30)) / 1e9))
     torch.cuda.reset_peak_memory_stats(0)
     t0 = time.perf_counter()
     B = _Bufs()
@@ -540,6 +546,256 @@ def test_k_rows_mix_past_2_to_the_32(bufs, name):
     assert not (want[live[-1]] == SENT_I).all()
 
 
+# ---- A.7 k_slide
+
+def _sl_lines(F, W, tile):
+    """lines a workgroup of k_slide stages at a time, by the plan csrc/lw_slide.hpp writes down: 64 KiB of LDS, 16 lines at most"""
+    cols = (tile + W + 30) & ~15
+    per_line = (cols + cols // 32 + 1) * 4 + cols // 16 * 16
+    lines = min(16, 65536 // per_line)
+    return min(F, lines & ~3 if lines >= 4 else lines)
+
+
+WIDE = 18 << 24                        # a capacity at which 16 lines are 18 slots: line 15 starts past 2^32, inside ONE group of lines
+SL_BIG, SL_SMALL = (300, 100, 1, 1), (8, 3, 0, 0)                     # (W, min, center, norm_vars)
+# name -> (geometry, or (rows, channels, lines; live rows); capacity; configuration; fill_to - n or None).  t.at is ((row x ch + by)
+# x F + f0) x line_el, f0 the first line of a group of `lines` lines; the lines of a group lie g x line_el behind it, g < 16.  The three
+# geometries reach slot 16 by the row, the channel and (17 lines in two groups of 16) by f0 = 16; second_group by f0 = 32 at 2^27
+# frames per line; in_group by g = 15 at WIDE
+SLIDE = {
+    "rows_centred_vars": ("rows", CAP, SL_BIG, 9),
+    "rows_causal": ("rows", ODD, SL_SMALL, None),
+    "channels_centred_vars": ("channels", ODD, SL_BIG, None),
+    "channels_causal": ("channels", CAP, SL_SMALL, 5),
+    "lines_centred_vars": ("lines", ODD, SL_BIG, 7),
+    "lines_causal": ("lines", CAP, SL_SMALL, None),
+    "lines_second_group_centred_vars": ((1, 1, 33, (0,)), 1 << 27, SL_BIG, 4),
+    "lines_second_group_causal": ((1, 1, 33, (0,)), 1 << 27, SL_SMALL, None),
+    "lines_in_group_centred_vars": ((1, 1, 16, (0,)), WIDE, SL_BIG, None),
+    "lines_in_group_causal": ((1, 1, 16, (0,)), WIDE, SL_SMALL, 3),
+}
+SL_TILE = 256                          # frames of a tile here (the default is 1024): rows of 600 to 1031 frames span three to five
+
+
+def _geometry(geo):
+    return GEO[geo] if isinstance(geo, str) else geo
+
+
+@pytest.mark.parametrize("name", list(SLIDE))
+def test_k_slide_past_2_to_the_32(bufs, name):
+    from lewton_amd.rows import SlidingCMVN
+    geo, cap, cfg, extra = SLIDE[name]
+    R, C, F, live = _geometry(geo)
+    sl = SlidingCMVN(cfg[0], cfg[1], bool(cfg[2]), bool(cfg[3]))
+    try:
+        sl.set_tile_frames(SL_TILE)
+        n = _lens(R, live, (700, 600, 1031) if len(live) == 3 else (1031,))
+        assert sl.tile_frames == SL_TILE and min(v for v in n if v) > 2 * SL_TILE
+        fill = None if extra is None else [v + extra if v else 0 for v in n]
+        W = max(n) + 41
+        x = SLM.source(n, C, F, W, 500 + len(name))
+        shape = (R, C, F, cap)
+        _assert_crosses(shape, max(n[-1], (fill or n)[-1]))
+        lines = _sl_lines(F, cfg[0], SL_TILE)
+        assert lines == min(F, 16)
+        if "second_group" in name:
+            assert F == 2 * lines + 1 and 2 * lines * cap >= 1 << 32 > (2 * lines - 1) * cap     # f0 x line_el on its own
+        if "in_group" in name:
+            assert F == lines and (F - 1) * cap >= 1 << 32                                       # g x line_el on its own
+        _lines_case(bufs, shape, shape, x, False, lambda s, d: sl.run(s, n, out=d, fill_to=fill),
+                    lambda before: SLM.rows(x, n, fill, before, cfg[0], cfg[1], bool(cfg[2]), bool(cfg[3])), SLM.same_bits)
+        assert sl.last_launches() == 1
+    finally:
+        sl.close()
+
+
+# ---- A.8 k_select_count and k_select
+
+# name -> (geometry, capacity, mask kind, tile, fill_to - n or None).  The mask is [rows][ch][capacity] BYTES: t.mask_at = (row x ch +
+# by) x line_el reaches 2^32 through rows and channels only, t.at as k_slide's (groups of 16 lines whatever the tile)
+SELECT = {
+    "rows_random_256": ("rows", CAP, "random", 256, 9),
+    "rows_last_1024": ("rows", ODD, "last", 1024, None),
+    "channels_random_1024": ("channels", ODD, "random", 1024, None),
+    "channels_last_256": ("channels", CAP, "last", 256, 5),
+    "lines_random_256": ("lines", ODD, "random", 256, 7),
+    "lines_last_1024": ("lines", CAP, "last", 1024, None),
+    "lines_in_group_random_1024": ((1, 1, 16, (0,)), WIDE, "random", 1024, 3),
+}
+
+
+@pytest.mark.parametrize("name", list(SELECT))
+def test_k_select_past_2_to_the_32(bufs, name):
+    """the kept frames of every line at its front, the zeroed tail, the sentinel behind it, and K of every row and channel"""
+    from lewton_amd.rows import SelectFrames
+    geo, cap, kind, tile, extra = SELECT[name]
+    R, C, F, live = _geometry(geo)
+    se = SelectFrames()
+    dm = None
+    try:
+        se.set_tile_frames(tile)
+        n = _lens(R, live, (2 * tile + 188, 2 * tile + 60, 2 * tile + 519) if len(live) == 3 else (2 * tile + 519,))
+        assert se.tile_frames == tile and min(v for v in n if v) > 2 * tile
+        fill = None if extra is None else [v + extra if v else 0 for v in n]
+        W = max(n) + 41
+        x = SEL.source(n, C, F, W, 600 + len(name))
+        mask = SEL.mask(kind, n, C, W, 31 + len(name))
+        shape, mshape = (R, C, F, cap), (R, C, cap)
+        _assert_crosses(shape, max(n[-1], (fill or n)[-1]))
+        assert math.prod(mshape) <= MASK_BYTES
+        if R * C > 1:
+            _assert_crosses(mshape, n[-1])                               # the mask's own product, in bytes
+        if "in_group" in name:
+            assert F == 16 and (F - 1) * cap >= 1 << 32
+        dm = torch.empty(mshape, dtype=torch.uint8, device="cuda:0")
+        dm[..., :W].copy_(torch.from_numpy(mask))
+        want_k = SEL.rows(x, mask, n, fill, np.zeros((R, C, F, W), F32))[1]
+        out, counts = _lines_case(bufs, shape, shape, x, False, lambda s, d: se.run(s, n, dm, out=d, fill_to=fill),
+                                  lambda before: SEL.rows(x, mask, n, fill, before)[0], lambda g, w, s: SEL.same_bits(g, w))
+        assert se.last_launches() == 2 and counts.dtype == torch.int64
+        assert np.array_equal(counts.cpu().numpy(), want_k) and (want_k[-1, -1] == 1 if kind == "last" else want_k[-1, -1] > tile)
+        assert np.array_equal(dm[..., :W].cpu().numpy(), mask), "the mask was written"
+    finally:
+        se.close()
+        dm = None
+        torch.cuda.empty_cache()
+
+
+# ---- A.9 k_istft
+
+# name -> (source [R][C] of 18 lines, frame capacity, destination rows, capacity, interleaved destination, live source rows,
+# (win_length, hop, window, center), lengths longer than natural by (None: the natural lengths), rows= map).  n_fft = 16: 2 B = 18 lines,
+# a half of the buffer exactly.  t.s_at = (row0 + bz) x s_row + by x s_ch, lc x s_line, t.d_at = dst_row x d.row + by x d.ch
+IS_HANN, IS_RECT = (16, 4, "hann"), (16, 16, "rect")
+ISTFT = {
+    "lines_hann": ((1, 1), CAP, 1, CAP, False, (0,), IS_HANN + (True,), None, None),                     # line 16, im[7], starts at 2^32
+    "lines_rect_uncentred": ((1, 1), CAP, 1, ODD, False, (0,), IS_RECT + (False,), 9, None),
+    "rows_hann": ((16, 1), 1 << 24, 17, CAP, False, (0, 8, 15), IS_HANN + (True,), 7, {15: 16, 0: 15, 8: 9}),  # source row 15 -> row 16
+    "rows_hann_uncentred": ((16, 1), 1 << 24, 17, ODD, False, (0, 8, 15), IS_HANN + (False,), None, {15: 16, 0: 15, 8: 1}),
+    "interleaved_rows_hann": ((8, 2), 1 << 24, 9, ODD, True, (0, 4, 7), IS_HANN + (True,), 5, {7: 8, 0: 7, 4: 1}),
+    "channels_hann": ((1, 17), 15_000_001, 1, CAP, False, (0,), IS_HANN + (True,), None, None),            # channel 16 of both
+    "channels_rect": ((1, 17), 15_000_001, 1, ODD, False, (0,), IS_RECT + (True,), 11, None),
+}
+
+
+@pytest.mark.parametrize("name", list(ISTFT))
+def test_k_istft_past_2_to_the_32(bufs, name):
+    """routes 0 and 1; the source lies in one half of the buffer, the destination in the other"""
+    from lewton_amd.rows import InverseSpectrogram
+    (R, C), fcap, n_dst, cap, itl, live, (win, hop, window, center), longer, rmap = ISTFT[name]
+    inv = InverseSpectrogram(16, hop, win, window, center)
+    try:
+        m, B = inv.tile_frames, inv.bins
+        assert 2 * B == 18
+        frames = _lens(R, live, (300, 211, 333) if len(live) == 3 else (333,))
+        nat = [inv.out_len(T) for T in frames]
+        assert min(v for v in nat if v) > 2 * m * hop                    # more than two tiles of m x hop samples
+        lens = None if longer is None else [v + longer if v else 0 for v in nat]
+        rows = None
+        if rmap is not None:
+            rest = [d for d in range(n_dst) if d not in rmap.values()]
+            rows = [rmap[r] if r in rmap else rest.pop(0) for r in range(R)]
+            assert len(set(rows)) == R and rows[R - 1] == n_dst - 1
+        Ws, Wd = max(frames) + 41, max(lens or nat) + 41
+        x = IC._source(frames, C, B, Ws, 800 + len(name))
+        sshape = (R, C, 18, fcap)
+        dshape = (n_dst, cap, C) if itl else (n_dst, C, cap)
+        assert math.prod(sshape) <= HALF and math.prod(dshape) <= HALF
+        last_src = (rows or list(range(R))).index(n_dst - 1) if n_dst > 1 else 0
+        if n_dst * C > 1:
+            _assert_crosses(dshape, (lens or nat)[last_src], itl)
+        if name.startswith("lines"):
+            assert _offset(sshape, (0, 0, 16, 0)) == 1 << 32 and _offset(sshape, (0, 0, B + 7, 0)) == 1 << 32    # im[7]
+        if name.startswith("interleaved"):                              # the row and the channel product together
+            assert _offset(sshape, (R - 1, 1, 0, 0)) >= 1 << 32 > _offset(sshape, (R - 1, 0, 0, 0)) > 1 << 31
+        else:
+            _assert_crosses(sshape, frames[-1])
+        src, dst = _view(bufs.a, sshape), _view(bufs.b, dshape)
+        _put(src, x)
+        want = IC._expected(inv, (inv.basis(), inv.window2()), x, frames, lens or nat, rows or list(range(R)), n_dst, Wd)
+        assert not (want[n_dst - 1, C - 1].view(np.uint32) == SENT).all()
+        for route in (0, 1):
+            inv.set_route(route)
+            _sentinel(dst, Wd, itl)
+            torch.cuda.synchronize()
+            out, got_lens = inv.run(src, frames, lengths=lens, out=dst, rows=rows, samples="f32_interleaved" if itl else "f32")
+            torch.cuda.synchronize()
+            assert out is dst and inv.last_route() == route and got_lens.tolist() == (lens or nat)
+            IC.same_bits(_get(dst, Wd, itl), want)
+        assert np.array_equal(_get(src, Ws).view(np.uint32), x.view(np.uint32)), "the source was written"
+    finally:
+        inv.close()
+
+
+# ---- A.10 k_spec_complex
+
+# name -> (source [R][C], live rows, frame capacity, pad mode, rows= map).  n_fft = 16, hop = 4: the destination is [R][C][18][frame
+# capacity], re[j] on line j, im[j] on line 9 + j.  The store is (bin + line0) x d_line with line0 = 9 for the im lines; t.d_at =
+# dst_row x d_row + by x d_ch with d_ch = 18 x d_line.  Nine rows or channels of 18 lines of 2^25 frames are 18 slots of 2^28 and
+# half a slot more, so those destinations take the start of the whole allocation and the source lies behind them
+COMPLEX = {
+    "lines_zero": ((1, 1), (0,), CAP, "zero", False),
+    "lines_reflect": ((1, 1), (0,), ODD, "reflect", False),
+    "rows_zero": ((9, 1), (0, 5, 8), (1 << 25) + 5, "zero", True),
+    "rows_reflect": ((9, 1), (0, 5, 8), 1 << 25, "reflect", True),
+    "channels_zero": ((1, 9), (0,), 1 << 25, "zero", False),
+    "channels_reflect": ((1, 9), (0,), (1 << 25) + 5, "reflect", False),
+}
+
+
+def _complex_want(sp, x, lengths, rows, n_dst, W):
+    """float32 [n_dst][C][2 B][W]: the two chains of the contract over the frame matrices of the pad mode, the sentinel elsewhere"""
+    basis = sp.basis()
+    want = np.full((n_dst, x.shape[1], sp.features, W), SENT_F, F32)
+    for r, n in enumerate(lengths):
+        for c in range(x.shape[1]):
+            if n == 0:
+                assert sp.frames(0) == 0
+                continue
+            X = (XR.frame_matrix(x[r, c, :n], sp.n_fft, sp.win_length, sp.hop) if sp.pad_mode == "reflect" else
+                 SM.frame_matrix(x[r, c, :n], sp.n_fft, sp.win_length, sp.hop, True))
+            assert len(X) == sp.frames(n)
+            want[rows[r], c, :, :len(X)] = IC._chains(basis, X).T
+    return want
+
+
+@pytest.mark.parametrize("name", list(COMPLEX))
+def test_k_spec_complex_past_2_to_the_32(bufs, name):
+    from lewton_amd.rows import Spectrogram
+    (R, C), live, fcap, pad, mapped = COMPLEX[name]
+    sp = Spectrogram(16, 4, pad_mode=pad, output="complex")
+    try:
+        B = sp.bins
+        assert sp.tile_frames == 32 and sp.features == 18 and B == 9
+        lengths = _lens(R, live, (700, 333, 1001))
+        rows = _row_map(R, live[2], live[1]) if mapped else None
+        Ws = max(lengths) + 41
+        Wd = sp.frames(max(lengths)) + 9
+        assert min(sp.frames(v) for v in lengths if v) > 2 * sp.tile_frames
+        x = S._source(lengths, C, Ws, 70 + len(name))
+        sshape, dshape = (R, C, Ws), (R, C, 18, fcap)
+        _assert_crosses(dshape, sp.frames(lengths[(rows or [0]).index(R - 1)]))
+        if name.startswith("lines"):                                    # every re line below 2^32, im[7] at or past it
+            assert _offset(dshape, (0, 0, B - 1, fcap - 1)) < 1 << 32 <= _offset(dshape, (0, 0, B + 7, 0)) and 1 << 31 < _offset(dshape, (0, 0, B, 0))
+        else:                                                           # t.d_at of the last row / channel on its own
+            assert (R * C - 1) * 18 * fcap >= 1 << 32 and HALF < math.prod(dshape) < 2 * HALF - R * C * Ws
+        dst = _view(bufs.big if math.prod(dshape) > HALF else bufs.b, dshape)
+        src = _view(bufs.big[math.prod(dshape):] if math.prod(dshape) > HALF else bufs.a, sshape)
+        src.view(torch.int32).copy_(torch.from_numpy(x.view(np.int32)))
+        want = _complex_want(sp, x, lengths, rows or list(range(R)), R, Wd)
+        for route in (0, 1):
+            sp.set_route(route)
+            _sentinel(dst, Wd)
+            torch.cuda.synchronize()
+            out, frames = sp.run(src, lengths, out=dst, rows=rows)
+            torch.cuda.synchronize()
+            assert out is dst and sp.last_route() == route and frames.tolist() == [sp.frames(v) for v in lengths]
+            _same_spec(_get(dst, Wd), want)
+        assert np.array_equal(src.cpu().numpy().view(np.uint32), x.view(np.uint32)), "the source was written"
+    finally:
+        sp.close()
+
+
 # ---- part B: 65 540 rows in one call
 
 NR = 65540
@@ -732,3 +988,117 @@ def test_cep_65540_rows(identity):
         assert np.array_equal(_live_of(src, LIVE).view(np.uint32), x.view(np.uint32))
     finally:
         cp.close()
+
+
+def test_slide_65540_rows():
+    """[65540][2][3][24] under (W, min, center, norm_vars) = (8, 3, 0, 1): the row record and t.at of the second row range"""
+    from lewton_amd.rows import SlidingCMVN
+    sl = SlidingCMVN(8, 3, False, True)
+    try:
+        n = _live_lengths(24)
+        fill = [min(24, v + 2) for v in n]
+        x = SLM.source(n, 2, 3, 24, 81)
+        src, dst = _many(x), S._filled((NR, 2, 3, 24))
+        sl.run(src, _all_rows(n), out=dst, fill_to=_all_rows(fill))
+        torch.cuda.synchronize()
+        assert sl.last_launches() == 2
+        want = SLM.rows(x, n, fill, np.full(x.shape, SENT_F, F32), 8, 3, False, True)
+        SLM.same_bits(_live_of(dst, LIVE), want, SLM.SENT)
+        _rest_is_sentinel(dst, LIVE)
+        assert np.array_equal(_live_of(src, LIVE).view(np.uint32), x.view(np.uint32))
+    finally:
+        sl.close()
+
+
+SEL_LIVE = [0, 1, 2, 3, 4, 65535, 65536, 65537, 65538, 65539]        # rows k and 65535 + k share the scratch entries of blockIdx.z = k
+
+
+def test_select_65540_rows():
+    """[65540][1][2][300] with a tile of 256: every live row has two tiles, so k_select reads its scratch list.  The second pair of
+    launches reuses the entries of the first: row 65535 + k those of row k, whose mask and length differ -- a list_at formed from the
+    global row, or a cnt_at formed from blockIdx.z, shows.  counts of all 65 540 rows: zeros for the empty ones"""
+    from lewton_amd.rows import SelectFrames
+    se = SelectFrames()
+    try:
+        se.set_tile_frames(256)
+        n = [300 - 3 * i for i in range(len(SEL_LIVE))]
+        fill = [min(300, v + 2) for v in n]
+        assert min(n) > 256
+        x = SEL.source(n, 1, 2, 300, 82)
+        mask = SEL.mask("random", n, 1, 300, 83)
+        want, k = SEL.rows(x, mask, n, fill, np.full(x.shape, SENT_F, F32))
+        assert len(set(k[:, 0].tolist())) > 5 and all(k[i, 0] != k[i + 5, 0] for i in range(5))
+        src = S._filled((NR, 1, 2, 300))
+        src[SEL_LIVE] = torch.from_numpy(x).to("cuda:0")
+        dm = torch.full((NR, 1, 300), SEL.SENT_MASK, dtype=torch.uint8, device="cuda:0")
+        dm[SEL_LIVE] = torch.from_numpy(mask).to("cuda:0")
+        dst = S._filled((NR, 1, 2, 300))
+        all_n, all_fill = [0] * NR, [0] * NR
+        for r, v, f in zip(SEL_LIVE, n, fill):
+            all_n[r], all_fill[r] = v, f
+        _, counts = se.run(src, all_n, dm, out=dst, fill_to=all_fill)
+        torch.cuda.synchronize()
+        assert se.last_launches() == 4
+        SEL.same_bits(_live_of(dst, SEL_LIVE), want)
+        _rest_is_sentinel(dst, SEL_LIVE)
+        all_k = np.zeros((NR, 1), np.int64)
+        all_k[SEL_LIVE] = k
+        assert np.array_equal(counts.cpu().numpy(), all_k)
+        assert np.array_equal(_live_of(src, SEL_LIVE).view(np.uint32), x.view(np.uint32))
+    finally:
+        se.close()
+
+
+@pytest.mark.parametrize("fmt", ["f32", "f32_interleaved"])
+def test_istft_65540_rows(fmt):
+    """[65540][2][6][9] -> [65540][2][8] in reversed row order (a live source row below the cut goes to a destination row above it
+    and the other way round), n_fft = 4, hop = 1, both routes: the row record, t.s_at and the record's dst_row of the second range"""
+    from lewton_amd.rows import InverseSpectrogram
+    itl = fmt.endswith("interleaved")
+    inv = InverseSpectrogram(4, 1)
+    try:
+        frames = [9 - i % 4 for i in range(len(LIVE))]
+        x = IC._source(frames, 2, inv.bins, 9, 84)
+        nat = [inv.out_len(T) for T in frames]
+        lens = [v + (i % 3) - 1 for i, v in enumerate(nat)]
+        cap = max(lens) + 1
+        dst_rows = [NR - 1 - r for r in LIVE]
+        assert any(r < 65535 <= d for r, d in zip(LIVE, dst_rows)) and any(d < 65535 <= r for r, d in zip(LIVE, dst_rows))
+        src = _many(x)
+        want = IC._expected(inv, (inv.basis(), inv.window2()), x, frames, lens, list(range(len(LIVE))), len(LIVE), cap)
+        for route in (0, 1):
+            inv.set_route(route)
+            dst = S._filled((NR, cap, 2) if itl else (NR, 2, cap))
+            inv.run(src, _all_rows(frames), lengths=_all_rows(lens), out=dst, rows=[NR - 1 - r for r in range(NR)], samples=fmt)
+            torch.cuda.synchronize()
+            assert inv.last_route() == route
+            IC.same_bits(_live_of(dst, dst_rows, itl), want)
+            _rest_is_sentinel(dst, dst_rows)
+        assert np.array_equal(_live_of(src, LIVE).view(np.uint32), x.view(np.uint32))
+    finally:
+        inv.close()
+
+
+@pytest.mark.parametrize("pad", ["zero", "reflect"])
+def test_spec_complex_65540_rows(pad):
+    """[65540][2][40] -> [65540][2][18][12] in reversed row order, n_fft = 16, hop = 4, both routes: test_spec_65540_rows with the re
+    and the im lines"""
+    from lewton_amd.rows import Spectrogram
+    sp = Spectrogram(16, 4, pad_mode=pad, output="complex")
+    try:
+        lens = _live_lengths(40)
+        x = S._source(lens, 2, 40, 9)
+        fcap = sp.frames(40) + 1
+        dst_rows = [NR - 1 - r for r in LIVE]
+        src = _many(x)
+        want = _complex_want(sp, x, lens, list(range(len(LIVE))), len(LIVE), fcap)
+        for route in (0, 1):
+            sp.set_route(route)
+            dst = S._filled((NR, 2, sp.features, fcap))
+            _, frames = sp.run(src, _all_rows(lens), out=dst, rows=[NR - 1 - r for r in range(NR)])
+            torch.cuda.synchronize()
+            assert sp.last_route() == route and [int(frames[r]) for r in LIVE] == [sp.frames(v) for v in lens]
+            _same_spec(_live_of(dst, dst_rows), want)
+            _rest_is_sentinel(dst, dst_rows)
+    finally:
+        sp.close()

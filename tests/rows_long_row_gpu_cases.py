@@ -1,10 +1,11 @@
-"""The rows chain past element 2^32 INSIDE a row, on the GPU: k_resample, k_spec, k_feat, k_norm and k_pack on one row of
-2^32 + 2^20 + 5 elements.  The cases of tests/test_gpu_rows_long_row.py, which runs this file with pytest in a process of its own,
+"""The rows chain past element 2^32 INSIDE a row, on the GPU: k_resample, k_spec, k_spec_complex, k_istft, k_feat, k_norm, k_slide,
+k_select and k_pack on one row of 2^32 + 2^20 + 5 elements.  The cases of tests/test_gpu_rows_long_row.py, which runs this file with pytest in a process of its own,
 torch imported first (tests/rows_gpu_cases.py says why).
 
 tests/rows_large_gpu_cases.py crosses 2^32 through every index of the layout with short rows; here the position within ONE row
 crosses it (c x s.el and n x d.el of k_resample, f0 x hop + lead + k and t.f0 + f of k_spec, at + t0 of k_feat and k_norm,
-(u0 + u) x D of k_pack), and a row length above 2^32 reaches the kernels as a count.  A (uint32_t) on one of these gives the samples
+(u0 + u) x D of k_pack, t.t0 and the windows of k_slide, t.t0, base and K of k_select, (bin + line0) x d_line of k_spec_complex,
+t.s0, tf0, r0 and (p - pad) x d.el of k_istft), and a row length above 2^32 reaches the kernels as a count.  A (uint32_t) on one of these gives the samples
 of the row's start under LW_OK without a fault: position 2^32 + k is position k of the same row in 32 bits.
 
 Windows and constant middles.  A row has N = 2^32 + 2^20 + 5 elements (odd: the 16-byte paths have a scalar tail) in a capacity of
@@ -14,15 +15,24 @@ than where it should have gone, which Python integers assert per case.  The whol
 Afterwards the windows of the destination that the source windows reach equal the window forms of the models (tests/*_model.py,
 tests/sparse_rows.py; tests/test_window_models.py checks them against the whole-array models) bit for bit, -0 as +0 where the
 cases of the kernel's own file do so, and EVERY other element is compared on the device, one torch reduction per stretch, with the
-constant a +0.0 source gives there: 0 (k_resample: the bits of the fold of zeros, per phase; unlogged k_spec), LOG(floor) clamped
-and finished (k_feat), (0 - m) g (k_norm), the shift / scale vector per column (k_pack); beyond the fill end, the sentinel.  No
+constant a +0.0 source gives there: 0 (k_resample: the bits of the fold of zeros, per phase; unlogged k_spec, k_spec_complex and
+k_istft: a zero of either sign; k_slide and k_select: +0.0, taken from the model on a short zero row), LOG(floor) clamped and
+finished (k_feat), (0 - m) g (k_norm), the shift / scale vector per column (k_pack); beyond the fill end, the sentinel.  No
 tolerance anywhere.
+
+k_spec_complex and k_istft share one geometry, (n_fft, win_length, hop) = (256, 256, 128), hann, centred: the transform of the long
+row has 258 lines of 2^25 + 2^13 + 1 frames, twice the waveform's size as at any hop of n_fft / 2 (hop = n_fft would halve it,
+but then no sample has two frames and the overlap-add, whose frames tf0 and r0 place, would fold nothing: the geometry is kept).
+k_spec_complex with more than 2^32 FRAMES has no case: four lines of 2^32 frames are 69 GB, and its store is the
+lw_sp_store_lines that k_spec's 32_hop1_mel1_zero crosses.
 
 k_cep has no case here: lw_cep_rows refuses a line of more than 2^24 - 1 tiles (LW_ERR_CAPACITY, include/lewton_amd.h; a tile has
 at most 256 frames), so no frame index of k_cep reaches 2^32 -- DESIGN 6.1.
 
-Memory: ONE allocation of SLOTS x CAP + 8 floats (34.4 GB) for the whole file, viewed per case; PEAK_BYTES bounds what the process
-may hold at its peak, is asserted below 72 GB in Python integers here, and against torch's own peak figure when the file is done."""
+Memory: ONE allocation of CAP + 258 x (2^25 + 2^13 + 4) + 8 floats (51.8 GB: the waveform's line and its complex transform) for
+the whole file, viewed per case, and k_select's mask of N + 3 bytes (4.3 GB) while its two cases run: 56.1 GB at the peak.
+PEAK_BYTES bounds what the process may hold at its peak, is asserted below 72 GB in Python integers here, and against torch's own
+peak figure when the file is done."""
 import torch  # noqa: F401  (first: see above)
 
 import time
@@ -31,13 +41,16 @@ import numpy as np
 import pytest
 
 import feat_model as FM
+import istft_model as IM
 import kaldi_model as K
 import norm_model as NM
 import pack_model as PM
 import resample_model as RM
+import select_model as SEL
+import slide_model as SLM
 import spec_model as SM
 import spec_reflect_model as XM
-from sparse_rows import SparseRow
+from sparse_rows import SparseMask, SparseRow
 
 pytestmark = pytest.mark.gpu
 
@@ -47,10 +60,15 @@ SENT_F = np.array(SENT, np.uint32).view(F32)
 X = 1 << 32                            # the crossing
 N = X + (1 << 20) + 5                  # elements of the long row
 CAP = N + 3
-SLOTS = 2                              # lines of CAP elements in the allocation
-ELEMS = SLOTS * CAP + 8                # (+ 8: a destination line may start one element off the 16-byte boundaries)
-PEAK_BYTES = 4 * ELEMS + (4 << 30)     # the allocation, and 4 GiB for torch's context, the small tensors and the read-backs
-assert N % 2 == 1 and CAP % 4 == 0 and 4 * ELEMS == 34_368_127_072 and PEAK_BYTES < 72_000_000_000
+CX_FFT, CX_HOP = 256, 128              # the complex transform of the long row: 258 lines of CX_T frames, and its inverse
+CX_T = 1 + N // CX_HOP                 # 2^25 + 2^13 + 1 frames
+CX_LINES, CX_FCAP = CX_FFT + 2, CX_T + 3
+CX_ELEMS = CX_LINES * CX_FCAP          # the transform: 2 slots and 67 M elements more
+ELEMS = CAP + CX_ELEMS + 8             # the waveform's slot and the transform (+ 8: a destination line may start one element off the 16-byte boundaries)
+MASK_BYTES = CAP                       # k_select's mask of the long row: a uint8 tensor of its own, alive during those cases only
+PEAK_BYTES = 4 * ELEMS + MASK_BYTES + (4 << 30)   # the allocation, the mask, and 4 GiB for torch's context, the small tensors and the read-backs
+assert N % 2 == 1 and CAP % 4 == 0 and CX_T == (1 << 25) + (1 << 13) + 1 and 2 * CAP < CX_ELEMS < 2 * CAP + (1 << 27)
+assert 4 * ELEMS == 51_820_695_648 and PEAK_BYTES == 60_411_678_824 and PEAK_BYTES < 72_000_000_000
 
 
 def _signed(v, bits=32):
@@ -604,3 +622,316 @@ def test_k_spec_inside_a_row_past_2_to_the_32(buf, name):
             assert np.array_equal(_read(src, a, a + len(d))[:, 0], _u32(d))
     finally:
         sp.close()
+
+
+# ---- k_slide
+
+SL_W = 3000                            # frames per window of the source: more than two tiles of 1024
+# name -> ((W, min, center, norm_vars), (n', fill_to) or None)
+SLIDE = {
+    "centred_vars": ((300, 100, 1, 1), None),
+    "causal": ((8, 3, 0, 0), None),
+    "fill_straddles": ((300, 100, 1, 1), (X - 100, X + 100)),       # the data ends just below the crossing, the fill crosses it
+}
+
+
+def _zero_row_gives(model):
+    """what the model makes of a +0.0 source, taken from the model on a short zero row: one bit pattern"""
+    bits = set(_u32(model(np.zeros((1, 1, 1, 700), F32))).ravel().tolist())
+    assert len(bits) == 1
+    return bits.pop()
+
+
+@pytest.mark.parametrize("name", list(SLIDE))
+def test_k_slide_inside_a_row_past_2_to_the_32(buf, name):
+    """[1][1][1][N + 3] at the default tile of 1024 frames: t.t0, the windows s and e of rule 1 in int64 against t.lo, and the
+    loads and stores at t.at + t.lo + i and t.at + t.t0 + i pass 2^32; the row's T reaches the kernel as a count above 2^32"""
+    from lewton_amd.rows import SlidingCMVN
+    cfg, straddle = SLIDE[name]
+    n, end = straddle or (N, N)
+    W = cfg[0]
+    rng = np.random.default_rng(20 + len(name))
+    wins = [(a, (rng.standard_normal((1, b - a)) * 3.0 - 12.0).astype(F32)) for a, b in _windows(N, SL_W)]
+    row = SparseRow(N, wins).clipped(n)
+    args = (cfg[0], cfg[1], bool(cfg[2]), bool(cfg[3]))
+    m = SL_W + W + 5                                                 # a frame's window reaches at most W frames to either side
+    checks = [(0, m), (X - m, X + m), (N - m, CAP)]
+    tiles = -(-end // 1024)
+    assert tiles == (1 << 22) + 1025 - (straddle is not None) * 1024 and tiles <= 0xFFFFFF
+
+    def want(a, b):
+        return _u32(SLM.window_rows(row, a, b, n, end, np.full((1, b - a), SENT_F, F32), *args)).T
+    zero = _zero_row_gives(lambda x: SLM.rows(x, [700], None, x, *args))
+    assert zero == 0
+    _assert_crosses(checks, end)
+    if straddle is None:
+        _assert_alias_differs(want, 100)
+    clock = _Clock("k_slide " + name)
+    src, dst = _line(buf, 0), _line(buf, CAP + 1)
+    _load(src, n, [(a, d[0, :max(0, min(d.shape[1], n - a))]) for a, d in wins if a < n])
+    _ints(dst).fill_(SENT_I)
+    sl = SlidingCMVN(*args)
+    try:
+        assert sl.tile_frames == 1024
+        clock.lap("load")
+        assert sl.run(src.view(1, 1, 1, CAP), [n], out=dst.view(1, 1, 1, CAP), fill_to=[end]) is not None
+        clock.lap("run")
+        assert sl.last_launches() == 1
+        _verify(dst, end, checks, want, mid_bits(zero), _same_nan)
+        clock.lap("verify")
+        clock.done()
+        for a, d in row.wins:                                         # the source was only read
+            assert np.array_equal(_read(src, a, a + d.shape[1])[:, 0], _u32(d[0]))
+    finally:
+        sl.close()
+
+
+def test_k_slide_refuses_more_tiles_than_a_grid_counts(buf):
+    """a tile of 16 frames on this row is 2^28 tiles and more: LW_ERR_CAPACITY before anything is queued, nothing written"""
+    from lewton_amd.rows import SlidingCMVN
+    src, dst = _line(buf, 0), _line(buf, CAP + 1)
+    src[:N].zero_()
+    _ints(dst).fill_(SENT_I)
+    sl = SlidingCMVN(8, 3, False, False)
+    try:
+        sl.set_tile_frames(16)
+        assert -(-N // 16) > 0xFFFFFF
+        with pytest.raises(ValueError):
+            sl.run(src.view(1, 1, 1, CAP), [N], out=dst.view(1, 1, 1, CAP))
+        torch.cuda.synchronize()
+        mid_bits(SENT)(dst, 0, CAP)
+    finally:
+        sl.close()
+
+
+# ---- k_select_count and k_select
+
+SE_W = 5000                            # frames per window: more than two tiles of 2048
+SE_TILE = 2048                         # every workgroup of k_select adds up ALL tile counts of its row: 2^21 + 513 of them here
+
+
+@pytest.mark.parametrize("name", ["keep_most", "drop_middle"])
+def test_k_select_inside_a_row_past_2_to_the_32(buf, name):
+    """[1][1][1][N + 3] with a mask of N + 3 bytes of its own.  keep_most: the mask is 1 except for random bytes in the three windows
+    (one in ten is 0), so the kept frames of the crossing window land at p - dropped_before(p), at and past 2^32, K > 2^32, and the
+    base of the later tiles sums past 2^32.  drop_middle: the mask is 0 between the first and the last window, so the frames of the
+    last window, gathered from past 2^32, land near the row's start, and the zeroed tail [K, N) runs across 2^32"""
+    from lewton_amd.rows import SelectFrames
+    rng = np.random.default_rng(30 + len(name))
+    ranges = _windows(N, SE_W)
+    wins = [(a, SEL.source([b - a], 1, 1, b - a, 40 + i)[0, 0]) for i, (a, b) in enumerate(ranges)]
+    row = SparseRow(N, wins)
+    if name == "keep_most":
+        bytes_ = [(rng.integers(1, 256, b - a) * (rng.random(b - a) >= 0.1)).astype(np.uint8) for a, b in ranges]
+        sm = SparseMask(N, [(0, SE_W, bytes_[0]), (SE_W, X - SE_W, 1), (X - SE_W, X + SE_W, bytes_[1]), (X + SE_W, N - SE_W, 1), (N - SE_W, N, bytes_[2])])
+    else:
+        bytes_ = [(rng.random(b - a) < 0.5).astype(np.uint8) for a, b in ranges]
+        sm = SparseMask(N, [(0, SE_W, bytes_[0]), (SE_W, N - SE_W, 0), (N - SE_W, N, bytes_[2])])
+    K = sm.count()
+    d0, d1 = (int((v == 0).sum()) for v in bytes_[:2])
+    if name == "keep_most":
+        assert K == N - d0 - d1 - int((bytes_[2] == 0).sum()) and K > X and 0 < d0 and d0 + d1 < SE_W
+        checks = [(0, SE_W + 5), (X - SE_W - d0 - 5, X + SE_W + 5), (K - SE_W - 5, CAP)]
+        assert X - SE_W < int(sm.places(X - 1, X)[0]) < int(sm.places(X, X + 1)[0]) < X + SE_W               # the crossing is fed from the window
+    else:
+        k0 = SE_W - d0
+        assert K == k0 + int((bytes_[2] != 0).sum()) and k0 < K < 2 * SE_W and int(sm.places(K - 1, K)[0]) > X
+        checks = [(0, 2 * SE_W + 5), (X - 5, X + 5), (N - 5, CAP)]
+
+    def want(a, b):
+        return _u32(SEL.window_rows(row, sm, a, b, N, N, np.full((1, b - a), SENT_F, F32))[0]).T
+    zero = _zero_row_gives(lambda x: SEL.rows(x, np.ones((1, 1, 700), np.uint8), [700], None, x)[0])
+    assert zero == 0
+    _assert_crosses(checks, N)
+    if name == "keep_most":
+        _assert_alias_differs(want, 100)
+    clock = _Clock("k_select " + name)
+    src, dst = _line(buf, 0), _line(buf, CAP + 1)
+    _load(src, N, [(a, d) for a, d in wins])
+    _ints(dst).fill_(SENT_I)
+    dm = torch.empty(CAP, dtype=torch.uint8, device="cuda:0")
+    se = SelectFrames()
+    try:
+        dm[N:].fill_(SEL.SENT_MASK)
+        for lo, hi, v in sm.pieces:
+            if isinstance(v, np.ndarray):
+                dm[lo:hi].copy_(torch.from_numpy(v))
+            else:
+                dm[lo:hi].fill_(int(v))
+        se.set_tile_frames(SE_TILE)
+        assert -(-N // SE_TILE) == (1 << 21) + 513 <= 0xFFFFFF
+        clock.lap("load")
+        _, counts = se.run(src.view(1, 1, 1, CAP), [N], dm.view(1, 1, CAP), out=dst.view(1, 1, 1, CAP))
+        clock.lap("run")
+        assert se.last_launches() == 2 and counts.cpu().tolist() == [[K]]
+        _verify(dst, N, checks, want, mid_bits(zero), _same)
+        clock.lap("verify")
+        clock.done()
+        for a, d in wins:                                             # the source and the mask were only read
+            assert np.array_equal(_read(src, a, a + d.shape[1])[:, 0], _u32(d[0]))
+        for lo, hi, v in sm.pieces:
+            if isinstance(v, np.ndarray):
+                assert np.array_equal(dm[lo:hi].cpu().numpy(), v)
+    finally:
+        se.close()
+        del dm
+        torch.cuda.empty_cache()
+
+
+# ---- k_spec_complex and k_istft: one geometry, (n_fft, win_length, hop) = (256, 256, 128), hann, centred
+
+def _verify_lines(lines, end, checks, want, same):
+    """_verify for a destination [lines][capacity], every line at once: checks are stretches [a, b) of frames, read back and
+    compared with want(a, b) (float32 [lines][b - a]) by same() on the bit patterns; every other frame below `end` is a zero of
+    either sign, from `end` on the sentinel, each stretch one reduction along the lines on the device (along: a reduction over
+    all of a strided stretch would copy it first, 34 GB of it)"""
+    cap, pos = lines.shape[1], 0
+    for a, b in list(checks) + [(cap, cap)]:
+        assert pos <= a <= b <= cap, (pos, a, b, cap)
+        if min(a, end) > pos:
+            lo, hi = torch.aminmax(lines[:, pos:min(a, end)], dim=1)   # (a NaN fails: aminmax propagates it)
+            lo, hi = float(lo.min()), float(hi.max())
+            assert lo == 0.0 and hi == 0.0, "frames [%d, %d): %r .. %r, not 0" % (pos, min(a, end), lo, hi)
+        if a > max(pos, end):
+            lo, hi = torch.aminmax(_ints(lines[:, max(pos, end):a]), dim=1)
+            _all_bits(torch.stack([lo, hi]), SENT_I, "frames [%d, %d)" % (max(pos, end), a))
+        if b > a:
+            same(_ints(lines[:, a:b]).cpu().numpy().view(np.uint32), _u32(want(a, b)))
+        pos = b
+
+
+def _chains(basis, Xf):
+    """the two chains of the contract over a frame matrix [T][W]: float32 [2 B][T], the re lines, then the im lines"""
+    re, im = (np.zeros((Xf.shape[0], basis.shape[2]), F32) for _ in range(2))
+    for k in range(basis.shape[1]):
+        re, im = SM.fmaf(Xf[:, k:k + 1], basis[0][k][None, :], re), SM.fmaf(Xf[:, k:k + 1], basis[1][k][None, :], im)
+    return np.concatenate([re, im], axis=1).T
+
+
+# name -> (pad mode, routes).  reflect runs both (route 1, the per-lane fmaf chains, takes 0.57 s for the 2^25 frames); zero runs route 0
+# alone: the index arithmetic around the fold is the same code on both routes
+COMPLEX = {"complex_256_128_reflect": ("reflect", (0, 1)), "complex_256_128_zero": ("zero", (0,))}
+
+
+@pytest.mark.parametrize("name", list(COMPLEX))
+def test_k_spec_complex_inside_a_row_past_2_to_the_32(buf, name):
+    """L[complex_256_128]: [1][1][CAP] of N samples -> [1][1][258][CX_T + 3].  The source sample index f0 x hop + lead + k and, under
+    reflect, the tail read back from len - 1 > 2^32 run in the complex instantiation; its store puts re[j] on line j and im[j] on
+    line 129 + j of a destination of 8.66 G elements, so (bin + line0) x d_line passes 2^32 (at line 128) and 2^33"""
+    from lewton_amd.rows import Spectrogram
+    pad, routes = COMPLEX[name]
+    sp = Spectrogram(CX_FFT, CX_HOP, pad_mode=pad, output="complex")
+    try:
+        frames, F = sp.frames(N), sp.features
+        assert frames == CX_T and F == CX_LINES and (F - 1) * CX_FCAP > 1 << 33 and 128 * CX_FCAP >= X > 127 * CX_FCAP
+        swin = _windows(N, SP_W)
+        data = [np.random.default_rng(50 + len(pad) + i).uniform(-1, 1, b - a).astype(F32) for i, (a, b) in enumerate(swin)]
+        row = SparseRow(N, [(a, d[None]) for (a, _), d in zip(swin, data)])
+        basis = sp.basis()
+        memo = {}
+
+        def lines(a, b):
+            if (a, b) not in memo:
+                out = np.full((F, b - a), SENT_F, F32)
+                hi = min(b, frames)
+                if hi > a:
+                    Xf = (XM.frame_matrix_window(row, a, hi, CX_FFT, CX_FFT, CX_HOP) if pad == "reflect" else
+                          SM.frame_matrix_window(row, a, hi, CX_FFT, CX_FFT, CX_HOP, True))
+                    out[:, :hi - a] = _chains(basis, Xf)
+                memo[a, b] = out
+            return memo[a, b]
+        checks = [(max(0, (a - 2 * CX_FFT) // CX_HOP - 1), min(frames, (b + 2 * CX_FFT) // CX_HOP + 2)) for a, b in swin]
+        checks[-1] = (checks[-1][0], CX_FCAP)
+        xf = X // CX_HOP
+        assert any(a < xf < b for a, b in checks) and (frames - 1) * CX_HOP + CX_FFT > X and checks[1][0] > checks[0][1]
+        assert (_zero_sign(_u32(lines(xf, xf + 20))) != _zero_sign(_u32(lines(0, 20)))).mean() > 0.9
+        assert not np.isnan(lines(xf, xf + 8)).any()
+        src = _line(buf, 0)
+        dst = buf[CAP:CAP + CX_ELEMS].view(F, CX_FCAP)
+        _load(src, N, [(a, d) for (a, _), d in zip(swin, data)])
+        clock = _Clock("k_spec_complex " + name)
+        for route in routes:
+            sp.set_route(route)
+            _ints(dst).fill_(SENT_I)
+            clock.lap("load")
+            out, got_frames = sp.run(src.view(1, 1, CAP), [N], out=dst.view(1, 1, F, CX_FCAP))
+            clock.lap("route %d" % route)
+            assert sp.last_route() == route and got_frames.tolist() == [frames]
+            _verify_lines(dst, frames, checks, lines, _same_zero_sign)
+            clock.lap("verify")
+        clock.done()
+        for (a, _), d in zip(swin, data):                              # the source was only read
+            assert np.array_equal(_read(src, a, a + len(d))[:, 0], _u32(d))
+    finally:
+        sp.close()
+
+
+IS_W = 8192                            # samples per window of the destination that the source's frame windows reach
+IT_T = (1 << 24) + (1 << 12) + 1       # frames of the interleaved case: 2 channels of 2^31 + 2^19 samples, 2^32 + 2^20 elements
+# name -> (channels, frames, samples written per channel, frames per tile (None: the plan's), routes)
+ISTFT = {
+    "istft_256_128_planar": (1, CX_T, N, None, (0, 1)),
+    "istft_256_128_interleaved": (2, IT_T, (IT_T - 1) * CX_HOP + 3, None, (0, 1)),       # (p - pad) x d.el crosses while p does not
+    "istft_256_128_tile_frames_1": (1, CX_T, N, 1, (0,)),                               # more tiles than one launch takes: tile0 != 0
+}
+
+
+@pytest.mark.parametrize("name", list(ISTFT))
+def test_k_istft_inside_a_row_past_2_to_the_32(buf, name):
+    """L[istft_256_128]: random spectral data in the frame windows that map to the three sample windows, +0.0 elsewhere, ->
+    a PCM row.  t.s0 = (tile0 + bx) x span, tf0 and the frame index t.tf0 + fc cross with the sample; r0 is what is left of s0
+    once tf0 x hop is taken off; the store (p - pad) x d.el crosses in the interleaved layout at half the sample index"""
+    from lewton_amd.rows import InverseSpectrogram
+    C, T, length, m1, routes = ISTFT[name]
+    inv = InverseSpectrogram(CX_FFT, CX_HOP)
+    try:
+        natural = inv.out_len(T)
+        xs = X // C                                                    # the sample (per channel) whose element lies at 2^32
+        fcap = CX_ELEMS // (C * CX_LINES)
+        cap = CAP // C
+        assert natural == (T - 1) * CX_HOP and natural < length <= cap and length * C > X and T < fcap and 2 * inv.bins == CX_LINES
+        assert (length > X) == (C == 1)
+        if m1:
+            inv.set_tile_frames(m1)
+        span = inv.tile_frames * CX_HOP
+        tiles = -(-(CX_FFT // 2 + length) // span)
+        assert (tiles > 0xFFFFFF) == bool(m1) and (not m1 or (0xFFFFFF * span < X < tiles * span))
+        G, w2 = inv.basis(), inv.window2()
+        fwin = [(max(0, a // CX_HOP - 2), min(T, b // CX_HOP + 3)) for a, b in _windows(natural, IS_W, xs)]
+        rng = np.random.default_rng(60 + len(name))
+        data = [rng.uniform(-1, 1, (C, CX_LINES, b - a)).astype(F32) for a, b in fwin]
+        rows = [SparseRow(T, [(a, d[c]) for (a, _), d in zip(fwin, data)], CX_LINES) for c in range(C)]
+        m = 2 * CX_FFT
+        checks = [(max(0, a * CX_HOP - m), min(cap, b * CX_HOP + m)) for a, b in fwin]
+        checks[-1] = (checks[-1][0], cap)
+        memo = {}
+
+        def want(a, b):
+            if (a, b) not in memo:
+                memo[a, b] = np.stack([_u32(IM.window_rows(G, w2, r, a, b, T, CX_FFT, CX_HOP, True, length, np.full(b - a, SENT_F, F32))) for r in rows], axis=1)
+            return memo[a, b]
+        assert any(a < xs < b for a, b in checks) and checks[1][0] > checks[0][1] and checks[2][0] > checks[1][1]
+        here, there = _zero_sign(want(xs, xs + 100)), _zero_sign(want(0, 100))
+        assert (here != there).mean() > 0.9 and (here != 0).mean() > 0.9
+        src = buf[CAP:CAP + C * CX_LINES * fcap].view(C * CX_LINES, fcap)
+        dst = _line(buf, 0, cap, C)
+        clock = _Clock("k_istft " + name)
+        src[:, :T].zero_()
+        _ints(src[:, T:]).fill_(SENT_I)
+        for (a, _), d in zip(fwin, data):
+            _ints(src[:, a:a + d.shape[2]]).copy_(torch.from_numpy(d.reshape(C * CX_LINES, -1).view(np.int32)))
+        for route in routes:
+            inv.set_route(route)
+            _ints(dst).fill_(SENT_I)
+            clock.lap("load")
+            shape_d = (1, cap, C) if C > 1 else (1, 1, cap)
+            out, got = inv.run(src.view(1, C, CX_LINES, fcap), [T], lengths=[length], out=dst.view(shape_d), samples="f32_interleaved" if C > 1 else "f32")
+            clock.lap("route %d" % route)
+            assert inv.last_route() == route and got.tolist() == [length]
+            _verify(dst, length, checks, want, mid_zero, _same_zero_sign)
+            clock.lap("verify")
+        clock.done()
+        for (a, _), d in zip(fwin, data):                              # the source was only read
+            assert np.array_equal(_ints(src[:, a:a + d.shape[2]]).cpu().numpy().view(np.uint32), _u32(d.reshape(C * CX_LINES, -1)))
+    finally:
+        inv.close()

@@ -29,6 +29,27 @@ def rows(x, mask, n, fill_to, dst):
     return out, counts
 
 
+def window_rows(row, mask, a, b, T, fill_end, before):
+    """The window form of rows() for ONE row and channel whose lines are +0.0 outside a few windows and whose mask is constant
+    outside a few (tests/sparse_rows.py: row a SparseRow of the F lines, mask a SparseMask, both of at least T frames): positions
+    [a, b) of every destination line after the call, from `before` float32 [F][b - a], and K.  The places of the kept frames come
+    from the mask's stretches in Python integers; the values travel as bit patterns"""
+    assert 0 <= a <= b and T <= fill_end
+    out = np.array(before, F32, copy=True)
+    ob = out.view(np.uint32)
+    m = mask.clipped(T)
+    K = m.count()
+    hi = min(b, K)
+    if hi > a:
+        at = m.places(a, hi)
+        assert len(at) == hi - a and (len(at) < 2 or (np.diff(at) > 0).all())
+        ob[:, :hi - a] = row.clipped(T).gather(at).view(np.uint32)
+    f0, f1 = min(max(a, K), fill_end), min(b, fill_end)
+    if f1 > f0:
+        ob[:, f0 - a:f1 - a] = 0
+    return out, K
+
+
 def same_bits(got, want):
     """every bit, NaN payloads included: the pass copies"""
     g, w = (np.ascontiguousarray(v, F32).view(np.uint32) for v in (got, want))

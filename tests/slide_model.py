@@ -121,6 +121,45 @@ def rows(x, n, fill_to, dst, W, min_window, center, norm_vars):
     return out
 
 
+def window_rows(row, a, b, T, fill_end, before, W, min_window, center, norm_vars):
+    """The window form of rows() for ONE row that is +0.0 outside a few windows (tests/sparse_rows.py: row has the row's lines, all
+    channels, of at least T frames): frames [a, b) of every destination line after the call, from `before` float32 [lines][b - a].
+    Rules 1 and 3 are evaluated at the ABSOLUTE frames: the windows against the row's true T, the block sums on multiples of 16
+    of the ROW wherever [a, b) lies.  Only the frames the windows of [a, b) reach are ever held: they start at a block boundary,
+    so the local blocks are the row's"""
+    assert 0 <= a <= b and T <= fill_end
+    out = np.array(before, F32, copy=True)
+    lo, hi = min(a, T), min(b, T)
+    if hi > lo:
+        wins = [window(t, T, W, min_window, center) for t in range(lo, hi)]
+        s0 = min(s for s, _ in wins) // BLOCK * BLOCK
+        e1 = max(e for _, e in wins)
+        x = row.clipped(T).take(s0, e1)
+        n_el = e1 - s0
+        lists = [[i - s0 if i < T else n_el + (i - T) - s0 // BLOCK for i in terms(s, e, T)] for s, e in wins]
+        K = max(len(v) for v in lists)
+        idx = np.zeros((hi - lo, K), np.int64)
+        cnt = np.array([len(v) for v in lists], np.int64)
+        for t, v in enumerate(lists):
+            idx[t, :len(v)] = v
+        assert int(idx.min()) >= 0 and int(idx.max()) < n_el + n_el // BLOCK
+        with np.errstate(over="ignore", invalid="ignore"):
+            d = x.astype(F64)
+            acc = []
+            for v in (d, d * d):
+                pool = np.concatenate([v, _block_sums(v)], axis=1)
+                s = np.zeros((x.shape[0], hi - lo), F64)
+                for k in range(K):
+                    s = np.where((k < cnt)[None, :], s + pool[:, idx[:, k]], s)
+                acc.append(s)
+        n = np.array([e - s for s, e in wins], np.int64)
+        out[:, lo - a:hi - a] = value(x[:, lo - s0:hi - s0], acc[0], acc[1], n, norm_vars)
+    f0, f1 = min(max(a, T), fill_end), min(b, fill_end)
+    if f1 > f0:
+        out[:, f0 - a:f1 - a] = 0.0
+    return out
+
+
 def same_bits(got, want, sentinel=None):
     """bits; a NaN result equals any NaN (which NaN it is, is outside the contract) except the destination's sentinel, which marks
     what must not have been written"""

@@ -5,6 +5,67 @@ import numpy as np
 F32 = np.float32
 
 
+class SparseMask:
+    """n bytes of a frame mask as stretches that tile [0, n): pieces = [(lo, hi, v)], ascending, v an integer (every byte of the
+    stretch holds it) or a uint8 array of hi - lo bytes.  A non-zero byte keeps its frame"""
+
+    def __init__(self, n, pieces):
+        self.n = int(n)
+        self.pieces = []
+        at = 0
+        for lo, hi, v in pieces:
+            assert lo == at and hi > lo, (at, lo, hi)
+            if not isinstance(v, (int, np.integer)):
+                v = np.ascontiguousarray(v, np.uint8).reshape(-1)
+                assert len(v) == hi - lo
+            else:
+                assert 0 <= int(v) < 256
+            self.pieces.append((int(lo), int(hi), v))
+            at = hi
+        assert at == self.n, (at, self.n)
+
+    @classmethod
+    def of_dense(cls, m, ranges):
+        """the stretches of a dense uint8 [n] mask that is constant between the windows `ranges` = [(lo, hi)]"""
+        m = np.asarray(m, np.uint8)
+        pieces, at = [], 0
+        for lo, hi in list(ranges) + [(len(m), len(m))]:
+            if lo > at:
+                assert (m[at:lo] == m[at]).all(), "the dense mask is not constant outside its windows"
+                pieces.append((at, lo, int(m[at])))
+            if hi > lo:
+                pieces.append((lo, hi, m[lo:hi]))
+            at = max(at, hi)
+        return cls(len(m), pieces)
+
+    def kept(self, lo, hi, v):
+        """kept frames of one stretch, a Python integer"""
+        return (hi - lo if v else 0) if isinstance(v, (int, np.integer)) else int(np.count_nonzero(v))
+
+    def count(self):
+        """K: the kept frames of the whole mask, a Python integer"""
+        return sum(self.kept(*p) for p in self.pieces)
+
+    def places(self, a, b):
+        """int64 [min(b, K) - a]: the frames that the kept frames number a, a + 1, .. are (Python integers per stretch)"""
+        out, before = [], 0
+        for lo, hi, v in self.pieces:
+            k = self.kept(lo, hi, v)
+            j0, j1 = max(a, before), min(b, before + k)
+            if j1 > j0:
+                if isinstance(v, (int, np.integer)):
+                    out.append(np.arange(lo + j0 - before, lo + j1 - before, dtype=np.int64))
+                else:
+                    out.append(lo + np.flatnonzero(v)[j0 - before:j1 - before].astype(np.int64))
+            before += k
+        return np.concatenate(out) if out else np.zeros(0, np.int64)
+
+    def clipped(self, n):
+        """the mask cut to its first n bytes"""
+        assert 0 <= n <= self.n
+        return SparseMask(n, [(lo, min(hi, n), v if isinstance(v, (int, np.integer)) else v[:min(hi, n) - lo]) for lo, hi, v in self.pieces if lo < n])
+
+
 class SparseRow:
     """lines x n float32, +0.0 outside the windows.  wins: [(offset, float32 [lines][length])], ascending, disjoint, inside
     [0, n)"""

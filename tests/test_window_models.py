@@ -187,3 +187,83 @@ def test_resample_fold_is_the_fold_of_the_gpu_cases_file():
     x = np.array([1.0, 2.0, 3.0, 4.0, 5.0, 6.0], F32)
     got = RM.fold(h, 3, 1, 1, x, 2)                                  # output 1: base 3, x[2..5] = 3, 4, 5, 6
     assert got.tolist() == [0.25 * 1 - 2 + 6, 1.5 + 1 - 5 + 12]
+
+
+@pytest.mark.parametrize("n, end", [(T, T), (T, T + 20), (140, 200), (123, 123), (17, 17), (1, 1), (0, 9)])
+@pytest.mark.parametrize("cfg", [(8, 3, 0, 0), (8, 3, 0, 1), (60, 20, 1, 1), (33, 33, 0, 0), (16, 1, 1, 1), (600, 100, 1, 0)])
+def test_slide_window_rows_is_the_whole_model(cfg, n, end):
+    """the term lists at absolute frames: windows that start off the multiples of 16 (125, 30, 7, n - 45), that touch both ends of
+    the row, rows whose T is no multiple of 16, and a window of the rule wider than the row"""
+    import slide_model as SL
+    C, F = 2, 3
+    x = _dense(C * F, 11) * F32(4.0) - F32(12.0) * (_dense(C * F, 11) != 0)
+    row = SparseRow.of_dense(x, RANGES)
+    full = np.full((1, C, F, CAP), SENT_F, F32)
+    full[0, :, :, :T] = x.reshape(C, F, T)
+    before = np.full((1, C, F, CAP), SENT_F, F32)
+    want = SL.rows(full, [n], [end], before, cfg[0], cfg[1], bool(cfg[2]), bool(cfg[3]))
+    for a, b in _positions(n, end, CAP) + [(16, 48), (33, 47)]:
+        got = SL.window_rows(row, a, b, n, end, before[0, :, :, a:b].reshape(C * F, b - a), cfg[0], cfg[1], bool(cfg[2]), bool(cfg[3]))
+        SL.same_bits(got.reshape(C, F, b - a), want[0, :, :, a:b], SL.SENT)
+
+
+@pytest.mark.parametrize("n, end", [(T, T), (T, T + 20), (140, 200), (1, 1), (0, 9)])
+@pytest.mark.parametrize("kind", ["keep_most", "drop_middle", "bytes", "zero", "one"])
+def test_select_window_rows_is_the_whole_model(kind, n, end):
+    """the places from the mask's stretches: a mask that is 1 outside random windows, one that is 0 between the first and the last
+    window, random bytes everywhere, nothing kept, everything kept"""
+    import select_model as SE
+    from sparse_rows import SparseMask
+    Fl = 3
+    x = _dense(Fl, 12)
+    x.view(np.uint32)[1, 130] = 0x7FC00001                           # NaNs of two payloads and a -0 travel as they are
+    x.view(np.uint32)[2, 5] = 0xFFC12345
+    x.view(np.uint32)[0, 299] = 0x80000000
+    row = SparseRow.of_dense(x, RANGES)
+    rng = np.random.default_rng(13)
+    m = np.ones(T, np.uint8)
+    if kind == "keep_most":
+        for lo, hi in RANGES:
+            m[lo:hi] = rng.integers(0, 256, hi - lo) * (rng.random(hi - lo) < 0.6)
+    elif kind == "drop_middle":
+        m[RANGES[0][1]:RANGES[2][0]] = 0
+        m[:RANGES[0][1]] = rng.random(RANGES[0][1]) < 0.5
+    elif kind == "bytes":
+        m[:] = rng.integers(0, 256, T) * (rng.random(T) < 0.7)
+    elif kind == "zero":
+        m[:] = 0
+    sm = SparseMask.of_dense(m, [(0, T)] if kind == "bytes" else RANGES)
+    assert sm.count() == int(np.count_nonzero(m)) and sm.clipped(130).count() == int(np.count_nonzero(m[:130]))
+    full = np.full((1, 1, Fl, CAP), SENT_F, F32)
+    full[0, 0, :, :T] = x
+    fm = np.full((1, 1, CAP), SE.SENT_MASK, np.uint8)
+    fm[0, 0, :T] = m
+    before = np.full((1, 1, Fl, CAP), SENT_F, F32)
+    want, k = SE.rows(full, fm, [n], [end], before)
+    for a, b in _positions(n, end, CAP) + [(int(k[0, 0]) // 2, min(CAP, int(k[0, 0]) + 5))]:
+        got, K = SE.window_rows(row, sm, a, b, n, end, before[0, 0, :, a:b])
+        SE.same_bits(got, want[0, 0, :, a:b])
+        assert K == int(k[0, 0])
+
+
+@pytest.mark.parametrize("frames, extra", [(T, 0), (T, 37), (T, -50), (140, 9), (3, 0), (1, 5), (0, 9)])
+@pytest.mark.parametrize("n_fft, win, hop, name, center", [(16, 16, 4, "hann", True), (16, 16, 4, "hann", False), (16, 16, 16, "rect", False),
+                                                           (32, 20, 5, "hann", True), (25, 25, 7, "hann", True), (64, 64, 32, "hann", True)])
+def test_istft_window_rows_is_the_whole_model(n_fft, win, hop, name, center, frames, extra):
+    """frames and envelope for a sample range: at the row's start (where the envelope may be 0), in its interior, across the natural
+    length into the zeros behind it and across `length` into the untouched capacity; lengths shorter and longer than natural"""
+    import istft_model as IM
+    B = n_fft // 2 + 1
+    X = _dense(2 * B, 14)
+    row = SparseRow.of_dense(X, RANGES)
+    G, w2 = IM.table_f32(n_fft, win, name), IM.window2(name, win)
+    natural = IM.geometry(n_fft, win, hop, center, frames)[4]
+    length = max(0, natural + extra)
+    cap = length + 11
+    whole = np.full(cap, SENT_F, F32)
+    whole[:length] = IM.istft(G, w2, X[:, :frames], n_fft, hop, center, length)
+    for a, b in [(0, min(cap, 50)), (min(cap, 125 * hop + 3), min(cap, 160 * hop)), (min(cap, 30 * hop + 1), min(cap, 180 * hop + 7)),
+                 (max(0, natural - 45), cap), (max(0, length - 1), length), (7, 7), (0, cap), (max(0, length - 3), min(cap, length + 3))]:
+        if a <= b:
+            got = IM.window_rows(G, w2, row, a, b, frames, n_fft, hop, center, length, np.full(b - a, SENT_F, F32))
+            assert np.array_equal(got.view(np.uint32), whole[a:b].view(np.uint32)), (a, b)
