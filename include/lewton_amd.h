@@ -883,6 +883,88 @@ uint32_t lw_slide_tile_frames(const lw_slide *sl);
 int lw_slide_set_tile_frames(lw_slide *sl, uint32_t tile);
 int lw_slide_last_launches(const lw_slide *sl);
 
+/* ---- energy voice-activity decisions of feature rows --------------------------------------------------------------------------
+ * Kaldi's compute-vad-energy on the GPU, as a pass of its own (k_vad): the per-frame voiced / unvoiced decision that every
+ * x-vector, diarization and language-ID recipe takes from the log energy of the RAW features, before apply-cmvn-sliding, and hands
+ * to select-voiced-frames.  The source is f32 [row][ch][F][frame_capacity], the layout of every stage before it; the mask is uint8
+ * [row][ch][frame_capacity], exactly what lw_select_rows takes.  Row i has T = n_frames[i] frames.  An object is made from Kaldi's
+ * options without their vad_ prefix, with Kaldi's defaults: energy_threshold 5.0f, energy_mean_scale 0.5f, frames_context 0,
+ * proportion_threshold 0.6f; line (0) is the feature line that holds the log energy; reserved is 0.  The float parameters are f32,
+ * as Kaldi's BaseFloat.  A contract on BITS, for every row and channel on its own, with e[t] element t of line `line`:
+ *   1  The threshold.  If energy_mean_scale == 0 or T == 0: thr = energy_threshold, and nothing of the line is summed (a NaN in the
+ *      line cannot reach thr).  Otherwise S is the sum S1 of steps 1 and 2 of "normalising rows" taken over this one line with n = T:
+ *      chunks of 256 frames counted from frame 0, ((d0 + d1) + d2) + d3 per lane, the six-level adjacent-pair tree, the chunk list
+ *      folded 64 at a time, all in double.  Then in f32, as Kaldi does after its own double sum:
+ *        sf = (float)S;   p = energy_mean_scale * sf;   q = p / (float)T;   thr = energy_threshold + q
+ *      where (float)T is the round-to-nearest-even conversion of the uint64.  Each of these is ONE IEEE f32 operation, nothing fused.
+ *   2  The raw decision.  d[t] = e[t] > thr, an f32 comparison: a NaN on either side gives 0.
+ *   3  The context.  In signed 64-bit integers: lo = max(0, t - frames_context), hi = min(T, t + frames_context + 1), den = hi - lo,
+ *      num = the number of d set in [lo, hi).  voiced[t] = (float)num >= (float)den * proportion_threshold, with ONE rounded f32
+ *      multiply, as Kaldi's int * BaseFloat does.  The f32 product is part of the contract on purpose:
+ *        (den, num) = (5, 3) at 0.6f:   5 * 0.6f rounds to 3.0f, so the frame IS voiced (the exact product is 3.00000012);
+ *        (den, num) = (10, 6) at 0.6f:  10 * 0.6f rounds to 6.0f, so the frame IS voiced (the exact product is 6.00000024).
+ *      T = 7, frames_context = 2, proportion_threshold 0.6f, d = 1 0 0 1 1 0 1:
+ *        t    0      1      2      3      4      5      6
+ *        lo   0      0      0      1      2      3      4
+ *        hi   3      4      5      6      7      7      7
+ *        den  3      4      5      5      5      4      3
+ *        num  1      2      3      2      3      3      2
+ *        v    0      0      1      0      1      1      1       ((float)den * 0.6f = 1.80000007, 2.4000001, 3.0)
+ *   4  The mask.  mask[t] is the byte 1 or 0 for t < T; positions [T, max(T, fill_to[row])) receive 0.  Every such byte is written
+ *      exactly once and no other byte of d_mask is written -- a wide store never reaches past the span.  Nothing of d_src at or
+ *      beyond T is read, and nothing of any other line.
+ *   5  The thresholds.  d_thr, when given, receives thr as one f32 per row and channel, [n_rows][ch], rows with T == 0 included.
+ *      Which NaN a NaN thr is, is outside the contract.
+ * Against Kaldi: its sum over the line is a sequential double sum, this one a tree.  Both are within a few 2^-53 of the exact sum
+ * per addition, which the conversion to f32 nearly always absorbs; where the two thresholds have the same bits, the masks are
+ * identical.
+ *
+ * lw_vad_rows: n_frames and fill_to (may be NULL: nothing is filled) are HOST arrays, copied during the call.  Asynchronous on
+ * hip_stream; calls on one object may be queued back to back.  Two forms with the same bits: the contract does not know the grid.
+ *   FUSED  ONE kernel launch per 65535 rows, whenever every row's max(T, fill_to) is at most LW_VAD_FUSED_MAX frames (64 chunks, so
+ *          the chunk list is ONE tree): a workgroup of 256 lanes takes a tile of lw_vad_tile_frames frames (1024) of a row and
+ *          channel, recomputes the line's S itself (at most 64 KiB out of L2) and decides its tile; tile 0 stores d_thr.
+ *   SPLIT  THREE launches per 65535 rows for longer rows: the chunk sums into a list the object owns, every row and channel's list
+ *          to thr, the decisions.
+ * With energy_mean_scale == 0 both are the decide launch alone.  With no byte of the mask to write there is no decide launch; d_thr,
+ * when given, is then filled with energy_threshold by a launch of ONE workgroup, which lw_vad_last_launches counts (1; 0 without
+ * d_thr or rows).  The raw decisions of a tile and of frames_context frames either side are ballot words in LDS, num is a popcount;
+ * mask bytes leave as dwords where the address allows and as bytes at the ragged head and tail of a tile's span.  No atomics, no
+ * workgroup waits on another.  A workgroup needs 832 bytes of LDS.
+ * lw_vad_threshold: rule 1 behind the sum on the host, from the same source as the kernels'.  lw_vad_voiced: rule 3 on the host, from
+ * the same source: 1 or 0, -1 for a NULL object.  lw_vad_set_tile_frames: a test's handle on the seams, a multiple of 256 in 256 ..
+ * 2048.  lw_vad_set_route: a test's handle on the two forms; LW_VAD_ROUTE_SPLIT is taken at any length, LW_VAD_ROUTE_FUSED only up to
+ * LW_VAD_FUSED_MAX.  lw_vad_last_launches: the kernels the last accepted call queued, -1 = no call yet.
+ * Refusals, decided on the host before anything is queued:
+ *   LW_ERR_NULL_ARG     v, p or thr NULL, n_frames NULL with rows, d_src NULL with frames to read, d_mask NULL with bytes to write
+ *   LW_ERR_UNSUPPORTED  (create) energy_threshold not finite; energy_mean_scale NaN, negative or infinite; frames_context >
+ *                       LW_VAD_MAX_CONTEXT; proportion_threshold not strictly inside (0, 1); reserved != 0; (set_tile_frames,
+ *                       set_route) a bad value; (rows) LW_VAD_ROUTE_FUSED on a call whose longest max(T, fill_to) exceeds
+ *                       LW_VAD_FUSED_MAX
+ *   LW_ERR_DEVICE       (create) no such device, or one whose workgroups have less LDS than the kernels need (the device is asked)
+ *   LW_ERR_CAPACITY     n_frames[i] or fill_to[i] > frame_capacity, ch == 0 or > 255, F == 0 or > 65535, line >= F, a buffer that 64
+ *                       bits of bytes cannot address, more than 2^24 - 1 tiles in a row */
+#define LW_VAD_MAX_CONTEXT 256
+#define LW_VAD_FUSED_MAX 16384
+typedef struct lw_vad lw_vad;
+enum { LW_VAD_ROUTE_AUTO = 0, LW_VAD_ROUTE_FUSED = 1, LW_VAD_ROUTE_SPLIT = 2 };
+typedef struct {
+	float energy_threshold, energy_mean_scale;
+	uint32_t frames_context;
+	float proportion_threshold;
+	uint32_t line, reserved;
+} lw_vad_params;
+lw_vad *lw_vad_create(int device, const lw_vad_params *p, int *err);
+void lw_vad_destroy(lw_vad *v);
+int lw_vad_rows(lw_vad *v, uint32_t ch, uint32_t F, const void *d_src, uint8_t *d_mask, float *d_thr, size_t n_rows, size_t frame_capacity,
+		const uint64_t *n_frames, const uint64_t *fill_to, void *hip_stream);
+int lw_vad_threshold(const lw_vad *v, double S, uint64_t T, float *thr);
+int lw_vad_voiced(const lw_vad *v, uint64_t num, uint64_t den);
+uint32_t lw_vad_tile_frames(const lw_vad *v);
+int lw_vad_set_tile_frames(lw_vad *v, uint32_t tile);
+int lw_vad_set_route(lw_vad *v, int route);
+int lw_vad_last_launches(const lw_vad *v);
+
 /* ---- frame decisions and frame selection ------------------------------------------------------------------------------------
  * Shortening feature rows by a mask on the GPU, as a pass of its own (k_select): Kaldi's select-voiced-frames for ANY mask -- an
  * energy VAD's, a neural VAD's, a silence trim.  Source and destination are f32 [row][ch][F][frame_capacity], the layout of every

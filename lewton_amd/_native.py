@@ -82,6 +82,11 @@ class SlideParams(C.Structure):
     _fields_ = [("cmn_window", C.c_uint32), ("min_cmn_window", C.c_uint32), ("center", C.c_int32), ("norm_vars", C.c_int32)]
 
 
+class VadParams(C.Structure):
+    _fields_ = [("energy_threshold", C.c_float), ("energy_mean_scale", C.c_float), ("frames_context", C.c_uint32),
+                ("proportion_threshold", C.c_float), ("line", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class OggPacket(C.Structure):
     _fields_ = [("data", C.c_void_p), ("len", C.c_size_t), ("stream_serial", C.c_uint32), ("absgp_page", C.c_uint64),
                 ("first_in_stream", C.c_uint8), ("last_in_stream", C.c_uint8), ("first_in_page", C.c_uint8),
@@ -252,6 +257,16 @@ SYMBOLS = {
     "lw_select_tile_frames": (C.c_uint32, [C.c_void_p]),
     "lw_select_set_tile_frames": (C.c_int, [C.c_void_p, C.c_uint32]),
     "lw_select_last_launches": (C.c_int, [C.c_void_p]),
+    "lw_vad_create": (C.c_void_p, [C.c_int, C.POINTER(VadParams), intp]),
+    "lw_vad_destroy": (None, [C.c_void_p]),
+    "lw_vad_rows": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p,
+                              C.c_void_p, C.c_void_p]),
+    "lw_vad_threshold": (C.c_int, [C.c_void_p, C.c_double, C.c_uint64, C.POINTER(C.c_float)]),
+    "lw_vad_voiced": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64]),
+    "lw_vad_tile_frames": (C.c_uint32, [C.c_void_p]),
+    "lw_vad_set_tile_frames": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "lw_vad_set_route": (C.c_int, [C.c_void_p, C.c_int]),
+    "lw_vad_last_launches": (C.c_int, [C.c_void_p]),
     "lw_ring_create": (C.c_void_p, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, intp]),
     "lw_ring_destroy": (None, [C.c_void_p]),
     "lw_ring_stage": (C.c_int, [C.c_void_p, C.POINTER(Packet), C.c_size_t, C.c_int]),

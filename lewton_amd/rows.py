@@ -57,6 +57,13 @@ float16, padding and the padding mask in one launch, bit for bit):
 
     out, out_frames, mask = FramePack.lfr(80, shift=s, scale=g, dtype="bf16").run(feats, frames, want_mask=True)
 
+EnergyVad, SlidingCMVN and SelectFrames are what the Kaldi speaker and language recipes run between fbank and the model
+(compute-vad-energy on the raw features, apply-cmvn-sliding, select-voiced-frames: lw_vad_rows, lw_slide_rows, lw_select_rows, each
+bit for bit):
+
+    voiced = EnergyVad(5.5, 0.5, 2, 0.12).run(feats, frames)
+    kept, counts = SelectFrames().run(SlidingCMVN(300, 100, center=True).run(feats, frames), frames, voiced)
+
 torch is imported inside the functions, never at module import.
 """
 import ctypes as C
@@ -1220,7 +1227,131 @@ class SelectFrames:
         return out, kept
 
 
-CEP_MAX_IN, CEP_MAX_OUT, CEP_MAX_WIDTH = 256, 256, 16     # LW_CEP_MAX_IN, LW_CEP_MAX_OUT, LW_CEP_MAX_WIDTH
+VAD_MAX_CONTEXT, VAD_FUSED_MAX = 256, 16384               # LW_VAD_MAX_CONTEXT, LW_VAD_FUSED_MAX
+VAD_ROUTES = {"auto": 0, "fused": 1, "split": 2}          # LW_VAD_ROUTE_*
+
+
+def _vad_params(energy_threshold, energy_mean_scale, frames_context, proportion_threshold, line, device):
+    """the parameters as (float32, float32, int, float32, int, int), or ValueError for what lw_vad_create refuses"""
+    vals = []
+    for v, what in ((energy_threshold, "energy_threshold"), (energy_mean_scale, "energy_mean_scale"), (proportion_threshold, "proportion_threshold")):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError("%s=%r: a number" % (what, v))
+        with np.errstate(over="ignore"):
+            vals.append(np.float32(v))
+    thr, scale, prop = vals
+    if not np.isfinite(thr):
+        raise ValueError("energy_threshold=%r: finite as a float32" % (energy_threshold,))
+    if not np.isfinite(scale) or scale < 0:
+        raise ValueError("energy_mean_scale=%r: finite and not negative" % (energy_mean_scale,))
+    if not 0 < prop < 1:
+        raise ValueError("proportion_threshold=%r: strictly inside (0, 1) as a float32" % (proportion_threshold,))
+    for v, what in ((frames_context, "frames_context"), (line, "line"), (device, "device")):
+        if not _is_int(v) or v < 0:
+            raise ValueError("%s=%r: a non-negative integer" % (what, v))
+    if frames_context > VAD_MAX_CONTEXT:
+        raise ValueError("frames_context=%r: at most %d" % (frames_context, VAD_MAX_CONTEXT))
+    if line > 65534:
+        raise ValueError("line=%r: a feature line, below 65535" % (line,))
+    return thr, scale, int(frames_context), prop, int(line), int(device)
+
+
+class EnergyVad:
+    """lw_vad: Kaldi's compute-vad-energy over feature rows [rows][C][F][capacity] on the GPU (k_vad), by the rule of
+    include/lewton_amd.h ("energy voice-activity decisions of feature rows"), a contract on bits: a frame's raw decision is its log
+    energy (feature line `line`) above energy_threshold + energy_mean_scale * the line's mean, and a frame is voiced when at least
+    proportion_threshold of the raw decisions within frames_context frames of it are set.  The arguments are Kaldi's options without
+    their vad_ prefix, with Kaldi's defaults, positional in Kaldi's order: EnergyVad(5.5, 0.5, 2, 0.12) is the SRE recipes' vad.conf.
+    Run it on the RAW features, before SlidingCMVN; the mask goes straight into SelectFrames.run, with no synchronisation in
+    between.  Parameter errors are ValueError and need no GPU; the object itself lives on cuda:device."""
+
+    def __init__(self, energy_threshold=5.0, energy_mean_scale=0.5, frames_context=0, proportion_threshold=0.6, line=0, device=0):
+        thr, scale, ctx, prop, line, device = _vad_params(energy_threshold, energy_mean_scale, frames_context, proportion_threshold, line, device)
+        self.energy_threshold, self.energy_mean_scale, self.frames_context, self.proportion_threshold = float(thr), float(scale), ctx, float(prop)
+        self.line, self.device = line, device
+        _gpu()
+        err = C.c_int(0)
+        p = N.VadParams(thr, scale, ctx, prop, line, 0)
+        self._h = N.lw_vad_create(device, C.byref(p), C.byref(err))
+        if not self._h:
+            if err.value in (N.ERR_UNSUPPORTED, N.ERR_NULL_ARG):
+                raise ValueError("lw_vad_create refused the parameters")
+            raise RuntimeError("lw_vad_create failed (%d): %s" % (err.value, N.device_error()))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            N.lw_vad_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        if N is not None and getattr(N, "lw_vad_destroy", None) is not None:  # not during interpreter shutdown
+            self.close()
+
+    def threshold(self, S, T):
+        """rule 1 behind the sum, on the host (lw_vad_threshold): the float32 threshold of a line of T frames whose sum is S"""
+        thr = C.c_float(0)
+        if not _is_int(T) or T < 0 or N.lw_vad_threshold(self._h, float(S), int(T), C.byref(thr)):
+            raise ValueError("threshold(%r, %r): T a non-negative frame count" % (S, T))
+        return np.float32(thr.value)
+
+    def voiced(self, num, den):
+        """rule 3 on the host (lw_vad_voiced): whether num raw decisions of a window of den frames make the frame voiced"""
+        if not _is_int(num) or not _is_int(den) or not 0 <= num <= den:
+            raise ValueError("voiced(%r, %r): 0 <= num <= den" % (num, den))
+        return N.lw_vad_voiced(self._h, int(num), int(den)) == 1
+
+    @property
+    def tile_frames(self):
+        """frames of a tile (lw_vad_tile_frames)"""
+        return N.lw_vad_tile_frames(self._h)
+
+    def set_tile_frames(self, m):
+        """a test's handle on the seams (lw_vad_set_tile_frames): a multiple of 256 in 256 .. 2048; the result does not depend on it"""
+        if N.lw_vad_set_tile_frames(self._h, int(m)):
+            raise ValueError("tile_frames=%r: a multiple of 256 in 256 .. 2048" % (m,))
+
+    def set_route(self, route):
+        """a test's handle on the two forms (lw_vad_set_route): "auto", "fused" (rows of at most 16384 frames) or "split"; the
+        result does not depend on it"""
+        if route not in VAD_ROUTES or N.lw_vad_set_route(self._h, VAD_ROUTES[route]):
+            raise ValueError("route=%r: one of %s" % (route, ", ".join(sorted(VAD_ROUTES))))
+
+    def last_launches(self):
+        """kernels the last call queued: per 65535 rows 1 (fused, or energy_mean_scale == 0) or 3 (split); with no byte of the mask
+        to write 1 for the thresholds when they are wanted, else 0; -1: no call yet"""
+        return N.lw_vad_last_launches(self._h)
+
+    def run(self, feats, frames, out=None, fill_to=None, stream=None, want_threshold=False):
+        """lw_vad_rows: the decisions of the frames[i] frames of row i of feats (float32 [rows][C][F][capacity]) -> positions
+        [0, frames[i]) of out (None: a zeroed tensor; else a contiguous uint8 or bool tensor [rows][C][capacity] on feats' device);
+        positions [frames[i], fill_to[i]) receive 0.  fill_to: None, one count for all rows or one per row.  Nothing else of out is
+        written.  stream: a hipStream_t value; None = torch's current stream on the object's device.  Asynchronous; returns the
+        mask as a torch.bool [rows][C][capacity] view of out's bytes, and with want_threshold (mask, thr), thr a float32 [rows][C]
+        device tensor of the thresholds."""
+        torch = _gpu()
+        if feats.dtype != torch.float32 or feats.device.type != "cuda" or feats.device.index != self.device or not feats.is_contiguous() or feats.dim() != 4:
+            raise ValueError("feats must be a contiguous float32 tensor [rows][C][F][capacity] on cuda:%d" % self.device)
+        n_rows, ch, F, cap = feats.shape
+        if out is None:
+            out = torch.zeros((n_rows, ch, cap), dtype=torch.uint8, device=feats.device)
+        if (out.dtype not in (torch.bool, torch.uint8) or out.device != feats.device or not out.is_contiguous() or
+                tuple(out.shape) != (n_rows, ch, cap)):
+            raise ValueError("out must be a contiguous bool or uint8 tensor %r on feats' device" % ((n_rows, ch, cap),))
+        counts, fill = _row_counts(frames, n_rows, "frames"), _row_fill(fill_to, n_rows)
+        thr = torch.empty((n_rows, ch), dtype=torch.float32, device=feats.device) if want_threshold else None
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream or None
+        rc = N.lw_vad_rows(self._h, ch, F, C.c_void_p(feats.data_ptr()), C.c_void_p(out.data_ptr()), None if thr is None else C.c_void_p(thr.data_ptr()),
+                           n_rows, cap, counts.ctypes.data_as(C.c_void_p), None if fill is None else fill.ctypes.data_as(C.c_void_p), stream)
+        if rc in (N.ERR_NULL_ARG, N.ERR_CAPACITY, N.ERR_UNSUPPORTED):
+            raise ValueError("lw_vad_rows refused the call (%d)" % rc)
+        if rc:
+            raise RuntimeError("lw_vad_rows: %d %s" % (rc, N.device_error()))
+        mask = out if out.dtype == torch.bool else out.view(torch.bool)
+        return (mask, thr) if want_threshold else mask
+
+
+CEP_MAX_IN,CEP_MAX_OUT, CEP_MAX_WIDTH = 256, 256, 16     # LW_CEP_MAX_IN, LW_CEP_MAX_OUT, LW_CEP_MAX_WIDTH
 
 
 def _is_int(v):
