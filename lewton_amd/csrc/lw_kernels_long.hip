@@ -102,6 +102,39 @@ __device__ __forceinline__ float4_t lds4(const char *base, uint32_t byte_off)
 	return *reinterpret_cast<const float4_t *>(base + byte_off);
 }
 
+// Global access at a wave-uniform base pointer plus a 32-bit byte offset per lane (plus an immediate): the SGPR-base addressing
+// mode of global_load / global_store.  A 64-bit address per lane costs one v_lshl_add_u64 (8-byte encoding) and one v_mov_b32 for
+// the zero high half in front of every access.  Everything that can pass 2^32 (state pool, output offsets) goes into `base`.
+// The base as an inline-asm operand: readfirstlane pins the register class and folds away where the compiler already keeps the value
+// in SGPRs.  Where it does not (k_mix holds the output pointer in VGPRs), a VALU instruction writes the SGPRs, and a memory
+// instruction that reads them needs 5 wait states behind it -- which the compiler does not insert in front of inline asm.  Hence the
+// s_nop, tied to the value: one per base (a group of four stores), not per store.
+__device__ __forceinline__ unsigned long long uniform_base(const void *base)
+{
+	const uintptr_t b = (uintptr_t)base;
+	const uint2_t w = uint2_t{(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)b), (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(b >> 32))};
+	unsigned long long sb = __builtin_bit_cast(unsigned long long, w);
+	asm volatile("s_nop 4" : "+s"(sb));
+	return sb;
+}
+
+template <int IMM = 0>
+__device__ __forceinline__ void store16_wt_u(unsigned long long sbase, uint32_t byte_off, float4_t v)
+{
+	static_assert(IMM >= 0 && IMM < 4096, "immediate offset of a global instruction");
+	asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3 sc1\n\ts_nop 1" ::"v"(byte_off), "v"(v), "s"(sbase), "n"(IMM) : "memory");
+}
+
+// 8-byte write-through PCM store (store_pcm8 of lw_pcm_store.inc) at base + IMM + byte_off.  The offset is laundered in place so that
+// its widening stays next to the store: hoisted out of the block, it hides the 32-bit offset from instruction selection, which then
+// falls back to a 64-bit address per lane.
+template <int IMM = 0>
+__device__ __forceinline__ void store_pcm8_u(void *base, uint32_t &byte_off, uint32_t lo, uint32_t hi)
+{
+	asm volatile("" : "+v"(byte_off));
+	store_pcm8(reinterpret_cast<char *>(base) + IMM + byte_off, lo, hi);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Packed f32 arithmetic.  Every multiply/add of the transform is issued as v_pk_mul_f32 / v_pk_add_f32 on
 // register pairs, with op_sel / op_sel_hi choosing the half of each source that feeds the low / high result
@@ -403,15 +436,22 @@ __device__ __forceinline__ void issue_residue_loads(const LwFastArgs &F, const I
 {
 	// non-temporal loads: the residues are read once -- streaming them past the caches instead of allocating 33 MB per launch
 	// in L2 / MALL took the launch from 16.7 to 15.6 us (interleaved A/B, 2000 steps each)
+	// (wave-uniform base + constant, one 32-bit byte offset per lane: with `64 x + lane` as the index, a lane id whose bits the
+	// compiler does not know -- the laundered one of the round loop -- got a 64-bit address per load)
+	const uint32_t lo = 16u * lane;
 	const float4_t *s0 = reinterpret_cast<const float4_t *>(F.residue + it.res_off + (uint32_t)un.ch_a * 1024u);
 #pragma unroll
-	for (int x = 0; x < 4; x++)
-		p.r[0][x] = NT ? __builtin_nontemporal_load(&s0[64 * x + lane]) : s0[64 * x + lane];
+	for (int x = 0; x < 4; x++) {
+		const float4_t *q = reinterpret_cast<const float4_t *>(reinterpret_cast<const char *>(s0 + 64 * x) + lo);
+		p.r[0][x] = NT ? __builtin_nontemporal_load(q) : *q;
+	}
 	if (PAIR || un.ch_b >= 0) {
 		const float4_t *s1 = reinterpret_cast<const float4_t *>(F.residue + it.res_off + (uint32_t)un.ch_b * 1024u);
 #pragma unroll
-		for (int x = 0; x < 4; x++)
-			p.r[1][x] = NT ? __builtin_nontemporal_load(&s1[64 * x + lane]) : s1[64 * x + lane];
+		for (int x = 0; x < 4; x++) {
+			const float4_t *q = reinterpret_cast<const float4_t *>(reinterpret_cast<const char *>(s1 + 64 * x) + lo);
+			p.r[1][x] = NT ? __builtin_nontemporal_load(q) : *q;
+		}
 	}
 }
 
@@ -577,6 +617,67 @@ __device__ __forceinline__ void spectrum_pair(const char *img, const char *sc, u
 #undef LW_SP_M
 }
 
+// ---- the same when both channels use ONE staged floor (every stereo stream of one submap): the interval offsets (SID16) and the
+//      bin numbers of a lane's bins are then the same for the two channels -- only the segment tables differ, and channel B's sits
+//      1 KB behind channel A's.  The pipeline alternates the channels (step b = 2 x + c): the four entry addresses and the four bin
+//      numbers of group x are formed once and serve both, channel B's entries through the ds_read's immediate offset.
+__device__ __forceinline__ void spectrum_pair_shared(const char *img, const char *sc, uint32_t lane, uint32_t fslot, float4_t (&r)[2][4])
+{
+	const float kf0 = (float)(4 * (int)lane);
+	uint2_t sid[4];
+#pragma unroll
+	for (int x = 0; x < 4; x++)
+		sid[x] = *reinterpret_cast<const uint2_t *>(img + LWI_SID16 + 8u * ((fslot * 4 + x) * 64u + lane));
+	const char *ta[4];
+	float kf[4];
+	float4_t ent[2][4];
+	float fl[2][4];
+#define LW_SS_G(b)                                                                     \
+	do {                                                                               \
+		if (((b) & 1) == 0) {                                                          \
+			const uint2_t sw = sid[(b) >> 1];                                          \
+			ta[0] = sc + (sw.x & 0xffffu);                                             \
+			ta[1] = sc + (sw.x >> 16);                                                 \
+			ta[2] = sc + (sw.y & 0xffffu);                                             \
+			ta[3] = sc + (sw.y >> 16);                                                 \
+		}                                                                              \
+		_Pragma("unroll") for (int j = 0; j < 4; j++)                                  \
+			ent[(b) & 1][j] = lds4(ta[j], 1024u * ((b) & 1));                          \
+	} while (0)
+#define LW_SS_XI(b)                                                                    \
+	do {                                                                               \
+		if (((b) & 1) == 0) {                                                          \
+			_Pragma("unroll") for (int j = 0; j < 4; j++)                              \
+				kf[j] = kf0 + (float)(256 * ((b) >> 1) + j);                           \
+		}                                                                              \
+		_Pragma("unroll") for (int j = 0; j < 4; j++)                                  \
+			fl[(b) & 1][j] = floor_bin(kf[j], ent[(b) & 1][j]);                        \
+	} while (0)
+#define LW_SS_M(b)                                                                     \
+	do {                                                                               \
+		float4_t &rr = r[(b) & 1][(b) >> 1];                                           \
+		const float2_t lo2 = pk_mul(float2_t{fl[(b) & 1][0], fl[(b) & 1][1]}, float2_t{rr.x, rr.y}); \
+		const float2_t hi2 = pk_mul(float2_t{fl[(b) & 1][2], fl[(b) & 1][3]}, float2_t{rr.z, rr.w}); \
+		rr = float4_t{lo2.x, lo2.y, hi2.x, hi2.y};                                     \
+	} while (0)
+	LW_SS_G(0);
+	LW_SS_G(1);
+	__builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+	for (int b = 0; b < 8; b++) {
+		LW_SS_XI(b);
+		if (b + 2 < 8)
+			LW_SS_G(b + 2);
+		if (b >= 1)
+			LW_SS_M(b - 1);
+		__builtin_amdgcn_sched_barrier(0);
+	}
+	LW_SS_M(7);
+#undef LW_SS_G
+#undef LW_SS_XI
+#undef LW_SS_M
+}
+
 // ---- floor value per bin (audio.rs:552-554) of one channel: fl[x][j] = floor of bin 4 (64 x + lane) + j
 __device__ __forceinline__ void floor_values(const char *img, const char *sc, uint32_t lane, uint32_t fslot, bool unused,
 		float4_t (&fl)[4])
@@ -599,6 +700,25 @@ __device__ __forceinline__ void floor_values(const char *img, const char *sc, ui
 	}
 }
 
+// ---- the same for both channels of a pair with ONE staged floor (see spectrum_pair_shared): interval offsets, entry addresses and
+//      bin numbers once, channel B's entries 1 KB behind channel A's
+__device__ __forceinline__ void floor_values_shared(const char *img, const char *sc, uint32_t lane, uint32_t fslot, float4_t (&fl)[2][4])
+{
+	const float kf0 = (float)(4 * (int)lane);
+#pragma unroll
+	for (int x = 0; x < 4; x++) {
+		const uint2_t sw = *reinterpret_cast<const uint2_t *>(img + LWI_SID16 + 8u * ((fslot * 4 + x) * 64u + lane));
+		const uint32_t s16[4] = {sw.x & 0xffffu, sw.x >> 16, sw.y & 0xffffu, sw.y >> 16};
+#pragma unroll
+		for (int j = 0; j < 4; j++) {
+			const char *t = sc + s16[j];
+			const float kf = kf0 + (float)(256 * x + j);
+			fl[0][x][j] = floor_bin(kf, lds4(t, 0u));
+			fl[1][x][j] = floor_bin(kf, lds4(t, 1024u));
+		}
+	}
+}
+
 // ---- the whole floor stage of one unit: segment tables (1 KB each in the wave's scratch) + floor value of every bin this
 //      lane holds.  Needs only the 58-byte floor records, so it runs while the unit's residues are still on their way.
 template <int NCH>
@@ -613,9 +733,13 @@ __device__ __forceinline__ void floor_phase(const LwFastArgs &F, const char *img
 	lds_fence();
 	// (no software pipeline across the channels as in spectrum_pair: this runs while the wave would otherwise idle, and the
 	// plain form needs half the registers)
-	floor_values(img, sc, lane, un.floor_a, unused0, fl[0]);
-	if (NCH == 2)
-		floor_values(img, sc + 1024, lane, un.floor_b, unused1, fl[1]);
+	if (NCH == 2 && !unused0 && !unused1 && un.floor_a == un.floor_b) { // (wave-uniform)
+		floor_values_shared(img, sc, lane, un.floor_a, fl);
+	} else {
+		floor_values(img, sc, lane, un.floor_a, unused0, fl[0]);
+		if (NCH == 2)
+			floor_values(img, sc + 1024, lane, un.floor_b, unused1, fl[1]);
+	}
 	lds_fence();
 	__builtin_amdgcn_s_setprio(0);
 }
@@ -948,16 +1072,36 @@ __device__ __forceinline__ void imdct_pair(const char *img, char *sc, uint32_t l
 }
 
 // ---- inverse coupling (audio.rs:762-777, :990-1002) of a coupled pair on the raw residues
+// decouple4's operations with the results in registers of their own and the operands only read.  The operands here
+// are the dwords of freshly loaded 16-byte tuples: as tied "+v" operands each of them was first copied into a single register (8
+// v_mov_b32 in front of every block, 64 per wave); as plain inputs they are read where the load put them.
+__device__ __forceinline__ void decouple_quads(float4_t &M, float4_t &A)
+{
+	float nm0, na0, nm1, na1, nm2, na2, nm3, na3, t0, t1, t2, t3;
+	unsigned long long c0, c1, c2, c3, d0, d1, d2, d3;
+	// %0-%7 = (m', a') x 4 (out)   %8-%11 = t   %12-%15 = c   %16-%19 = d   %20-%27 = (m, a) x 4 (in)
+	asm("v_cmp_lt_f32_e64 %12, 0, %20\n\tv_cmp_lt_f32_e64 %13, 0, %22\n\tv_cmp_lt_f32_e64 %14, 0, %24\n\tv_cmp_lt_f32_e64 %15, 0, %26\n\t"
+	    "v_cmp_lt_f32_e64 %16, 0, %21\n\tv_cmp_lt_f32_e64 %17, 0, %23\n\tv_cmp_lt_f32_e64 %18, 0, %25\n\tv_cmp_lt_f32_e64 %19, 0, %27\n\t"
+	    "s_xnor_b64 %12, %12, %16\n\ts_xnor_b64 %13, %13, %17\n\ts_xnor_b64 %14, %14, %18\n\ts_xnor_b64 %15, %15, %19\n\t"
+	    "v_cndmask_b32_e64 %8, %21, -%21, %12\n\tv_cndmask_b32_e64 %9, %23, -%23, %13\n\t"
+	    "v_cndmask_b32_e64 %10, %25, -%25, %14\n\tv_cndmask_b32_e64 %11, %27, -%27, %15\n\t"
+	    "v_add_f32_e32 %8, %20, %8\n\tv_add_f32_e32 %9, %22, %9\n\tv_add_f32_e32 %10, %24, %10\n\tv_add_f32_e32 %11, %26, %11\n\t"
+	    "v_cndmask_b32_e64 %1, %20, %8, %16\n\tv_cndmask_b32_e64 %3, %22, %9, %17\n\t"
+	    "v_cndmask_b32_e64 %5, %24, %10, %18\n\tv_cndmask_b32_e64 %7, %26, %11, %19\n\t"
+	    "v_cndmask_b32_e64 %0, %8, %20, %16\n\tv_cndmask_b32_e64 %2, %9, %22, %17\n\t"
+	    "v_cndmask_b32_e64 %4, %10, %24, %18\n\tv_cndmask_b32_e64 %6, %11, %26, %19"
+	    : "=&v"(nm0), "=&v"(na0), "=&v"(nm1), "=&v"(na1), "=&v"(nm2), "=&v"(na2), "=&v"(nm3), "=&v"(na3), "=&v"(t0), "=&v"(t1),
+	      "=&v"(t2), "=&v"(t3), "=&s"(c0), "=&s"(c1), "=&s"(c2), "=&s"(c3), "=&s"(d0), "=&s"(d1), "=&s"(d2), "=&s"(d3)
+	    : "v"(M.x), "v"(A.x), "v"(M.y), "v"(A.y), "v"(M.z), "v"(A.z), "v"(M.w), "v"(A.w));
+	M = float4_t{nm0, nm1, nm2, nm3};
+	A = float4_t{na0, na1, na2, na3};
+}
+
 __device__ __forceinline__ void decouple_pair(Pref &pf)
 {
 #pragma unroll
-	for (int x = 0; x < 4; x++) {
-		float m[4] = {pf.r[0][x].x, pf.r[0][x].y, pf.r[0][x].z, pf.r[0][x].w};
-		float a[4] = {pf.r[1][x].x, pf.r[1][x].y, pf.r[1][x].z, pf.r[1][x].w};
-		decouple4(m[0], a[0], m[1], a[1], m[2], a[2], m[3], a[3]);
-		pf.r[0][x] = float4_t{m[0], m[1], m[2], m[3]};
-		pf.r[1][x] = float4_t{a[0], a[1], a[2], a[3]};
-	}
+	for (int x = 0; x < 4; x++)
+		decouple_quads(pf.r[0][x], pf.r[1][x]);
 }
 
 // ... and up to three inverse-coupling steps (audio.rs:762-777) on the registers r0 / r1 (the unit's channels) and t0 / t1, each
@@ -1004,7 +1148,9 @@ __device__ __forceinline__ void apply_pre(uint32_t prog, Pref &pf, PreRegs &q)
 
 // ---- from the landed residues to the spectrum, floor stage included (the path of a wave whose residues were requested
 //      before it had time for the floor stage): segment tables, inverse coupling, floor x residue fused into the gathers
-template <int NCH, bool SPLIT = false>
+// SHARE: a pair with one staged floor takes spectrum_pair_shared (the round loop's instance keeps to spectrum_pair alone: with both
+// forms in the loop the headline kernel no longer fits 128 registers without scratch)
+template <int NCH, bool SPLIT = false, bool SHARE = false>
 __device__ __forceinline__ void spectrum_fused(const LwFastArgs &F, const char *img, char *sc, uint32_t lane,
 		const LwFastUnit &un, Pref &pf)
 {
@@ -1035,7 +1181,10 @@ __device__ __forceinline__ void spectrum_fused(const LwFastArgs &F, const char *
 		}
 	}
 	if (NCH == 2 && !unused0 && !unused1) {
-		spectrum_pair(img, sc, lane, un.floor_a, un.floor_b, pf.r);
+		if (SHARE && un.floor_a == un.floor_b) // (wave-uniform)
+			spectrum_pair_shared(img, sc, lane, un.floor_a, pf.r);
+		else
+			spectrum_pair(img, sc, lane, un.floor_a, un.floor_b, pf.r);
 	} else {
 		spectrum(F, img, sc, lane, un.floor_a, unused0, pf.r[0]);
 		if (NCH == 2)
@@ -1065,11 +1214,12 @@ __device__ __forceinline__ void spectrum_ready(const LwFastUnit &un, Pref &pf, c
 // operations of a wave execute in order).
 // UP (k_mix): the long blocks' waves share their SIMDs with short blocks' waves that will wait for them: one priority level up
 template <int NCH, int UP = 0>
-__device__ __forceinline__ void long_imdct(const LwFastArgs &F, const char *img, char *sc, uint32_t lane, Pref &pf,
+__device__ __forceinline__ void long_imdct(const LwFastArgs &F, const char *img, char *sc, uint32_t lane, uint32_t wave, Pref &pf,
 		float2_t (&R)[2][2][4])
 {
 	// the last waves to get their data (the launch ends when they do) run the IMDCT one priority level up
-	if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) >= LW_IMDCT_PRIO_LATE)
+	// (wave: the caller's scalar -- reading threadIdx.x again here kept its register occupied through the whole kernel)
+	if (wave >= LW_IMDCT_PRIO_LATE)
 		__builtin_amdgcn_s_setprio(LW_PRIO_IMDCT + 1 + UP);
 	else
 		__builtin_amdgcn_s_setprio(LW_PRIO_IMDCT + UP);
@@ -1145,8 +1295,14 @@ __device__ __forceinline__ void prev_from_lds(const char *src, uint32_t lane, Pr
 
 __device__ __forceinline__ void prev_from_global(const float *g, uint32_t lane, PrevHalf &h)
 {
-	const float4_t g0 = *reinterpret_cast<const float4_t *>(g + 4u * lane);        // q = 4l .. 4l+3
-	const float4_t g1 = *reinterpret_cast<const float4_t *>(g + 508u - 4u * lane); // q = 508-4l ..
+	// (g is wave-uniform: 32-bit byte offsets, see store16_wt_u)
+	// (the offsets are laundered so that their widening stays next to the loads: hoisted out of the block, it hides the 32-bit
+	// offset from instruction selection, which then falls back to a 64-bit address per lane)
+	const char *gb = reinterpret_cast<const char *>(g);
+	uint32_t o0 = 16u * lane, o1 = 2032u - 16u * lane;
+	asm volatile("" : "+v"(o0), "+v"(o1));
+	const float4_t g0 = *reinterpret_cast<const float4_t *>(gb + o0); // q = 4l .. 4l+3
+	const float4_t g1 = *reinterpret_cast<const float4_t *>(gb + o1); // q = 508-4l ..
 	h.pp[0][1] = float2_t{g0.y, g0.x}; // (c2=0: k=2 -> q=4l+1, k=3 -> q=4l)
 	h.pp[1][1] = float2_t{g0.w, g0.z}; // (c2=1: k=2 -> 4l+3, k=3 -> 4l+2)
 	h.pp[1][0] = float2_t{g1.y, g1.x}; // (c2=1: k=0 -> 509-4l, k=1 -> 508-4l)
@@ -1187,7 +1343,7 @@ __device__ __forceinline__ void ola_pack_i16(const char *img, uint32_t lane, con
 __device__ __forceinline__ void store_interleaved2(const LwFastArgs &F, uint32_t lane, uint32_t out_off,
 		const uint32_t (&L)[4][2], const uint32_t (&R)[4][2])
 {
-	int16_t *o = reinterpret_cast<int16_t *>(F.out) + out_off;
+	const unsigned long long sb = uniform_base(reinterpret_cast<int16_t *>(F.out) + out_off);
 	const uint32_t pos[4] = {4u * lane, 508u - 4u * lane, 512u + 4u * lane, 1020u - 4u * lane};
 #pragma unroll
 	for (int g = 0; g < 4; g++) {
@@ -1195,7 +1351,7 @@ __device__ __forceinline__ void store_interleaved2(const LwFastArgs &F, uint32_t
 		const uint32_t d1 = __builtin_amdgcn_perm(R[g][0], L[g][0], 0x07060302u); // (L[p+1], R[p+1])
 		const uint32_t d2 = __builtin_amdgcn_perm(R[g][1], L[g][1], 0x05040100u);
 		const uint32_t d3 = __builtin_amdgcn_perm(R[g][1], L[g][1], 0x07060302u);
-		store16_wt(o + 2u * pos[g], float4_t{__uint_as_float(d0), __uint_as_float(d1), __uint_as_float(d2), __uint_as_float(d3)});
+		store16_wt_u(sb, 4u * pos[g], float4_t{__uint_as_float(d0), __uint_as_float(d1), __uint_as_float(d2), __uint_as_float(d3)});
 	}
 }
 
@@ -1240,7 +1396,7 @@ __device__ __forceinline__ void store_interleaved2_f32(const LwFastArgs &F, uint
 			const float rx = LW_BP(R[g].x), ry = LW_BP(R[g].y), rz = LW_BP(R[g].z), rw = LW_BP(R[g].w);
 #undef LW_BP
 			const float4_t v = odd ? float4_t{lz, rz, lw, rw} : float4_t{lx, rx, ly, ry};
-			store16_wt(o + 2u * (b + 128u * (uint32_t)h + 2u * lane), v);
+			store16_wt_u(uniform_base(o + 2u * (b + 128u * (uint32_t)h)), 16u * lane, v);
 		}
 	}
 }
@@ -1264,10 +1420,11 @@ __device__ __forceinline__ void ola_store(const LwFastArgs &F, const char *img, 
 	const uint32_t p0 = 4u * lane, p1 = 508u - 4u * lane, p2 = 512u + 4u * lane, p3 = 1020u - 4u * lane;
 	if (FMT == LW_OUT_F32_PLANAR) {
 		float *o = reinterpret_cast<float *>(F.out) + out_off + (uint32_t)chn * mch;
-		store16_wt(o + p0, float4_t{O[0][3].x, O[0][2].x, O[1][3].x, O[1][2].x});
-		store16_wt(o + p1, float4_t{O[1][1].x, O[1][0].x, O[0][1].x, O[0][0].x});
-		store16_wt(o + p2, float4_t{O[0][0].y, O[0][1].y, O[1][0].y, O[1][1].y});
-		store16_wt(o + p3, float4_t{O[1][2].y, O[1][3].y, O[0][2].y, O[0][3].y});
+		const unsigned long long sb = uniform_base(o);
+		store16_wt_u(sb, 4u * p0, float4_t{O[0][3].x, O[0][2].x, O[1][3].x, O[1][2].x});
+		store16_wt_u(sb, 4u * p1, float4_t{O[1][1].x, O[1][0].x, O[0][1].x, O[0][0].x});
+		store16_wt_u<2048>(sb, 4u * p0, float4_t{O[0][0].y, O[0][1].y, O[1][0].y, O[1][1].y});
+		store16_wt_u<2048>(sb, 4u * p1, float4_t{O[1][2].y, O[1][3].y, O[0][2].y, O[0][3].y});
 	} else if (FMT == LW_OUT_F32_INTERLEAVED) {
 		// any channel count: 4-byte stores at stride ch (the stereo unit form never gets here, see store_interleaved2_f32)
 		float *o = reinterpret_cast<float *>(F.out) + out_off + (uint32_t)chn;
@@ -1302,19 +1459,20 @@ __device__ __forceinline__ void ola_store(const LwFastArgs &F, const char *img, 
 				uint32_t u;
 			} a, b;
 			int16_t *o = reinterpret_cast<int16_t *>(F.out) + out_off + (uint32_t)chn * mch;
+			uint32_t b0 = 2u * p0, b1 = 2u * p1; // byte offsets of positions 4l.. and 508-4l..; 512+4l.. and 1020-4l.. are 1 KB further
 			{
 			a.s = __builtin_amdgcn_cvt_pk_i16(iq[0][3], iq[0][2]);
 			b.s = __builtin_amdgcn_cvt_pk_i16(iq[1][3], iq[1][2]);
-			store_pcm8(o + p0, a.u, b.u);
+			store_pcm8_u(o, b0, a.u, b.u);
 			a.s = __builtin_amdgcn_cvt_pk_i16(iq[1][1], iq[1][0]);
 			b.s = __builtin_amdgcn_cvt_pk_i16(iq[0][1], iq[0][0]);
-			store_pcm8(o + p1, a.u, b.u);
+			store_pcm8_u(o, b1, a.u, b.u);
 			a.s = __builtin_amdgcn_cvt_pk_i16(im[0][0], im[0][1]);
 			b.s = __builtin_amdgcn_cvt_pk_i16(im[1][0], im[1][1]);
-			store_pcm8(o + p2, a.u, b.u);
+			store_pcm8_u<1024>(o, b0, a.u, b.u);
 			a.s = __builtin_amdgcn_cvt_pk_i16(im[1][2], im[1][3]);
 			b.s = __builtin_amdgcn_cvt_pk_i16(im[0][2], im[0][3]);
-			store_pcm8(o + p3, a.u, b.u);
+			store_pcm8_u<1024>(o, b1, a.u, b.u);
 			}
 		} else {
 			// any channel count: 2-byte stores at stride ch (the stereo case never gets here, see store_interleaved2)
@@ -1347,10 +1505,11 @@ __device__ __forceinline__ void store_left_half(float *dst, uint32_t lane, float
 {
 	const float4_t hi0 = float4_t{-lo1.w, -lo1.z, -lo1.y, -lo1.x}; // 1023-q for q = 511-4l .. 508-4l
 	const float4_t hi1 = float4_t{-lo0.w, -lo0.z, -lo0.y, -lo0.x};
-	store16_wt(dst + 4u * lane, lo0);
-	store16_wt(dst + 508u - 4u * lane, lo1);
-	store16_wt(dst + 512u + 4u * lane, hi0);
-	store16_wt(dst + 1020u - 4u * lane, hi1);
+	const unsigned long long sb = uniform_base(dst);
+	store16_wt_u(sb, 16u * lane, lo0);
+	store16_wt_u(sb, 2032u - 16u * lane, lo1);
+	store16_wt_u<2048>(sb, 16u * lane, hi0);
+	store16_wt_u<2048>(sb, 2032u - 16u * lane, hi1);
 }
 
 // ---- raw right half of one channel to a [1024]-float block (state slot / td block): q ascending, then mirrored
@@ -1358,10 +1517,11 @@ __device__ __forceinline__ void store_right_half(float *dst, uint32_t lane, floa
 {
 	const float4_t hi0 = float4_t{lo1.w, lo1.z, lo1.y, lo1.x}; // 1023-q for q = 511-4l .. 508-4l
 	const float4_t hi1 = float4_t{lo0.w, lo0.z, lo0.y, lo0.x};
-	store16_wt(dst + 4u * lane, lo0);
-	store16_wt(dst + 508u - 4u * lane, lo1);
-	store16_wt(dst + 512u + 4u * lane, hi0);
-	store16_wt(dst + 1020u - 4u * lane, hi1);
+	const unsigned long long sb = uniform_base(dst);
+	store16_wt_u(sb, 16u * lane, lo0);
+	store16_wt_u(sb, 2032u - 16u * lane, lo1);
+	store16_wt_u<2048>(sb, 16u * lane, hi0);
+	store16_wt_u<2048>(sb, 2032u - 16u * lane, hi1);
 }
 
 // ---- four consecutive un-windowed samples of one channel (audio.rs:1119: positions past the overlap are copied), converted

@@ -117,9 +117,9 @@
 		LW_STAMP(1);
 		__builtin_amdgcn_s_setprio(LW_PRIO_PACE);
 		lds_wait_ge(LW_CNT_LANDED(wave - F.late_from), 1u);
-		issue_residue_loads<true, !PRE>(F, it, un, lane_id, pf);
+		issue_residue_loads<true, !PRE>(F, it, un, lane0, pf);
 		if (PRE)
-			issue_pre_loads(F, it, pre_prog, lane_id, pq);
+			issue_pre_loads(F, it, pre_prog, lane0, pq);
 		LW_STAMP(15);
 		if (wave + F.late_from < LW_FAST_WAVES) {
 			asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LW_PACE_VMCNT) : "memory");
@@ -141,9 +141,9 @@
 				lds_wait_ge(LW_CNT_LANDED(wave - F.late_from), 1u);
 				if (valid)
 					{
-				issue_loads<!PRE>(F, it, un, lane_id, pf);
+				issue_loads<!PRE>(F, it, un, lane0, pf);
 				if (PRE)
-					issue_pre_loads(F, it, pre_prog, lane_id, pq);
+					issue_pre_loads(F, it, pre_prog, lane0, pq);
 			}
 			}
 			LW_STAMP(15);
@@ -160,7 +160,7 @@
 			if (PRE)
 				apply_pre(pre_prog, pf, pq);
 			if (two)
-				spectrum_fused<2>(F, img, sc, lane0, un, pf);
+				spectrum_fused<2, false, true>(F, img, sc, lane0, un, pf);
 			else
 				spectrum_fused<1, SPLIT>(F, img, sc, lane0, un, pf);
 		}
@@ -174,8 +174,9 @@
 	for (uint32_t j = 0; j < rounds; j++) {
 		// launder the lane id once per round: everything derived from it (LDS addresses, bin numbers as floats) is
 		// recomputed where it is used instead of being hoisted out of the loop and kept in registers
-		uint32_t lane = lane_id;
-		asm volatile("" : "+v"(lane));
+		// (in place, in the ONE register that holds the lane id from the barrier on: a laundered copy per round kept a second one occupied)
+		asm volatile("" : "+v"(lane0));
+		const uint32_t lane = lane0;
 		float2_t R[2][2][4]; // [channel][c2][k] = (pa, pb) at q_k(m' = 2 lane + c2): un-windowed left / right halves
 		const uint32_t item_n = item0 + (j + 1) * per_round;
 		const bool valid_n = active && j + 1 < rounds && item_n < F.n_items;
@@ -184,9 +185,9 @@
 			itn = load_item(F.items, item_n);
 		if (valid) {
 			if (two)
-				long_imdct<2, MIXF ? 1 : 0>(F, img, sc, lane, pf, R);
+				long_imdct<2, MIXF ? 1 : 0>(F, img, sc, lane, wave, pf, R);
 			else
-				long_imdct<1, MIXF ? 1 : 0>(F, img, sc, lane, pf, R);
+				long_imdct<1, MIXF ? 1 : 0>(F, img, sc, lane, wave, pf, R);
 			if (j == 0)
 				LW_STAMP(8);
 		}
@@ -196,8 +197,9 @@
 				for (int c = 0; c < 2; c++)
 					if (c == 0 || two) {
 						float *dst = F.halo + ((size_t)it.halo_out * F.ch + chn[c]) * 512u;
-						*reinterpret_cast<float4_t *>(dst + 4u * lane) = LW_PB_LO0(c);
-						*reinterpret_cast<float4_t *>(dst + 508u - 4u * lane) = LW_PB_LO1(c);
+						char *dstb = reinterpret_cast<char *>(dst); // (wave-uniform base, 32-bit byte offsets: see store16_wt_u)
+						*reinterpret_cast<float4_t *>(dstb + 16u * lane) = LW_PB_LO0(c);
+						*reinterpret_cast<float4_t *>(dstb + (2032u - 16u * lane)) = LW_PB_LO1(c);
 					}
 			} else {
 				__builtin_amdgcn_s_setprio(LW_PRIO_FINISH); // finish: hand-over, overlap-add, stores
