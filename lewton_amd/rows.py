@@ -107,6 +107,108 @@ def _gpu():
                            "runtime; import torch (or use lewton_amd.rows) before any other lewton_amd module")
     return torch
 
+
+class _Handle:
+    """What the classes over a lw_* handle share: creation with its status check, close(), a __del__ that cannot raise, and the
+    call of a *_rows entry point with its status check.  _C is the prefix of the handle's functions (_C + "_create",
+    _C + "_destroy"), as a string: the library is not loaded when the classes are defined."""
+
+    _C = None
+    _REFUSED_PARAMETERS = ("ERR_UNSUPPORTED", "ERR_NULL_ARG")   # create statuses that are a ValueError (names of lewton_amd._native)
+
+    def _create(self, *args, create="_create"):
+        """self._h from _C + create (args, &err), or ValueError / RuntimeError"""
+        _gpu()
+        err = C.c_int(0)
+        self._h = getattr(N, self._C + create)(*args, C.byref(err))
+        if not self._h:
+            if err.value in [getattr(N, name) for name in self._REFUSED_PARAMETERS]:
+                raise ValueError("%s%s refused the parameters" % (self._C, create))
+            raise RuntimeError("%s%s failed (%d): %s" % (self._C, create, err.value, N.device_error()))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(N, self._C + "_destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        if N is not None and getattr(N, self._C + "_destroy", None) is not None:  # not during interpreter shutdown
+            self.close()
+
+    def _call(self, fn, *args):
+        """fn(handle, *args) for an entry point that returns a status: ValueError for a refusal, RuntimeError for anything else"""
+        rc = fn(self._h, *args)
+        if rc:
+            if rc in (N.ERR_NULL_ARG, N.ERR_CAPACITY, N.ERR_STATE_MISMATCH, N.ERR_UNSUPPORTED):
+                raise ValueError("%s refused the call (%d)" % (fn.__name__, rc))
+            raise RuntimeError("%s: %d %s" % (fn.__name__, rc, N.device_error()))
+
+
+def _stream_of(stream, device):
+    """the hipStream_t value a call is queued on: the caller's, or torch's current stream on the device (None: the null stream)"""
+    if stream is None:
+        import torch
+        stream = torch.cuda.current_stream(device).cuda_stream or None
+    return stream
+
+
+def _tensor_ptr(t):
+    """the address of a tensor's first element as a C argument; None stays None"""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _array_ptr(a):
+    """the address of a numpy array's first element as a C argument; None stays None.  The value does not keep the array alive (and
+    costs half of what data_as does): the caller holds the array for the length of the call"""
+    return None if a is None else C.c_void_p(a.ctypes.data)
+
+
+def _check_tensor(t, what, layout, device, dtypes, dims=None, shape=None):
+    """ValueError that names `what` and the expected `layout`, unless t is a contiguous tensor of one of `dtypes` on cuda:device
+    with one of the dimension counts `dims` (None: any) and, where given, exactly `shape`"""
+    if (t.dtype not in dtypes or not t.is_cuda or t.get_device() != device or not t.is_contiguous() or
+            (dims is not None and t.dim() not in dims) or (shape is not None and tuple(t.shape) != tuple(shape))):
+        raise ValueError("%s must be a contiguous %s tensor %s on cuda:%d, not %s %r on %s" % (
+            what, " or ".join(str(d) for d in dtypes), layout, device, t.dtype, tuple(t.shape), t.device))
+
+
+def _pcm_shape(t, samples, what, device):
+    """(n_rows, channels, row_capacity) of a float32 rows tensor [B, C, T], or [B, T, C] for an interleaved format; or ValueError"""
+    _check_tensor(t, what, "[rows][channels][samples] (interleaved: [rows][samples][channels])", device, (_gpu().float32,), (3,))
+    b, x, y = t.shape
+    return (b, y, x) if N.fmt_interleaved(_FMT[samples]) else (b, x, y)
+
+
+def _row_counts(v, n_rows, what):
+    """one non-negative count per row as uint64, from a list, an array or a tensor"""
+    counts = [int(c) for c in (v.tolist() if hasattr(v, "tolist") else v)]
+    if len(counts) != n_rows or any(c < 0 for c in counts):
+        raise ValueError("%s= needs one non-negative entry per row" % what)
+    return np.asarray(counts, np.uint64)
+
+
+def _row_fill(fill_to, n_rows):
+    """None, or one non-negative count per row as uint64 from one count for all rows or one per row"""
+    if fill_to is None:
+        return None
+    fill = fill_to.tolist() if hasattr(fill_to, "tolist") else fill_to
+    fill = [int(fill)] * n_rows if isinstance(fill, (int, np.integer)) else [int(v) for v in fill]
+    if len(fill) != n_rows or any(v < 0 for v in fill):
+        raise ValueError("fill_to= needs one non-negative count, or one per row")
+    return np.asarray(fill, np.uint64)
+
+
+def _row_map(rows, n_rows):
+    """rows= of the calls that scatter their rows -> (the destination rows as uint32 or None, the rows of a destination that just
+    holds them: max(rows) + 1, or n_rows without a map)"""
+    if rows is None:
+        return None, n_rows
+    rows = [int(v) for v in (rows.tolist() if hasattr(rows, "tolist") else rows)]
+    if len(rows) != n_rows or any(not 0 <= v < 1 << 32 for v in rows):
+        raise ValueError("rows= needs one destination row per source row")
+    return np.asarray(rows, np.uint32), max(rows) + 1 if rows else n_rows
+
+
 ALL = 0xFFFFFFFF  # lw_row_place.keep: all samples that remain behind skip
 PLACE_DTYPE = np.dtype([("row", "<u4"), ("skip", "<u4"), ("keep", "<u4"), ("pad_", "<u4"), ("t0", "<u8")])   # lw_row_place
 _RESULT_DTYPE = np.dtype([("status", "<i4"), ("n_samples", "<u4"), ("out_offset", "<u8")])                    # lw_packet_result
@@ -189,42 +291,26 @@ def torch_dtype(fmt):
     return torch.float32 if fmt in (N.FMT_F32_PLANAR, N.FMT_F32_INTERLEAVED) else torch.int16
 
 
-class Rows:
+class Rows(_Handle):
     """lw_rows: the staging PCM buffer and the segment arrays behind lw_rows_synth, for batches of one decoder and format."""
+
+    _C = "lw_rows"
+    _REFUSED_PARAMETERS = ()    # lw_rows_create reports max_packets == 0 as LW_ERR_NULL_ARG, and that has always been a RuntimeError
 
     def __init__(self, decoder, max_packets, samples="f32"):
         _gpu()
-        err = C.c_int(0)
         self.dec = decoder
         self.fmt = _FMT[samples]
         self.max_packets = max_packets
-        self._h = N.lw_rows_create(decoder._h, max_packets, self.fmt, C.byref(err))
-        if not self._h:
-            raise RuntimeError("lw_rows_create failed (%d): %s" % (err.value, N.device_error()))
+        self._create(decoder._h, max_packets, self.fmt)
 
     create = classmethod(lambda cls, decoder, max_packets, samples="f32": cls(decoder, max_packets, samples))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            N.lw_rows_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        if N is not None and getattr(N, "lw_rows_destroy", None) is not None:  # not during interpreter shutdown
-            self.close()
 
     def check_tensor(self, tensor, out_ch=None):
         """(n_rows, row_capacity) of a rows tensor, or ValueError: dtype, device, contiguity and shape against the format;
         out_ch: the channels of the rows when a matrix is used (None: the decoder's)"""
         ch = self.dec.ident.audio_channels if out_ch is None else out_ch
-        if tensor.dtype != torch_dtype(self.fmt):
-            raise ValueError("rows tensor is %s, the format needs %s" % (tensor.dtype, torch_dtype(self.fmt)))
-        if tensor.device.type != "cuda" or tensor.device.index != self.dec.device:
-            raise ValueError("rows tensor is on %s, the decoder on cuda:%d" % (tensor.device, self.dec.device))
-        if not tensor.is_contiguous():
-            raise ValueError("rows tensor is not contiguous")
-        if tensor.dim() != 3:
-            raise ValueError("rows tensor must have three dimensions, not %d" % tensor.dim())
+        _check_tensor(tensor, "rows tensor", "of three dimensions", self.dec.device, (torch_dtype(self.fmt),), (3,))
         if N.fmt_interleaved(self.fmt):
             if tensor.shape[2] != ch:
                 raise ValueError("interleaved rows are [rows][samples][%d channels], not %s" % (ch, tuple(tensor.shape)))
@@ -238,25 +324,18 @@ class Rows:
         (row, skip, keep, t0) per packet of the batch, or an array of PLACE_DTYPE.  stream: a hipStream_t value; None = torch's
         current stream on the decoder's device.  mix: a channel matrix, array-like [out_ch][in_ch] (lw_rows_synth_mix, k_rows_mix
         in place of k_rows); the tensor then has out_ch channels.  Asynchronous."""
-        torch = _gpu()
+        _gpu()
         if mix is not None:
             mix = mix_array(mix, self.dec.ident.audio_channels)
         n_rows, cap = self.check_tensor(tensor, None if mix is None else mix.shape[0])
         arr = places_array(places)
-        if stream is None:
-            stream = torch.cuda.current_stream(self.dec.device).cuda_stream or None
-        pl = arr.ctypes.data_as(C.c_void_p) if arr.size else None
+        stream = _stream_of(stream, self.dec.device)
+        pl = _array_ptr(arr if arr.size else None)
         if mix is None:
-            name = "lw_rows_synth"
-            rc = N.lw_rows_synth(self._h, batch._h, pl, arr.size, C.c_void_p(tensor.data_ptr()), n_rows, cap, stream)
+            self._call(N.lw_rows_synth, batch._h, pl, arr.size, _tensor_ptr(tensor), n_rows, cap, stream)
         else:
-            name = "lw_rows_synth_mix"
-            m = N.RowMix(mix.shape[0], mix.shape[1], mix.ctypes.data_as(C.c_void_p))      # (the coefficients are copied by the call)
-            rc = N.lw_rows_synth_mix(self._h, batch._h, pl, arr.size, C.byref(m), C.c_void_p(tensor.data_ptr()), n_rows, cap, stream)
-        if rc in (N.ERR_NULL_ARG, N.ERR_CAPACITY, N.ERR_STATE_MISMATCH, N.ERR_UNSUPPORTED):
-            raise ValueError("%s refused the call (%d)" % (name, rc))
-        if rc:
-            raise RuntimeError("%s: %d %s" % (name, rc, N.device_error()))
+            m = N.RowMix(mix.shape[0], mix.shape[1], _array_ptr(mix))      # (the coefficients are copied by the call)
+            self._call(N.lw_rows_synth_mix, batch._h, pl, arr.size, C.byref(m), _tensor_ptr(tensor), n_rows, cap, stream)
 
     @property
     def last_segments(self):
@@ -300,10 +379,12 @@ def _resample_params(resample):
     return p
 
 
-class Resampler:
+class Resampler(_Handle):
     """lw_resampler: rows of f32 PCM at in_rate -> rows at out_rate on the GPU (k_resample), by the windowed-sinc polyphase filter
     of include/lewton_amd.h ("resampling rows"), a contract on bits.  window: "hann" or "kaiser" (beta: KAISER_BETA when None).
     Parameter errors are ValueError and need no GPU; the object itself lives on cuda:device."""
+
+    _C = "lw_resampler"
 
     def __init__(self, in_rate, out_rate, zeros=6, rolloff=0.99, window="hann", beta=None, device=0):
         if window not in _WINDOWS:
@@ -314,32 +395,16 @@ class Resampler:
             raise ValueError("beta=%r: in [0, 700)" % (beta,))
         self.orig, self.new, self.half_width, self.taps_per_phase = resample_geometry(in_rate, out_rate, zeros, rolloff)
         self.in_rate, self.out_rate, self.device = int(in_rate), int(out_rate), device
-        _gpu()
-        err = C.c_int(0)
-        self._h = N.lw_resampler_create(device, int(in_rate), int(out_rate), int(zeros), float(rolloff), _WINDOWS[window], float(beta),
-                                        C.byref(err))
-        if not self._h:
-            if err.value == N.ERR_UNSUPPORTED:
-                raise ValueError("lw_resampler_create refused the parameters")
-            raise RuntimeError("lw_resampler_create failed (%d): %s" % (err.value, N.device_error()))
+        self._create(device, int(in_rate), int(out_rate), int(zeros), float(rolloff), _WINDOWS[window], float(beta))
         geo = [C.c_uint32() for _ in range(4)]
         N.lw_resampler_geometry(self._h, *[C.byref(g) for g in geo])
         assert tuple(g.value for g in geo) == (self.orig, self.new, self.half_width, self.taps_per_phase)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            N.lw_resampler_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        if N is not None and getattr(N, "lw_resampler_destroy", None) is not None:  # not during interpreter shutdown
-            self.close()
 
     def taps(self):
         """the filter [new][K], float32"""
         out = np.empty((self.new, self.taps_per_phase), np.float32)
         assert N.lw_resampler_taps(self._h, None) == out.size
-        N.lw_resampler_taps(self._h, out.ctypes.data_as(C.c_void_p))
+        N.lw_resampler_taps(self._h, _array_ptr(out))
         return out
 
     def out_len(self, n):
@@ -353,17 +418,7 @@ class Resampler:
 
     def check_tensor(self, tensor, samples, what):
         """(n_rows, channels, row_capacity) of a rows tensor, or ValueError: as Rows.check_tensor, for the two f32 formats"""
-        torch = _gpu()
-        if tensor.dtype != torch.float32:
-            raise ValueError("%s is %s, the resampler works on float32" % (what, tensor.dtype))
-        if tensor.device.type != "cuda" or tensor.device.index != self.device:
-            raise ValueError("%s is on %s, the resampler on cuda:%d" % (what, tensor.device, self.device))
-        if not tensor.is_contiguous():
-            raise ValueError("%s is not contiguous" % what)
-        if tensor.dim() != 3:
-            raise ValueError("%s must have three dimensions, not %d" % (what, tensor.dim()))
-        b, x, y = tensor.shape
-        return (b, y, x) if N.fmt_interleaved(_FMT[samples]) else (b, x, y)
+        return _pcm_shape(tensor, samples, what, self.device)
 
     def run(self, src, lengths, out=None, rows=None, stream=None, samples="f32"):
         """lw_resample_rows: row i of src ([B, C, T], or [B, T, C] for samples="f32_interleaved"), lengths[i] samples per channel,
@@ -375,31 +430,16 @@ class Resampler:
         if fmt not in (N.FMT_F32_PLANAR, N.FMT_F32_INTERLEAVED):
             raise ValueError("the resampler works on the f32 formats, not %r" % (samples,))
         n_src, ch, cap = self.check_tensor(src, samples, "src")
-        lens = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
-        if len(lens) != n_src or any(v < 0 for v in lens):
-            raise ValueError("lengths= needs one non-negative entry per row of src")
-        lens = np.asarray(lens, np.uint64)
-        rmap = None
-        if rows is not None:
-            rows = [int(v) for v in (rows.tolist() if hasattr(rows, "tolist") else rows)]
-            if len(rows) != n_src or any(not 0 <= v < 1 << 32 for v in rows):
-                raise ValueError("rows= needs one destination row per row of src")
-            rmap = np.asarray(rows, np.uint32)
+        lens = _row_counts(lengths, n_src, "lengths")
+        rmap, n_dst = _row_map(rows, n_src)
         if out is None:
-            n_dst = max(rows) + 1 if rows else n_src
             T = max([self.out_len(v) for v in lens.tolist()], default=0)
             out = torch.zeros((n_dst, T, ch) if N.fmt_interleaved(fmt) else (n_dst, ch, T), dtype=torch.float32, device="cuda:%d" % self.device)
         n_dst, och, dcap = self.check_tensor(out, samples, "out")
         if och != ch:
             raise ValueError("out has %d channels, src %d" % (och, ch))
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device).cuda_stream or None
-        rc = N.lw_resample_rows(self._h, fmt, ch, C.c_void_p(src.data_ptr()), n_src, cap, lens.ctypes.data_as(C.c_void_p),
-                                None if rmap is None else rmap.ctypes.data_as(C.c_void_p), C.c_void_p(out.data_ptr()), n_dst, dcap, stream)
-        if rc in (N.ERR_NULL_ARG, N.ERR_CAPACITY, N.ERR_UNSUPPORTED):
-            raise ValueError("lw_resample_rows refused the call (%d)" % rc)
-        if rc:
-            raise RuntimeError("lw_resample_rows: %d %s" % (rc, N.device_error()))
+        self._call(N.lw_resample_rows, fmt, ch, _tensor_ptr(src), n_src, cap, _array_ptr(lens), _array_ptr(rmap), _tensor_ptr(out),
+                   n_dst, dcap, _stream_of(stream, self.device))
         return out
 
 
@@ -502,7 +542,7 @@ def _spec_params(n_fft, hop, win_length, window, mel):
     return int(win_length), mel
 
 
-class Spectrogram:
+class Spectrogram(_Handle):
     """lw_spec: rows of f32 PCM -> power spectrum or mel features on the GPU (k_spec), by the windowed DFT of
     include/lewton_amd.h ("spectral frames of rows"), a contract on bits.  window: "hann" (periodic), "rect", or the symmetric
     (i / (win_length - 1)) "povey", "hamming_sym", "hann_sym", "blackman_sym"; win_length: n_fft when None; mel: None for the power spectrum [n_fft // 2 + 1 lines], or a matrix [n_mels][n_fft // 2 + 1] (mel_filterbank).
@@ -515,6 +555,8 @@ class Spectrogram:
     energy puts the frame's energy (after remove_dc, before pre-emphasis and window, times scale^2) in line 0, the other lines
     behind it.  output: "power", or "complex": 2 * bins lines, re[j] on line j and im[j] on line bins + j, the chains themselves
     (as_complex() makes the complex tensor; InverseSpectrogram reads the lines as they are); not with mel=, remove_dc or energy.  Parameter errors are ValueError and need no GPU; the object itself lives on cuda:device."""
+
+    _C = "lw_spec"
 
     def __init__(self, n_fft=400, hop=160, win_length=None, window="hann", center=True, mel=None, device=0, pad_mode="zero",
                  framing="stft", snip_edges=True, preemphasis=0.0, remove_dc=False, energy=False, scale=1.0, output="power"):
@@ -542,29 +584,15 @@ class Spectrogram:
         self.preemphasis, self.scale, self.remove_dc, self.energy, self.window = preemphasis, scale, bool(remove_dc), bool(energy), window
         self.n_fft, self.hop, self.center, self.device = int(n_fft), int(hop), bool(center), device
         _gpu()
-        err = C.c_int(0)
         n_mels = 0 if self._mel is None else self._mel.shape[0]
         p = N.SpecParams(self.n_fft, self.win_length, self.hop, n_mels, None if self._mel is None else self._mel.ctypes.data, _SPEC_WINDOWS[window],
                          int(self.center), _SPEC_FRAMINGS[framing, bool(snip_edges)], int(self.remove_dc), int(self.energy), 0, preemphasis, scale, _SPEC_OUTPUTS[output])
-        self._h = N.lw_spec_create_ex(device, C.byref(p), C.byref(err))
-        if not self._h:
-            if err.value in (N.ERR_UNSUPPORTED, N.ERR_NULL_ARG):
-                raise ValueError("lw_spec_create_ex refused the parameters")
-            raise RuntimeError("lw_spec_create_ex failed (%d): %s" % (err.value, N.device_error()))
+        self._create(device, C.byref(p), create="_create_ex")
         assert self.bins == self.n_fft // 2 + 1
         assert self.features == (2 * self.bins if output == "complex" else (n_mels or self.bins) + int(self.energy))
         if framing == "stft" and N.lw_spec_set_pad_mode(self._h, _SPEC_PAD_MODES[pad_mode]):
             self.close()
             raise ValueError("lw_spec_set_pad_mode refused pad_mode=%r" % (pad_mode,))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            N.lw_spec_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        if N is not None and getattr(N, "lw_spec_destroy", None) is not None:  # not during interpreter shutdown
-            self.close()
 
     @property
     def bins(self):
@@ -587,7 +615,7 @@ class Spectrogram:
         """[2][win_length][bins] float32: C, then S, the window folded in"""
         out = np.empty((2, self.win_length, self.bins), np.float32)
         assert N.lw_spec_basis(self._h, None) == out.size
-        N.lw_spec_basis(self._h, out.ctypes.data_as(C.c_void_p))
+        N.lw_spec_basis(self._h, _array_ptr(out))
         return out
 
     @staticmethod
@@ -607,17 +635,7 @@ class Spectrogram:
 
     def check_tensor(self, tensor, samples, what):
         """(n_rows, channels, row_capacity) of a source rows tensor, or ValueError: as Resampler.check_tensor"""
-        torch = _gpu()
-        if tensor.dtype != torch.float32:
-            raise ValueError("%s is %s, the spectrogram works on float32" % (what, tensor.dtype))
-        if tensor.device.type != "cuda" or tensor.device.index != self.device:
-            raise ValueError("%s is on %s, the spectrogram on cuda:%d" % (what, tensor.device, self.device))
-        if not tensor.is_contiguous():
-            raise ValueError("%s is not contiguous" % what)
-        if tensor.dim() != 3:
-            raise ValueError("%s must have three dimensions, not %d" % (what, tensor.dim()))
-        b, x, y = tensor.shape
-        return (b, y, x) if N.fmt_interleaved(_FMT[samples]) else (b, x, y)
+        return _pcm_shape(tensor, samples, what, self.device)
 
     def run(self, src, lengths, out=None, rows=None, stream=None, samples="f32", log=None, floor=1e-10):
         """lw_spec_rows: row i of src ([B, C, T], or [B, T, C] for samples="f32_interleaved"), lengths[i] samples per channel,
@@ -634,38 +652,23 @@ class Spectrogram:
         if log not in (None, "ln", "log10"):
             raise ValueError("log=%r: None, \"ln\" or \"log10\"" % (log,))
         n_src, ch, cap = self.check_tensor(src, samples, "src")
-        lens = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
-        if len(lens) != n_src or any(v < 0 for v in lens):
-            raise ValueError("lengths= needs one non-negative entry per row of src")
-        frames = [self.frames(v) for v in lens]
-        lens = np.asarray(lens, np.uint64)
-        rmap = None
-        if rows is not None:
-            rows = [int(v) for v in (rows.tolist() if hasattr(rows, "tolist") else rows)]
-            if len(rows) != n_src or any(not 0 <= v < 1 << 32 for v in rows):
-                raise ValueError("rows= needs one destination row per row of src")
-            rmap = np.asarray(rows, np.uint32)
+        lens = _row_counts(lengths, n_src, "lengths")
+        frames = [self.frames(v) for v in lens.tolist()]
+        rmap, n_dst = _row_map(rows, n_src)
         F = self.features
         if out is None:
-            n_dst = max(rows) + 1 if rows else n_src
             out = torch.zeros((n_dst, ch, F, max(frames, default=0)), dtype=torch.float32, device="cuda:%d" % self.device)
-        if out.dtype != torch.float32 or out.device.type != "cuda" or out.device.index != self.device or not out.is_contiguous():
-            raise ValueError("out must be a contiguous float32 tensor on cuda:%d" % self.device)
-        if out.dim() != 4 or out.shape[1] != ch or out.shape[2] != F:
+        _check_tensor(out, "out", "[rows][%d channels][%d features][frames]" % (ch, F), self.device, (torch.float32,), (4,))
+        if out.shape[1] != ch or out.shape[2] != F:
             raise ValueError("out must be [rows][%d channels][%d features][frames], not %r" % (ch, F, tuple(out.shape)))
         n_dst, fcap = out.shape[0], out.shape[3]
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device).cuda_stream or None
-        rc = N.lw_spec_rows(self._h, fmt, ch, C.c_void_p(src.data_ptr()), n_src, cap, lens.ctypes.data_as(C.c_void_p),
-                            None if rmap is None else rmap.ctypes.data_as(C.c_void_p), C.c_void_p(out.data_ptr()), n_dst, fcap, stream)
-        if rc in (N.ERR_NULL_ARG, N.ERR_CAPACITY, N.ERR_UNSUPPORTED):
-            raise ValueError("lw_spec_rows refused the call (%d)" % rc)
-        if rc:
-            raise RuntimeError("lw_spec_rows: %d %s" % (rc, N.device_error()))
+        stream = _stream_of(stream, self.device)
+        self._call(N.lw_spec_rows, fmt, ch, _tensor_ptr(src), n_src, cap, _array_ptr(lens), _array_ptr(rmap), _tensor_ptr(out), n_dst, fcap,
+                   stream)
         if log is not None and n_dst and max(frames, default=0):
             per_row = [0] * n_dst
             for i, n in enumerate(frames):
-                per_row[rows[i] if rows else i] = n
+                per_row[i if rmap is None else rmap[i]] = n
             with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=self.device) if stream else torch.cuda.default_stream(self.device)):
                 count = torch.tensor(per_row, dtype=torch.int64).to(out.device)
                 part = out[:, :, :, :max(frames)]                        # no frame of this call lies beyond
@@ -675,12 +678,14 @@ class Spectrogram:
         return out, torch.tensor(frames, dtype=torch.int64)
 
 
-class InverseSpectrogram:
+class InverseSpectrogram(_Handle):
     """lw_istft: complex spectral frames [rows][C][2 * bins][frames] (Spectrogram(output="complex")'s lines: re, then im) -> rows
     of f32 PCM on the GPU (k_istft), by the inverse DFT, overlap-add and envelope division of include/lewton_amd.h ("inverse
     spectral frames of rows"), a contract on bits; torch.istft's algorithm with the analysis window.  window, win_length and
     center as Spectrogram's; hop <= win_length and ceil(win_length / hop) <= 16.  Where the window envelope is not above 1e-11 a
     sample is +0.0 (torch raises).  Parameter errors are ValueError and need no GPU; the object itself lives on cuda:device."""
+
+    _C = "lw_istft"
 
     def __init__(self, n_fft=400, hop=160, win_length=None, window="hann", center=True, device=0):
         self.win_length, _ = _spec_params(n_fft, hop, win_length, window, None)
@@ -688,23 +693,9 @@ class InverseSpectrogram:
             raise ValueError("hop=%r: at most win_length, and at least win_length / %d" % (hop, ISTFT_MAX_OVERLAP))
         self.n_fft, self.hop, self.center, self.window, self.device = int(n_fft), int(hop), bool(center), window, device
         _gpu()
-        err = C.c_int(0)
         p = N.IstftParams(self.n_fft, self.win_length, self.hop, _SPEC_WINDOWS[window], int(self.center), 0)
-        self._h = N.lw_istft_create(device, C.byref(p), C.byref(err))
-        if not self._h:
-            if err.value in (N.ERR_UNSUPPORTED, N.ERR_NULL_ARG):
-                raise ValueError("lw_istft_create refused the parameters")
-            raise RuntimeError("lw_istft_create failed (%d): %s" % (err.value, N.device_error()))
+        self._create(device, C.byref(p))
         assert self.bins == self.n_fft // 2 + 1
-
-    def close(self):
-        if getattr(self, "_h", None):
-            N.lw_istft_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        if N is not None and getattr(N, "lw_istft_destroy", None) is not None:  # not during interpreter shutdown
-            self.close()
 
     @property
     def bins(self):
@@ -727,14 +718,14 @@ class InverseSpectrogram:
         """[2 * bins][win_length] float32: the cosine lines, then the sine lines, window and 1 / n_fft folded in"""
         out = np.empty((2 * self.bins, self.win_length), np.float32)
         assert N.lw_istft_basis(self._h, None) == out.size
-        N.lw_istft_basis(self._h, out.ctypes.data_as(C.c_void_p))
+        N.lw_istft_basis(self._h, _array_ptr(out))
         return out
 
     def window2(self):
         """[win_length] float64: the squared window the envelope is folded from"""
         out = np.empty(self.win_length, np.float64)
         assert N.lw_istft_window2(self._h, None) == out.size
-        N.lw_istft_window2(self._h, out.ctypes.data_as(C.c_void_p))
+        N.lw_istft_window2(self._h, _array_ptr(out))
         return out
 
     def last_route(self):
@@ -755,47 +746,26 @@ class InverseSpectrogram:
         fmt = _FMT[samples]
         if fmt not in (N.FMT_F32_PLANAR, N.FMT_F32_INTERLEAVED):
             raise ValueError("the inverse spectrogram writes the f32 formats, not %r" % (samples,))
-        dev = "cuda:%d" % self.device
-        if spec.dtype != torch.float32 or spec.device.type != "cuda" or spec.device.index != self.device or not spec.is_contiguous():
-            raise ValueError("spec must be a contiguous float32 tensor on %s" % dev)
-        if spec.dim() != 4 or spec.shape[2] != 2 * self.bins:
+        _check_tensor(spec, "spec", "[rows][channels][%d lines][frames]" % (2 * self.bins), self.device, (torch.float32,), (4,))
+        if spec.shape[2] != 2 * self.bins:
             raise ValueError("spec must be [rows][channels][%d lines][frames], not %r" % (2 * self.bins, tuple(spec.shape)))
         n_src, ch, _, fcap = spec.shape
-        T = [int(v) for v in (frames.tolist() if hasattr(frames, "tolist") else frames)]
-        if len(T) != n_src or any(v < 0 for v in T):
-            raise ValueError("frames= needs one non-negative entry per row of spec")
+        T = _row_counts(frames, n_src, "frames")
         if lengths is None:
-            lens = [self.out_len(v) for v in T]
+            lens = np.asarray([self.out_len(v) for v in T.tolist()], np.uint64)
         else:
-            lens = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
-            if len(lens) != n_src or any(v < 0 for v in lens):
-                raise ValueError("lengths= needs one non-negative entry per row of spec")
-        rmap = None
-        if rows is not None:
-            rows = [int(v) for v in (rows.tolist() if hasattr(rows, "tolist") else rows)]
-            if len(rows) != n_src or any(not 0 <= v < 1 << 32 for v in rows):
-                raise ValueError("rows= needs one destination row per row of spec")
-            rmap = np.asarray(rows, np.uint32)
+            lens = _row_counts(lengths, n_src, "lengths")
+        rmap, n_dst = _row_map(rows, n_src)
         itl = N.fmt_interleaved(fmt)
         if out is None:
-            n_dst, cap = (max(rows) + 1 if rows else n_src), max(lens, default=0)
-            out = torch.zeros((n_dst, cap, ch) if itl else (n_dst, ch, cap), dtype=torch.float32, device=dev)
-        if out.dtype != torch.float32 or out.device.type != "cuda" or out.device.index != self.device or not out.is_contiguous():
-            raise ValueError("out must be a contiguous float32 tensor on %s" % dev)
-        if out.dim() != 3 or out.shape[1 + itl] != ch:
-            raise ValueError("out must be [rows][%d channels][samples] (interleaved: [rows][samples][channels]), not %r" % (ch, tuple(out.shape)))
-        n_dst, cap = out.shape[0], out.shape[2 - itl]
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device).cuda_stream or None
-        Ta, La = np.asarray(T, np.uint64), np.asarray(lens, np.uint64)
-        rc = N.lw_istft_rows(self._h, ch, C.c_void_p(spec.data_ptr()), n_src, fcap, Ta.ctypes.data_as(C.c_void_p),
-                             None if rmap is None else rmap.ctypes.data_as(C.c_void_p), La.ctypes.data_as(C.c_void_p), fmt,
-                             C.c_void_p(out.data_ptr()), n_dst, cap, stream)
-        if rc in (N.ERR_NULL_ARG, N.ERR_CAPACITY, N.ERR_UNSUPPORTED):
-            raise ValueError("lw_istft_rows refused the call (%d)" % rc)
-        if rc:
-            raise RuntimeError("lw_istft_rows: %d %s" % (rc, N.device_error()))
-        return out, torch.tensor(lens, dtype=torch.int64)
+            cap = max(lens.tolist(), default=0)
+            out = torch.zeros((n_dst, cap, ch) if itl else (n_dst, ch, cap), dtype=torch.float32, device="cuda:%d" % self.device)
+        n_dst, och, cap = _pcm_shape(out, samples, "out", self.device)
+        if och != ch:
+            raise ValueError("out has %d channels, spec %d" % (och, ch))
+        self._call(N.lw_istft_rows, ch, _tensor_ptr(spec), n_src, fcap, _array_ptr(T), _array_ptr(rmap), _array_ptr(lens), fmt,
+                   _tensor_ptr(out), n_dst, cap, _stream_of(stream, self.device))
+        return out, torch.tensor(lens.tolist(), dtype=torch.int64)
 
 
 _FEAT_LOGS = {None: 0, "none": 0, "ln": 1, "log10": 2, "db": 3}      # LW_FEAT_LOG_*
@@ -822,13 +792,14 @@ def _feat_params(log, floor, top, add, mul, scope):
     return _FEAT_LOGS[log], _FEAT_SCOPES[scope], floor, top, add, mul
 
 
-class LogCompress:
+class LogCompress(_Handle):
     """lw_feat: finishes feature rows [rows][C][F][frame capacity] (Spectrogram.run's output) on the GPU (k_feat), by the rule of
     include/lewton_amd.h ("finishing feature rows"), a contract on bits: v = max(x, floor) (a NaN becomes the floor), l = LOG(v)
     in specified double arithmetic (log: None, "ln", "log10", "db"), M = the largest l of the scope ("row": all channels and lines
     of the row; "channel"), y = max(l, M - top) (top=inf: no clamp), z = (y + add) * mul.  The defaults are Whisper's.  Parameter
     errors are ValueError and need no GPU; the object itself lives on cuda:device."""
 
+    _C = "lw_feat"
     WHISPER = dict(log="log10", floor=1e-10, top=8.0, add=4.0, mul=0.25, scope="row")
 
     def __init__(self, log="log10", floor=1e-10, top=8.0, add=4.0, mul=0.25, scope="row", device=0):
@@ -836,27 +807,13 @@ class LogCompress:
         self.log_kind, self.scope, self.device = log, scope, device
         self.floor, self.top, self.add, self.mul = float(floor), float(top), float(add), float(mul)
         _gpu()
-        err = C.c_int(0)
         p = N.FeatParams(kind, sc, floor, top, add, mul)
-        self._h = N.lw_feat_create(device, C.byref(p), C.byref(err))
-        if not self._h:
-            if err.value in (N.ERR_UNSUPPORTED, N.ERR_NULL_ARG):
-                raise ValueError("lw_feat_create refused the parameters")
-            raise RuntimeError("lw_feat_create failed (%d): %s" % (err.value, N.device_error()))
+        self._create(device, C.byref(p))
 
     @classmethod
     def whisper(cls, device=0):
         """log10, floor 1e-10, clamp 8 below the row's maximum, (x + 4) / 4"""
         return cls(device=device, **cls.WHISPER)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            N.lw_feat_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        if N is not None and getattr(N, "lw_feat_destroy", None) is not None:  # not during interpreter shutdown
-            self.close()
 
     def log(self, v):
         """the contract's LOG of one float32 value, evaluated on the host (lw_feat_log)"""
@@ -876,34 +833,16 @@ class LogCompress:
         if out is None:
             out = feat
         for t, what in ((feat, "feat"), (out, "out")):
-            if t.dtype != torch.float32 or t.device.type != "cuda" or t.device.index != self.device or not t.is_contiguous() or t.dim() != 4:
-                raise ValueError("%s must be a contiguous float32 tensor [rows][C][F][frames] on cuda:%d" % (what, self.device))
+            _check_tensor(t, what, "[rows][C][F][frames]", self.device, (torch.float32,), (4,))
         if tuple(out.shape) != tuple(feat.shape):
             raise ValueError("out must have feat's shape %r, not %r" % (tuple(feat.shape), tuple(out.shape)))
         n_rows, ch, F, cap = feat.shape
-        counts = [int(v) for v in (frames.tolist() if hasattr(frames, "tolist") else frames)]
-        if len(counts) != n_rows or any(v < 0 for v in counts):
-            raise ValueError("frames= needs one non-negative entry per row of feat")
-        fill = None
-        if fill_to is not None:
-            fill = fill_to.tolist() if hasattr(fill_to, "tolist") else fill_to
-            fill = [int(fill)] * n_rows if isinstance(fill, (int, np.integer)) else [int(v) for v in fill]
-            if len(fill) != n_rows or any(v < 0 for v in fill):
-                raise ValueError("fill_to= needs one non-negative count, or one per row of feat")
-            fill = np.asarray(fill, np.uint64)
-        counts = np.asarray(counts, np.uint64)
+        counts, fill = _row_counts(frames, n_rows, "frames"), _row_fill(fill_to, n_rows)
         mx = None
         if want_max:
             mx = torch.empty((n_rows,) if self.scope == "row" else (n_rows, ch), dtype=torch.float32, device=feat.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device).cuda_stream or None
-        rc = N.lw_feat_rows(self._h, ch, F, C.c_void_p(feat.data_ptr()), C.c_void_p(out.data_ptr()), n_rows, cap,
-                            counts.ctypes.data_as(C.c_void_p), None if fill is None else fill.ctypes.data_as(C.c_void_p),
-                            None if mx is None else C.c_void_p(mx.data_ptr()), stream)
-        if rc in (N.ERR_NULL_ARG, N.ERR_CAPACITY, N.ERR_UNSUPPORTED):
-            raise ValueError("lw_feat_rows refused the call (%d)" % rc)
-        if rc:
-            raise RuntimeError("lw_feat_rows: %d %s" % (rc, N.device_error()))
+        self._call(N.lw_feat_rows, ch, F, _tensor_ptr(feat), _tensor_ptr(out), n_rows, cap, _array_ptr(counts), _array_ptr(fill),
+                   _tensor_ptr(mx), _stream_of(stream, self.device))
         return (out, mx) if want_max else out
 
 
@@ -930,7 +869,7 @@ def _norm_params(center, scale, eps, target, scope):
     return int(bool(center)), _NORM_SCALES[scale], _NORM_SCOPES[scope], eps, target
 
 
-class Normalize:
+class Normalize(_Handle):
     """lw_norm: normalises rows [rows][C][capacity] (waveforms) or [rows][C][F][capacity] (features) on the GPU (k_norm), by the
     rule of include/lewton_amd.h ("normalising rows"), a contract on bits with a fixed summation order: z = (x - m) * g in double,
     rounded once, with m the scope's mean (center) and g from its standard deviation ("std": 1 / sqrt(var + eps)), its RMS
@@ -938,17 +877,14 @@ class Normalize:
     and lines of a row), "channel" or "line".  Parameter errors are ValueError and need no GPU; the object itself lives on
     cuda:device."""
 
+    _C = "lw_norm"
+
     def __init__(self, center=True, scale="std", eps=1e-7, target=1.0, scope="row", device=0):
         c, kind, sc, eps, target = _norm_params(center, scale, eps, target, scope)
         self.center, self.scale, self.scope, self.eps, self.target, self.device = bool(c), scale, scope, eps, target, device
         _gpu()
-        err = C.c_int(0)
         p = N.NormParams(c, kind, sc, 0, eps, target)
-        self._h = N.lw_norm_create(device, C.byref(p), C.byref(err))
-        if not self._h:
-            if err.value in (N.ERR_UNSUPPORTED, N.ERR_NULL_ARG):
-                raise ValueError("lw_norm_create refused the parameters")
-            raise RuntimeError("lw_norm_create failed (%d): %s" % (err.value, N.device_error()))
+        self._create(device, C.byref(p))
 
     @classmethod
     def wav2vec2(cls, device=0):
@@ -969,15 +905,6 @@ class Normalize:
     def rms(cls, target, device=0):
         """the row's RMS becomes target; nothing is centred"""
         return cls(False, "rms", 0.0, target, "row", device)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            N.lw_norm_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        if N is not None and getattr(N, "lw_norm_destroy", None) is not None:  # not during interpreter shutdown
-            self.close()
 
     def scalars(self, S1, S2, P, N_):
         """step 3 of the contract on the host (lw_norm_scalars): (m, g) of a scope with sums S1, S2, peak P and N_ elements"""
@@ -1000,38 +927,18 @@ class Normalize:
         if out is None:
             out = x
         for t, what in ((x, "x"), (out, "out")):
-            if (t.dtype != torch.float32 or t.device.type != "cuda" or t.device.index != self.device or not t.is_contiguous() or
-                    t.dim() not in (3, 4)):
-                raise ValueError("%s must be a contiguous float32 tensor [rows][C][capacity] or [rows][C][F][capacity] on cuda:%d" % (
-                    what, self.device))
+            _check_tensor(t, what, "[rows][C][capacity] or [rows][C][F][capacity]", self.device, (torch.float32,), (3, 4))
         if tuple(out.shape) != tuple(x.shape):
             raise ValueError("out must have x's shape %r, not %r" % (tuple(x.shape), tuple(out.shape)))
         n_rows, ch, cap = x.shape[0], x.shape[1], x.shape[-1]
         F = x.shape[2] if x.dim() == 4 else 1
-        counts = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
-        if len(counts) != n_rows or any(v < 0 for v in counts):
-            raise ValueError("lengths= needs one non-negative entry per row of x")
-        fill = None
-        if fill_to is not None:
-            fill = fill_to.tolist() if hasattr(fill_to, "tolist") else fill_to
-            fill = [int(fill)] * n_rows if isinstance(fill, (int, np.integer)) else [int(v) for v in fill]
-            if len(fill) != n_rows or any(v < 0 for v in fill):
-                raise ValueError("fill_to= needs one non-negative count, or one per row of x")
-            fill = np.asarray(fill, np.uint64)
-        counts = np.asarray(counts, np.uint64)
+        counts, fill = _row_counts(lengths, n_rows, "lengths"), _row_fill(fill_to, n_rows)
         stats = None
         if want_stats:
             shape = {"row": (n_rows, 2), "channel": (n_rows, ch, 2), "line": (n_rows, ch, F, 2) if x.dim() == 4 else (n_rows, ch, 2)}[self.scope]
             stats = torch.empty(shape, dtype=torch.float64, device=x.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device).cuda_stream or None
-        rc = N.lw_norm_rows(self._h, ch, F, C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), n_rows, cap,
-                            counts.ctypes.data_as(C.c_void_p), None if fill is None else fill.ctypes.data_as(C.c_void_p),
-                            None if stats is None else C.c_void_p(stats.data_ptr()), stream)
-        if rc in (N.ERR_NULL_ARG, N.ERR_CAPACITY, N.ERR_UNSUPPORTED):
-            raise ValueError("lw_norm_rows refused the call (%d)" % rc)
-        if rc:
-            raise RuntimeError("lw_norm_rows: %d %s" % (rc, N.device_error()))
+        self._call(N.lw_norm_rows, ch, F, _tensor_ptr(x), _tensor_ptr(out), n_rows, cap, _array_ptr(counts), _array_ptr(fill),
+                   _tensor_ptr(stats), _stream_of(stream, self.device))
         return (out, stats) if want_stats else out
 
 
@@ -1051,26 +958,7 @@ def _slide_params(cmn_window, min_cmn_window, center, norm_vars):
     return int(cmn_window), int(min_cmn_window), int(bool(center)), int(bool(norm_vars))
 
 
-def _row_counts(v, n_rows, what):
-    """one non-negative count per row as uint64, from a list, an array or a tensor"""
-    counts = [int(c) for c in (v.tolist() if hasattr(v, "tolist") else v)]
-    if len(counts) != n_rows or any(c < 0 for c in counts):
-        raise ValueError("%s= needs one non-negative entry per row" % what)
-    return np.asarray(counts, np.uint64)
-
-
-def _row_fill(fill_to, n_rows):
-    """None, or one non-negative count per row as uint64 from one count for all rows or one per row"""
-    if fill_to is None:
-        return None
-    fill = fill_to.tolist() if hasattr(fill_to, "tolist") else fill_to
-    fill = [int(fill)] * n_rows if isinstance(fill, (int, np.integer)) else [int(v) for v in fill]
-    if len(fill) != n_rows or any(v < 0 for v in fill):
-        raise ValueError("fill_to= needs one non-negative count, or one per row")
-    return np.asarray(fill, np.uint64)
-
-
-class SlidingCMVN:
+class SlidingCMVN(_Handle):
     """lw_slide: Kaldi's apply-cmvn-sliding over feature rows [rows][C][F][capacity] on the GPU (k_slide), by the rule of
     include/lewton_amd.h ("sliding-window normalisation of feature rows"), a contract on bits with a fixed summation order: every
     frame minus the mean of a window of cmn_window frames around it (center) or of the cmn_window + 1 frames up to it, and with
@@ -1078,26 +966,14 @@ class SlidingCMVN:
     defaults; the x-vector recipes use SlidingCMVN(300, 100, center=True).  Parameter errors are ValueError and need no GPU; the
     object itself lives on cuda:device."""
 
+    _C = "lw_slide"
+
     def __init__(self, cmn_window=600, min_cmn_window=100, center=False, norm_vars=False, device=0):
         W, m, c, nv = _slide_params(cmn_window, min_cmn_window, center, norm_vars)
         self.cmn_window, self.min_cmn_window, self.center, self.norm_vars, self.device = W, m, bool(c), bool(nv), device
         _gpu()
-        err = C.c_int(0)
         p = N.SlideParams(W, m, c, nv)
-        self._h = N.lw_slide_create(device, C.byref(p), C.byref(err))
-        if not self._h:
-            if err.value in (N.ERR_UNSUPPORTED, N.ERR_NULL_ARG):
-                raise ValueError("lw_slide_create refused the parameters")
-            raise RuntimeError("lw_slide_create failed (%d): %s" % (err.value, N.device_error()))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            N.lw_slide_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        if N is not None and getattr(N, "lw_slide_destroy", None) is not None:  # not during interpreter shutdown
-            self.close()
+        self._create(device, C.byref(p))
 
     def window(self, t, T):
         """rule 1 on the host (lw_slide_window): (start, end) of the window of frame t of a line of T frames"""
@@ -1130,26 +1006,19 @@ class SlidingCMVN:
         if out is None:
             out = torch.zeros_like(feats)
         for t, what in ((feats, "feats"), (out, "out")):
-            if t.dtype != torch.float32 or t.device.type != "cuda" or t.device.index != self.device or not t.is_contiguous() or t.dim() != 4:
-                raise ValueError("%s must be a contiguous float32 tensor [rows][C][F][capacity] on cuda:%d" % (what, self.device))
+            _check_tensor(t, what, "[rows][C][F][capacity]", self.device, (torch.float32,), (4,))
         if tuple(out.shape) != tuple(feats.shape):
             raise ValueError("out must have feats' shape %r, not %r" % (tuple(feats.shape), tuple(out.shape)))
         if out.data_ptr() == feats.data_ptr() and feats.numel():
             raise ValueError("out must not be feats: the pass has no in-place form")
         n_rows, ch, F, cap = feats.shape
         counts, fill = _row_counts(frames, n_rows, "frames"), _row_fill(fill_to, n_rows)
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device).cuda_stream or None
-        rc = N.lw_slide_rows(self._h, ch, F, C.c_void_p(feats.data_ptr()), C.c_void_p(out.data_ptr()), n_rows, cap,
-                             counts.ctypes.data_as(C.c_void_p), None if fill is None else fill.ctypes.data_as(C.c_void_p), stream)
-        if rc in (N.ERR_NULL_ARG, N.ERR_CAPACITY, N.ERR_UNSUPPORTED):
-            raise ValueError("lw_slide_rows refused the call (%d)" % rc)
-        if rc:
-            raise RuntimeError("lw_slide_rows: %d %s" % (rc, N.device_error()))
+        self._call(N.lw_slide_rows, ch, F, _tensor_ptr(feats), _tensor_ptr(out), n_rows, cap, _array_ptr(counts), _array_ptr(fill),
+                   _stream_of(stream, self.device))
         return out
 
 
-class SelectFrames:
+class SelectFrames(_Handle):
     """lw_select: keeps the frames of feature rows [rows][C][F][capacity] that a mask marks and moves them to the front of every
     line on the GPU (k_select), by the rule of include/lewton_amd.h ("frame decisions and frame selection"): Kaldi's
     select-voiced-frames for any mask -- an energy VAD's, a neural VAD's, a silence trim.  Bit copies; the rest of every line up to
@@ -1158,24 +1027,13 @@ class SelectFrames:
     viewed as [B * C][1][F][cap] is the same memory, and counts.reshape(B * C) are the frames of its rows.  Parameter errors are
     ValueError and need no GPU; the object itself lives on cuda:device."""
 
+    _C = "lw_select"
+
     def __init__(self, device=0):
         if isinstance(device, (bool, np.bool_)) or not isinstance(device, (int, np.integer)) or device < 0:
             raise ValueError("device=%r: a device number" % (device,))
         self.device = int(device)
-        _gpu()
-        err = C.c_int(0)
-        self._h = N.lw_select_create(self.device, C.byref(err))
-        if not self._h:
-            raise RuntimeError("lw_select_create failed (%d): %s" % (err.value, N.device_error()))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            N.lw_select_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        if N is not None and getattr(N, "lw_select_destroy", None) is not None:  # not during interpreter shutdown
-            self.close()
+        self._create(self.device)
 
     @property
     def tile_frames(self):
@@ -1203,27 +1061,18 @@ class SelectFrames:
         if out is None:
             out = torch.zeros_like(feats)
         for t, what in ((feats, "feats"), (out, "out")):
-            if t.dtype != torch.float32 or t.device.type != "cuda" or t.device.index != self.device or not t.is_contiguous() or t.dim() != 4:
-                raise ValueError("%s must be a contiguous float32 tensor [rows][C][F][capacity] on cuda:%d" % (what, self.device))
+            _check_tensor(t, what, "[rows][C][F][capacity]", self.device, (torch.float32,), (4,))
         if tuple(out.shape) != tuple(feats.shape):
             raise ValueError("out must have feats' shape %r, not %r" % (tuple(feats.shape), tuple(out.shape)))
         if out.data_ptr() == feats.data_ptr() and feats.numel():
             raise ValueError("out must not be feats: the pass has no in-place form")
         n_rows, ch, F, cap = feats.shape
-        if (mask.dtype not in (torch.bool, torch.uint8) or mask.device != feats.device or not mask.is_contiguous() or
-                tuple(mask.shape) != (n_rows, ch, cap)):
-            raise ValueError("mask must be a contiguous bool or uint8 tensor %r on feats' device" % ((n_rows, ch, cap),))
+        _check_tensor(mask, "mask", "[rows][C][capacity] = %r" % ((n_rows, ch, cap),), self.device, (torch.bool, torch.uint8),
+                      shape=(n_rows, ch, cap))
         counts, fill = _row_counts(frames, n_rows, "frames"), _row_fill(fill_to, n_rows)
         kept = torch.empty((n_rows, ch), dtype=torch.int64, device=feats.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device).cuda_stream or None
-        rc = N.lw_select_rows(self._h, ch, F, C.c_void_p(feats.data_ptr()), C.c_void_p(mask.data_ptr()), C.c_void_p(out.data_ptr()),
-                              C.c_void_p(kept.data_ptr()), n_rows, cap, counts.ctypes.data_as(C.c_void_p),
-                              None if fill is None else fill.ctypes.data_as(C.c_void_p), stream)
-        if rc in (N.ERR_NULL_ARG, N.ERR_CAPACITY, N.ERR_UNSUPPORTED):
-            raise ValueError("lw_select_rows refused the call (%d)" % rc)
-        if rc:
-            raise RuntimeError("lw_select_rows: %d %s" % (rc, N.device_error()))
+        self._call(N.lw_select_rows, ch, F, _tensor_ptr(feats), _tensor_ptr(mask), _tensor_ptr(out), _tensor_ptr(kept), n_rows, cap,
+                   _array_ptr(counts), _array_ptr(fill), _stream_of(stream, self.device))
         return out, kept
 
 
@@ -1256,7 +1105,7 @@ def _vad_params(energy_threshold, energy_mean_scale, frames_context, proportion_
     return thr, scale, int(frames_context), prop, int(line), int(device)
 
 
-class EnergyVad:
+class EnergyVad(_Handle):
     """lw_vad: Kaldi's compute-vad-energy over feature rows [rows][C][F][capacity] on the GPU (k_vad), by the rule of
     include/lewton_amd.h ("energy voice-activity decisions of feature rows"), a contract on bits: a frame's raw decision is its log
     energy (feature line `line`) above energy_threshold + energy_mean_scale * the line's mean, and a frame is voiced when at least
@@ -1265,27 +1114,15 @@ class EnergyVad:
     Run it on the RAW features, before SlidingCMVN; the mask goes straight into SelectFrames.run, with no synchronisation in
     between.  Parameter errors are ValueError and need no GPU; the object itself lives on cuda:device."""
 
+    _C = "lw_vad"
+
     def __init__(self, energy_threshold=5.0, energy_mean_scale=0.5, frames_context=0, proportion_threshold=0.6, line=0, device=0):
         thr, scale, ctx, prop, line, device = _vad_params(energy_threshold, energy_mean_scale, frames_context, proportion_threshold, line, device)
         self.energy_threshold, self.energy_mean_scale, self.frames_context, self.proportion_threshold = float(thr), float(scale), ctx, float(prop)
         self.line, self.device = line, device
         _gpu()
-        err = C.c_int(0)
         p = N.VadParams(thr, scale, ctx, prop, line, 0)
-        self._h = N.lw_vad_create(device, C.byref(p), C.byref(err))
-        if not self._h:
-            if err.value in (N.ERR_UNSUPPORTED, N.ERR_NULL_ARG):
-                raise ValueError("lw_vad_create refused the parameters")
-            raise RuntimeError("lw_vad_create failed (%d): %s" % (err.value, N.device_error()))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            N.lw_vad_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        if N is not None and getattr(N, "lw_vad_destroy", None) is not None:  # not during interpreter shutdown
-            self.close()
+        self._create(device, C.byref(p))
 
     def threshold(self, S, T):
         """rule 1 behind the sum, on the host (lw_vad_threshold): the float32 threshold of a line of T frames whose sum is S"""
@@ -1329,24 +1166,16 @@ class EnergyVad:
         mask as a torch.bool [rows][C][capacity] view of out's bytes, and with want_threshold (mask, thr), thr a float32 [rows][C]
         device tensor of the thresholds."""
         torch = _gpu()
-        if feats.dtype != torch.float32 or feats.device.type != "cuda" or feats.device.index != self.device or not feats.is_contiguous() or feats.dim() != 4:
-            raise ValueError("feats must be a contiguous float32 tensor [rows][C][F][capacity] on cuda:%d" % self.device)
+        _check_tensor(feats, "feats", "[rows][C][F][capacity]", self.device, (torch.float32,), (4,))
         n_rows, ch, F, cap = feats.shape
         if out is None:
             out = torch.zeros((n_rows, ch, cap), dtype=torch.uint8, device=feats.device)
-        if (out.dtype not in (torch.bool, torch.uint8) or out.device != feats.device or not out.is_contiguous() or
-                tuple(out.shape) != (n_rows, ch, cap)):
-            raise ValueError("out must be a contiguous bool or uint8 tensor %r on feats' device" % ((n_rows, ch, cap),))
+        _check_tensor(out, "out", "[rows][C][capacity] = %r" % ((n_rows, ch, cap),), self.device, (torch.bool, torch.uint8),
+                      shape=(n_rows, ch, cap))
         counts, fill = _row_counts(frames, n_rows, "frames"), _row_fill(fill_to, n_rows)
         thr = torch.empty((n_rows, ch), dtype=torch.float32, device=feats.device) if want_threshold else None
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device).cuda_stream or None
-        rc = N.lw_vad_rows(self._h, ch, F, C.c_void_p(feats.data_ptr()), C.c_void_p(out.data_ptr()), None if thr is None else C.c_void_p(thr.data_ptr()),
-                           n_rows, cap, counts.ctypes.data_as(C.c_void_p), None if fill is None else fill.ctypes.data_as(C.c_void_p), stream)
-        if rc in (N.ERR_NULL_ARG, N.ERR_CAPACITY, N.ERR_UNSUPPORTED):
-            raise ValueError("lw_vad_rows refused the call (%d)" % rc)
-        if rc:
-            raise RuntimeError("lw_vad_rows: %d %s" % (rc, N.device_error()))
+        self._call(N.lw_vad_rows, ch, F, _tensor_ptr(feats), _tensor_ptr(out), _tensor_ptr(thr), n_rows, cap, _array_ptr(counts),
+                   _array_ptr(fill), _stream_of(stream, self.device))
         mask = out if out.dtype == torch.bool else out.view(torch.bool)
         return (mask, thr) if want_threshold else mask
 
@@ -1406,7 +1235,7 @@ def _cep_params(n_in, matrix, delta_order, delta_width):
     return int(n_in), n_out, matrix, int(delta_order), int(delta_width) if delta_order else 0
 
 
-class Cepstrum:
+class Cepstrum(_Handle):
     """lw_cep: feature rows [rows][C][n_in][frame capacity] -> [rows][C][n_out * (1 + delta_order)][frame capacity] on the GPU
     (k_cep), by the rule of include/lewton_amd.h ("cepstra and deltas of feature rows"), a contract on bits: static line q is the
     fmaf chain over the input lines with row q of matrix ([n_out][n_in]; None: the identity, a bit copy), the next n_out lines
@@ -1414,17 +1243,12 @@ class Cepstrum:
     Kaldi order; what torchaudio's compute_deltas applied twice gives).  Parameter errors are ValueError and need no GPU; the
     object itself lives on cuda:device."""
 
+    _C = "lw_cep"
+
     def __init__(self, n_in, matrix=None, delta_order=0, delta_width=2, device=0):
         self.n_in, self.n_out, self._matrix, self.delta_order, self.delta_width = _cep_params(n_in, matrix, delta_order, delta_width)
         self.device = device
-        _gpu()
-        err = C.c_int(0)
-        self._h = N.lw_cep_create(device, self.n_in, self.n_out, None if self._matrix is None else self._matrix.ctypes.data_as(C.c_void_p),
-                                  self.delta_order, self.delta_width, C.byref(err))
-        if not self._h:
-            if err.value in (N.ERR_UNSUPPORTED, N.ERR_NULL_ARG):
-                raise ValueError("lw_cep_create refused the parameters")
-            raise RuntimeError("lw_cep_create failed (%d): %s" % (err.value, N.device_error()))
+        self._create(device, self.n_in, self.n_out, _array_ptr(self._matrix), self.delta_order, self.delta_width)
         assert self.features == self.n_out * (1 + self.delta_order)
 
     @classmethod
@@ -1436,15 +1260,6 @@ class Cepstrum:
     def deltas(cls, n_in, order=2, width=2, device=0):
         """the lines themselves, bit for bit, then their deltas ("fbank + deltas")"""
         return cls(n_in, None, order, width, device)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            N.lw_cep_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        if N is not None and getattr(N, "lw_cep_destroy", None) is not None:  # not during interpreter shutdown
-            self.close()
 
     @property
     def features(self):
@@ -1463,13 +1278,13 @@ class Cepstrum:
             return None
         out = np.empty((self.n_out, self.n_in), np.float32)
         assert n == out.size
-        N.lw_cep_matrix(self._h, out.ctypes.data_as(C.c_void_p))
+        N.lw_cep_matrix(self._h, _array_ptr(out))
         return out
 
     def delta_weights(self):
         """w_1 .. w_N float32 (empty without deltas)"""
         out = np.empty(int(N.lw_cep_delta_weights(self._h, None)), np.float32)
-        N.lw_cep_delta_weights(self._h, out.ctypes.data_as(C.c_void_p))
+        N.lw_cep_delta_weights(self._h, _array_ptr(out))
         return out
 
     def last_launches(self):
@@ -1483,35 +1298,17 @@ class Cepstrum:
         Nothing else of out is written.  stream: a hipStream_t value; None = torch's current stream on the object's device.
         Asynchronous; returns out."""
         torch = _gpu()
-        if (feat.dtype != torch.float32 or feat.device.type != "cuda" or feat.device.index != self.device or not feat.is_contiguous() or
-                feat.dim() != 4 or feat.shape[2] != self.n_in):
-            raise ValueError("feat must be a contiguous float32 tensor [rows][C][%d][frames] on cuda:%d" % (self.n_in, self.device))
+        _check_tensor(feat, "feat", "[rows][C][%d][frames]" % self.n_in, self.device, (torch.float32,), (4,))
+        if feat.shape[2] != self.n_in:
+            raise ValueError("feat must be [rows][C][%d][frames], not %r" % (self.n_in, tuple(feat.shape)))
         n_rows, ch, _, cap = feat.shape
         if out is None:
             out = torch.zeros((n_rows, ch, self.features, cap), dtype=torch.float32, device=feat.device)
-        if out.dtype != torch.float32 or out.device.type != "cuda" or out.device.index != self.device or not out.is_contiguous() or out.dim() != 4:
-            raise ValueError("out must be a contiguous float32 tensor [rows][C][features][frames] on cuda:%d" % self.device)
-        if tuple(out.shape) != (n_rows, ch, self.features, cap):
-            raise ValueError("out must be %r, not %r" % ((n_rows, ch, self.features, cap), tuple(out.shape)))
-        counts = [int(v) for v in (frames.tolist() if hasattr(frames, "tolist") else frames)]
-        if len(counts) != n_rows or any(v < 0 for v in counts):
-            raise ValueError("frames= needs one non-negative entry per row of feat")
-        fill = None
-        if fill_to is not None:
-            fill = fill_to.tolist() if hasattr(fill_to, "tolist") else fill_to
-            fill = [int(fill)] * n_rows if isinstance(fill, (int, np.integer)) else [int(v) for v in fill]
-            if len(fill) != n_rows or any(v < 0 for v in fill):
-                raise ValueError("fill_to= needs one non-negative count, or one per row of feat")
-            fill = np.asarray(fill, np.uint64)
-        counts = np.asarray(counts, np.uint64)
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device).cuda_stream or None
-        rc = N.lw_cep_rows(self._h, ch, C.c_void_p(feat.data_ptr()), C.c_void_p(out.data_ptr()), n_rows, cap,
-                           counts.ctypes.data_as(C.c_void_p), None if fill is None else fill.ctypes.data_as(C.c_void_p), stream)
-        if rc in (N.ERR_NULL_ARG, N.ERR_CAPACITY, N.ERR_UNSUPPORTED):
-            raise ValueError("lw_cep_rows refused the call (%d)" % rc)
-        if rc:
-            raise RuntimeError("lw_cep_rows: %d %s" % (rc, N.device_error()))
+        shape = (n_rows, ch, self.features, cap)
+        _check_tensor(out, "out", "[rows][C][features][frames] = %r" % (shape,), self.device, (torch.float32,), shape=shape)
+        counts, fill = _row_counts(frames, n_rows, "frames"), _row_fill(fill_to, n_rows)
+        self._call(N.lw_cep_rows, ch, _tensor_ptr(feat), _tensor_ptr(out), n_rows, cap, _array_ptr(counts), _array_ptr(fill),
+                   _stream_of(stream, self.device))
         return out
 
 
@@ -1588,15 +1385,10 @@ class KaldiFbank:
         torch = _gpu()
         if out is None:
             n_src, ch, _ = self.spec.check_tensor(pcm, samples, "pcm")
-            lens = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
-            if len(lens) != n_src or any(v < 0 for v in lens):
-                raise ValueError("lengths= needs one non-negative entry per row of pcm")
-            fill = fill_to.tolist() if hasattr(fill_to, "tolist") else fill_to
-            fill = [] if fill is None else [int(fill)] if isinstance(fill, (int, np.integer)) else [int(v) for v in fill]
-            cap = max([self.spec.frames(v) for v in lens] + fill, default=0)
+            lens, fill = _row_counts(lengths, n_src, "lengths"), _row_fill(fill_to, n_src)
+            cap = max([self.spec.frames(v) for v in lens.tolist()] + ([] if fill is None else fill.tolist()), default=0)
             out = torch.zeros((n_src, ch, self.features, cap), dtype=torch.float32, device="cuda:%d" % self.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device).cuda_stream or None
+        stream = _stream_of(stream, self.device)
         out, frames = self.spec.run(pcm, lengths, out=out, samples=samples, stream=stream)
         self.log.run(out, frames, fill_to=fill_to, stream=stream)
         if self.use_energy and self.energy_floor > 0.0 and out.shape[3]:
@@ -1648,7 +1440,7 @@ def _pack_params(n_in, left, right, stride, edge, dtype, shift, scale, pad):
     return int(n_in), int(left), int(right), int(stride), edge, dtype, vecs[0], vecs[1], pad
 
 
-class FramePack:
+class FramePack(_Handle):
     """lw_pack: feature rows [rows][C][n_in][frame capacity] (float32, the chain's layout) -> [rows][C][out capacity][W * n_in]
     frames of float32, bfloat16 or float16 on the GPU (k_pack), by the rule of include/lewton_amd.h ("frame-major model input"), a
     contract on bits: W = left + right + 1 frames of context per output frame, every stride-th frame, the edge frames replicated
@@ -1657,19 +1449,15 @@ class FramePack:
     rounding to dtype, pad beyond the frames and the padding mask.  Parameter errors are ValueError and need no GPU; the object
     itself lives on cuda:device."""
 
+    _C = "lw_pack"
+
     def __init__(self, n_in, left=0, right=0, stride=1, edge="replicate", dtype="f32", shift=None, scale=None, pad=0.0, device=0):
         (self.n_in, self.left, self.right, self.stride, self.edge, self.dtype, self._shift, self._scale,
          self.pad) = _pack_params(n_in, left, right, stride, edge, dtype, shift, scale, pad)
         self.device = device
         _gpu()
-        err = C.c_int(0)
         p = N.PackParams(self.n_in, self.left, self.right, self.stride, _PACK_EDGES[edge], _PACK_DTYPES[dtype], self.pad, 0)
-        self._h = N.lw_pack_create(device, C.byref(p), None if self._shift is None else self._shift.ctypes.data_as(C.c_void_p),
-                                   None if self._scale is None else self._scale.ctypes.data_as(C.c_void_p), C.byref(err))
-        if not self._h:
-            if err.value in (N.ERR_UNSUPPORTED, N.ERR_NULL_ARG):
-                raise ValueError("lw_pack_create refused the parameters")
-            raise RuntimeError("lw_pack_create failed (%d): %s" % (err.value, N.device_error()))
+        self._create(device, C.byref(p), _array_ptr(self._shift), _array_ptr(self._scale))
         assert self.width == (self.left + self.right + 1) * self.n_in
 
     @classmethod
@@ -1702,15 +1490,6 @@ class FramePack:
             raise ValueError("m=%r: a positive integer" % (m,))
         return cls(n_in, (m - 1) // 2, m - 1 - (m - 1) // 2, n, **kw)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            N.lw_pack_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        if N is not None and getattr(N, "lw_pack_destroy", None) is not None:  # not during interpreter shutdown
-            self.close()
-
     @property
     def width(self):
         """elements per output frame: D = W * n_in"""
@@ -1742,26 +1521,17 @@ class FramePack:
         of it written.  Nothing else of out is written either.  stream: a hipStream_t value; None = torch's current stream on the object's
         device.  Asynchronous; returns (out, out_frames) or (out, out_frames, mask), out_frames a numpy uint64 array."""
         torch = _gpu()
-        if (feat.dtype != torch.float32 or feat.device.type != "cuda" or feat.device.index != self.device or not feat.is_contiguous() or
-                feat.dim() != 4 or feat.shape[2] != self.n_in):
-            raise ValueError("feat must be a contiguous float32 tensor [rows][C][%d][frames] on cuda:%d" % (self.n_in, self.device))
+        _check_tensor(feat, "feat", "[rows][C][%d][frames]" % self.n_in, self.device, (torch.float32,), (4,))
+        if feat.shape[2] != self.n_in:
+            raise ValueError("feat must be [rows][C][%d][frames], not %r" % (self.n_in, tuple(feat.shape)))
         n_rows, ch, _, cap = feat.shape
-        counts = [int(v) for v in (frames.tolist() if hasattr(frames, "tolist") else frames)]
-        if len(counts) != n_rows or any(v < 0 for v in counts):
-            raise ValueError("frames= needs one non-negative entry per row of feat")
-        fill = None
-        if fill_to is not None:
-            fill = fill_to.tolist() if hasattr(fill_to, "tolist") else fill_to
-            fill = [int(fill)] * n_rows if isinstance(fill, (int, np.integer)) else [int(v) for v in fill]
-            if len(fill) != n_rows or any(v < 0 for v in fill):
-                raise ValueError("fill_to= needs one non-negative count, or one per row of feat")
-        out_frames = np.asarray([self.frames(v) for v in counts], np.uint64)
+        counts, fill = _row_counts(frames, n_rows, "frames"), _row_fill(fill_to, n_rows)
+        out_frames = np.asarray([self.frames(v) for v in counts.tolist()], np.uint64)
         tdtype = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}[self.dtype]
         if out is None:
-            out_cap = max(out_frames.tolist() + (fill or []), default=0)
+            out_cap = max(out_frames.tolist() + ([] if fill is None else fill.tolist()), default=0)
             out = torch.zeros((n_rows, ch, out_cap, self.width), dtype=tdtype, device=feat.device)
-        if out.dtype != tdtype or out.device.type != "cuda" or out.device.index != self.device or not out.is_contiguous() or out.dim() != 4:
-            raise ValueError("out must be a contiguous %s tensor [rows][C][frames][width] on cuda:%d" % (tdtype, self.device))
+        _check_tensor(out, "out", "[rows][C][frames][width]", self.device, (tdtype,), (4,))
         if tuple(out.shape[:2]) != (n_rows, ch) or out.shape[3] != self.width:
             raise ValueError("out must be (%d, %d, frames, %d), not %r" % (n_rows, ch, self.width, tuple(out.shape)))
         out_cap = out.shape[2]
@@ -1770,19 +1540,10 @@ class FramePack:
             mask = torch.zeros((n_rows, out_cap), dtype=torch.uint8, device=feat.device)
         elif want_mask is not False and want_mask is not None:
             mask = want_mask
-            if (mask.dtype != torch.uint8 or mask.device != out.device or not mask.is_contiguous() or tuple(mask.shape) != (n_rows, out_cap)):
-                raise ValueError("want_mask= must be True or a contiguous uint8 tensor (%d, %d) on cuda:%d" % (n_rows, out_cap, self.device))
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device).cuda_stream or None
-        counts = np.asarray(counts, np.uint64)
-        fill = None if fill is None else np.asarray(fill, np.uint64)
-        rc = N.lw_pack_rows(self._h, ch, C.c_void_p(feat.data_ptr()), C.c_void_p(out.data_ptr()), n_rows, cap, out_cap,
-                            counts.ctypes.data_as(C.c_void_p), None if fill is None else fill.ctypes.data_as(C.c_void_p),
-                            None if mask is None else C.c_void_p(mask.data_ptr()), stream)
-        if rc in (N.ERR_NULL_ARG, N.ERR_CAPACITY, N.ERR_UNSUPPORTED):
-            raise ValueError("lw_pack_rows refused the call (%d)" % rc)
-        if rc:
-            raise RuntimeError("lw_pack_rows: %d %s" % (rc, N.device_error()))
+            _check_tensor(mask, "want_mask=", "[rows][out capacity] = %r (or True)" % ((n_rows, out_cap),), self.device, (torch.uint8,),
+                          shape=(n_rows, out_cap))
+        self._call(N.lw_pack_rows, ch, _tensor_ptr(feat), _tensor_ptr(out), n_rows, cap, out_cap, _array_ptr(counts), _array_ptr(fill),
+                   _tensor_ptr(mask), _stream_of(stream, self.device))
         return (out, out_frames) if mask is None else (out, out_frames, mask)
 
 
@@ -1932,7 +1693,7 @@ def _decode_group(dec, streams, samples, max_packets, run, entropy_on_device, sk
                     if packet_keep[s] and t in packet_keep[s]:
                         m[i] = min(m[i], packet_keep[s][t])
             places = plan_places(st_idx, m, decoded, skip_a, keep_a, row_a)
-            bt.upload(torch.cuda.current_stream(dec.device).cuda_stream or None)
+            bt.upload(_stream_of(None, dec.device))
             rows.synth(bt, places, pcm, mix=mix)
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream(dec.device))

@@ -342,6 +342,43 @@ def test_refusals_on_the_gpu_write_nothing():
     rows.close()
 
 
+def _smallest_rows(Rows):
+    audio, ident, st = _product(SETUPS["mono_small"]())
+    return Rows(audio.decoder_for(ident, st), 1, "i16")
+
+
+LIFECYCLE = {"Rows": _smallest_rows, "Resampler": lambda R: R(2, 1), "Spectrogram": lambda R: R(16, 8), "InverseSpectrogram": lambda R: R(16, 8),
+             "LogCompress": lambda R: R(), "Normalize": lambda R: R(), "SlidingCMVN": lambda R: R(2, 1), "SelectFrames": lambda R: R(),
+             "EnergyVad": lambda R: R(), "Cepstrum": lambda R: R(4), "FramePack": lambda R: R(4), "KaldiFbank": lambda R: R()}
+
+
+@pytest.mark.parametrize("name", sorted(LIFECYCLE))
+def test_handle_lifecycle(name):
+    """what the classes over a handle share, with the smallest legal arguments and no launch: a handle after construction, -1
+    launches before any call where the C API counts them, close() twice, then the finaliser; nothing raises"""
+    import gc
+    import sys
+    from lewton_amd import rows as R
+    unraisable, hook = [], sys.unraisablehook
+    sys.unraisablehook = unraisable.append                                     # (where an exception in __del__ ends up)
+    try:
+        obj = LIFECYCLE[name](getattr(R, name))
+        parts = [p for p in (obj.spec, obj.log, obj.norm) if p is not None] if name == "KaldiFbank" else [obj]
+        assert parts and all(p._h for p in parts)
+        for p in parts:
+            if hasattr(p, "last_launches"):
+                assert p.last_launches() == -1
+        obj.close()
+        assert all(p._h is None for p in parts)
+        obj.close()
+        assert all(p._h is None for p in parts)
+        del obj, parts, p
+        gc.collect()
+    finally:
+        sys.unraisablehook = hook
+    assert not unraisable, [repr(u.exc_value) for u in unraisable]
+
+
 def test_size_256_streams_of_64_packets():
     """[256, 2, 65 536] f32 planar from 4 batches of 4096 packets, every row against the oracle"""
     import torch

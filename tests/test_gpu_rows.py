@@ -15,7 +15,8 @@ pytestmark = pytest.mark.gpu
 CASES = "rows_gpu_cases.py"
 GROUPS = ["test_rows_equal_packet_major_and_oracle", "test_rows_single_launch_patterns", "test_rows_device_entropy",
           "test_rows_damaged_packets", "test_alignment_cases", "test_back_to_back_on_a_side_stream",
-          "test_same_call_twice_is_idempotent", "test_refusals_on_the_gpu_write_nothing", "test_size_256_streams_of_64_packets",
+          "test_same_call_twice_is_idempotent", "test_refusals_on_the_gpu_write_nothing", "test_handle_lifecycle",
+          "test_size_256_streams_of_64_packets",
           "test_destination_beyond_2_to_the_32_elements", "test_decode_streams", "test_decode_ogg_files_golden_three_times",
           "test_decode_ogg_files_two_setups", "test_decode_ogg_files_refuses_chained_and_mixed"]
 

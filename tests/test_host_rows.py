@@ -284,6 +284,37 @@ def test_ogg_bookkeeping_matches_the_oracle_reader():
         assert set(keeps) <= {len(packets) - 1}
 
 
+REFUSED = {"Resampler": dict(in_rate=2, out_rate=1, window="none"), "Spectrogram": dict(n_fft=1), "InverseSpectrogram": dict(n_fft=16, hop=17),
+           "LogCompress": dict(log="log2"), "Normalize": dict(scope="frame"), "SlidingCMVN": dict(cmn_window=0), "SelectFrames": dict(device=-1),
+           "EnergyVad": dict(line=-1), "Cepstrum": dict(n_in=0), "FramePack": dict(n_in=0), "KaldiFbank": dict(dither=1.0)}
+
+
+@pytest.mark.parametrize("name", ["Rows"] + sorted(REFUSED))
+def test_python_finaliser_after_a_refused_constructor(name):
+    """an object whose constructor raised in parameter validation has no handle, and its finaliser must not raise (no GPU
+    needed).  Rows validates nothing before it creates its handle: its object is one whose __init__ never ran"""
+    import gc
+    import sys
+    from lewton_amd import rows as R
+    cls = getattr(R, name)
+    unraisable, hook = [], sys.unraisablehook
+    sys.unraisablehook = unraisable.append                                      # (where an exception in __del__ ends up)
+    try:
+        obj = cls.__new__(cls)
+        if name != "Rows":
+            with pytest.raises(ValueError):
+                obj.__init__(**REFUSED[name])                                   # this object stays, for close() below
+            with pytest.raises(ValueError):
+                cls(**REFUSED[name])                                            # the usual way: finalised as the exception goes
+        assert getattr(obj, "_h", None) is None
+        obj.close()
+        del obj
+        gc.collect()
+    finally:
+        sys.unraisablehook = hook
+    assert not unraisable, [repr(u.exc_value) for u in unraisable]
+
+
 def test_decode_ogg_files_refusals_need_no_gpu():
     from lewton_amd.rows import decode_ogg_files
     from lewton_amd import ogg
