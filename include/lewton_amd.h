@@ -1003,6 +1003,96 @@ uint32_t lw_select_tile_frames(const lw_select *se);
 int lw_select_set_tile_frames(lw_select *se, uint32_t tile);
 int lw_select_last_launches(const lw_select *se);
 
+/* ---- segments of a frame mask -------------------------------------------------------------------------------------------------
+ * Stretches of speech from a frame mask on the GPU, as a pass of its own (k_segment_count, k_segment): the mask is smoothed and
+ * turned into (start, end) pairs in the order of pyannote's Binarize -- pad, merge across short gaps, drop short regions; a
+ * Kaldi-style hangover is pad_offset alone.  d_mask is uint8 [row][ch][frame_capacity], exactly what lw_vad_rows writes and
+ * lw_select_rows reads; any non-zero byte is "set".  Row i has T = n_frames[i] frames; nothing at or beyond T is read.  An object
+ * is made from four counts of frames, each at most LW_SEG_MAX_SPAN (10 s at a 10 ms shift).  With m[t] = (mask[t] != 0) on [0, T),
+ * for each row and channel, pointwise (nothing outside [0, T) is ever set):
+ *   1. pad   P[t] = 1 iff some u in [0, T) has m[u] and t - pad_offset <= u <= t + pad_onset;
+ *   2. fill  C[t] = P[t], or there are a < t < b with P[a], P[b] and b - a - 1 < min_off: a gap of fewer than min_off frames
+ *            BETWEEN two set frames is filled; a gap that touches either end of the line is not;
+ *   3. drop  O[t] = C[t] and the maximal run of C that holds t has at least min_on frames; runs at the line's ends are not exempt;
+ *   4. the segments are the maximal runs of O in ascending order, [a_0, b_0) < .. < [a_(K-1), b_(K-1)).
+ * With all four counts 0 the segments are the runs of the raw mask.  Worked examples (x = set, . = unset; tests/test_segment_model.py
+ * pins them):
+ *   min_off = 3:            x..x -> xxxx (a gap of min_off - 1)      x...x -> x...x (a gap of min_off)     x..  -> x.. (an end's gap stays)
+ *   min_on = 3:             .xx. -> .... (a run of min_on - 1)       .xxx. -> .xxx.
+ *   pad_onset = 2, pad_offset = 1, T = 6:   .....x -> ...xxx   x..... -> xx....   (clamped at 0 and at T)
+ *   pad_onset = pad_offset = 1:             .x..x. -> xxxxxx  (the pads meet: one segment)
+ *   T = 0: K = 0.  T = 1: x -> one segment [0, 1), unless min_on > 1.  xxxx: [0, T).  ....: K = 0.  x.x.x: K = ceil(T / 2).
+ * O[t] depends on m only within H = max(pad_onset, pad_offset) + min_off + min_on <= 3 * LW_SEG_MAX_SPAN frames of t: that bound
+ * is what lets a workgroup recompute the rule for its tile from the tile and a halo, and it is the reason for the limit.
+ *
+ * Outputs, each may be NULL and is then not computed:
+ *   d_spans   uint64 [row][ch][seg_capacity][2] receives (a_k, b_k) for k < min(K, seg_capacity); entries at or beyond K are not written;
+ *   d_counts  uint64 [row][ch] receives the true K even when K > seg_capacity (how the caller sees the overflow), rows with T == 0 included;
+ *   d_smooth  uint8 [row][ch][frame_capacity] receives O[t] as a 0 / 1 byte for t < T and 0 on [T, max(T, fill_to[row])); every byte
+ *             of that span is written once, nothing else is: lw_select_rows with a hangover.
+ * lw_segment_rows: n_frames and fill_to (may be NULL: nothing is filled) are HOST arrays, copied during the call.  Asynchronous on
+ * hip_stream; calls on one object may be queued back to back.  TWO kernel launches per 65535 rows: a workgroup of 256 lanes takes a
+ * tile of lw_segment_tile_frames frames (1024), loads it and H + 1 frames either side as ballot words into LDS and recomputes P, C
+ * and O there; the first launch counts the segment starts of every tile into a list the object owns, in the second every
+ * workgroup adds up the list in front of its tile in 64 bits, ranks its own starts and ends by popcounts (the ends in front of a
+ * tile are the starts in front of it, minus one if a run crosses the tile's start) and stores spans, smoothed bytes (four at a 4-byte
+ * boundary of the address as one dword, byte by byte at a cut) and, for tile 0, the count.  The count launch is left out when no
+ * row has a frame or neither spans nor counts are wanted; with nothing to write there is no launch, and d_counts is zeroed by a
+ * memset on the stream.  No atomics, no workgroup waits on another.  A workgroup needs 6176 bytes of LDS.
+ * lw_segment_set_tile_frames: a test's handle on the seams, a multiple of 256 in 256 .. 2048 (at 256 the halo covers twelve tiles
+ * either side).  lw_segment_last_launches: the kernels the last accepted call queued, -1 = no call yet.
+ * Refusals, decided on the host before anything is queued:
+ *   LW_ERR_NULL_ARG     sg or p NULL, n_frames NULL with rows, d_mask NULL with frames to read
+ *   LW_ERR_UNSUPPORTED  (create) a count above LW_SEG_MAX_SPAN, reserved != 0; (set_tile_frames) a tile that is no multiple of 256 in
+ *                       256 .. 2048
+ *   LW_ERR_DEVICE       (create) no such device, or one whose workgroups have less LDS than the kernel needs (the device is asked)
+ *   LW_ERR_CAPACITY     n_frames[i] or fill_to[i] > frame_capacity, ch == 0 or > 255, seg_capacity == 0 with d_spans given, a buffer
+ *                       that 64 bits of bytes cannot address, more than 2^24 - 1 workgroups (tiles) in a channel */
+#define LW_SEG_MAX_SPAN 1024
+typedef struct lw_segment lw_segment;
+typedef struct {
+	uint32_t pad_onset;  /* frames a segment starts earlier */
+	uint32_t pad_offset; /* frames a segment ends later: the hangover */
+	uint32_t min_off;    /* gaps of fewer frames between two set frames are filled */
+	uint32_t min_on;     /* runs of fewer frames are dropped */
+	uint32_t reserved;   /* 0 */
+} lw_segment_params;
+lw_segment *lw_segment_create(int device, const lw_segment_params *p, int *err);
+void lw_segment_destroy(lw_segment *sg);
+int lw_segment_rows(lw_segment *sg, uint32_t ch, const uint8_t *d_mask, uint64_t *d_spans, uint64_t *d_counts, uint8_t *d_smooth, size_t n_rows,
+		size_t frame_capacity, size_t seg_capacity, const uint64_t *n_frames, const uint64_t *fill_to, void *hip_stream);
+uint32_t lw_segment_tile_frames(const lw_segment *sg);
+int lw_segment_set_tile_frames(lw_segment *sg, uint32_t tile);
+int lw_segment_last_launches(const lw_segment *sg);
+
+/* ---- cutting rows into segment rows -------------------------------------------------------------------------------------------
+ * One output row per segment on the GPU, as a pass of its own (k_cut).  Source and destination are [row][ch][F][capacity] and
+ * [n_out][ch][F][out_capacity], elements of elem_bytes in {2, 4}: i16 PCM, f32 PCM or features; a waveform is F = 1.  jobs is a HOST
+ * array of n_out triples (row, start, end) in uint64, copied during the call, as are n_frames (one per source row, for the check)
+ * and fill_to (one per job; may be NULL: nothing is filled).  For job i with len = end - start, every channel c and line f:
+ *   dst[i][c][f][j] is a BIT COPY of src[row][c][f][start + j] for j < len (NaN payloads are kept);
+ *   positions [len, max(len, fill_to[i])) receive zero bits;
+ * nothing else of d_dst is written, nothing of d_src outside [start, end) of the job's lines is read.  Jobs may overlap in the
+ * source and may name a row any number of times; overlap of the buffers is the caller's error.  Both buffers are aligned to
+ * elem_bytes.  Asynchronous on hip_stream; calls on one object may be queued back to back.  ONE kernel launch per 65535 jobs: a
+ * workgroup takes 16384 destination bytes of one line; the destination leaves in aligned 16-byte stores wherever the line's
+ * address allows, the source is read by 16-byte loads at the alignment its start gives it; all addresses in 64 bits.
+ * lw_cut_last_launches: the kernels the last accepted call queued, -1 = no call yet.
+ * Refusals, decided on the host before anything is queued:
+ *   LW_ERR_NULL_ARG     c NULL, n_frames NULL with rows, jobs NULL with jobs, d_src NULL with elements to read, d_dst NULL with
+ *                       elements to write
+ *   LW_ERR_UNSUPPORTED  elem_bytes not 2 or 4
+ *   LW_ERR_DEVICE       (create) no such device
+ *   LW_ERR_CAPACITY     row >= n_rows, start > end, end > n_frames[row], n_frames[row] > capacity, len or fill_to[i] > out_capacity,
+ *                       ch == 0 or > 255, F == 0 or > 65535, a buffer that 64 bits of bytes cannot address, more than 2^24 - 1
+ *                       workgroups (tiles * F) in a channel */
+typedef struct lw_cut lw_cut;
+lw_cut *lw_cut_create(int device, int *err);
+void lw_cut_destroy(lw_cut *c);
+int lw_cut_rows(lw_cut *c, uint32_t ch, uint32_t F, uint32_t elem_bytes, const void *d_src, size_t n_rows, size_t capacity, const uint64_t *n_frames,
+		const uint64_t *jobs, size_t n_out, void *d_dst, size_t out_capacity, const uint64_t *fill_to, void *hip_stream);
+int lw_cut_last_launches(const lw_cut *c);
+
 /* ---- staging ring (BASELINE north_star: "pinned hipMemcpyAsync staging ring so entropy decode of packet N+1 overlaps
  * GPU synthesis of packet N") ------------------------------------------------------------------------------------------
  * A ring of `slots` staging slots on the decoder's device; a slot = one batch object (pinned records + device mirror), a device

@@ -87,6 +87,10 @@ class VadParams(C.Structure):
                 ("proportion_threshold", C.c_float), ("line", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class SegmentParams(C.Structure):
+    _fields_ = [("pad_onset", C.c_uint32), ("pad_offset", C.c_uint32), ("min_off", C.c_uint32), ("min_on", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class OggPacket(C.Structure):
     _fields_ = [("data", C.c_void_p), ("len", C.c_size_t), ("stream_serial", C.c_uint32), ("absgp_page", C.c_uint64),
                 ("first_in_stream", C.c_uint8), ("last_in_stream", C.c_uint8), ("first_in_page", C.c_uint8),
@@ -267,6 +271,18 @@ SYMBOLS = {
     "lw_vad_set_tile_frames": (C.c_int, [C.c_void_p, C.c_uint32]),
     "lw_vad_set_route": (C.c_int, [C.c_void_p, C.c_int]),
     "lw_vad_last_launches": (C.c_int, [C.c_void_p]),
+    "lw_segment_create": (C.c_void_p, [C.c_int, C.POINTER(SegmentParams), intp]),
+    "lw_segment_destroy": (None, [C.c_void_p]),
+    "lw_segment_rows": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t,
+                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lw_segment_tile_frames": (C.c_uint32, [C.c_void_p]),
+    "lw_segment_set_tile_frames": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "lw_segment_last_launches": (C.c_int, [C.c_void_p]),
+    "lw_cut_create": (C.c_void_p, [C.c_int, intp]),
+    "lw_cut_destroy": (None, [C.c_void_p]),
+    "lw_cut_rows": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
+                              C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "lw_cut_last_launches": (C.c_int, [C.c_void_p]),
     "lw_ring_create": (C.c_void_p, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, intp]),
     "lw_ring_destroy": (None, [C.c_void_p]),
     "lw_ring_stage": (C.c_int, [C.c_void_p, C.POINTER(Packet), C.c_size_t, C.c_int]),

@@ -64,6 +64,14 @@ bit for bit):
     voiced = EnergyVad(5.5, 0.5, 2, 0.12).run(feats, frames)
     kept, counts = SelectFrames().run(SlidingCMVN(300, 100, center=True).run(feats, frames), frames, voiced)
 
+Segments turns a mask into stretches of speech (lw_segment_rows, k_segment: pad, fill short gaps, drop short runs, the order of
+pyannote's Binarize, on integers) and CutRows makes every stretch a row of its own (lw_cut_rows, k_cut), so that a recogniser, a
+speaker-embedding extractor or a diarizer gets its segments with one synchronisation and one launch:
+
+    spans, counts = Segments(pad_onset=2, pad_offset=8, min_off=10, min_on=5).run(voiced, frames)
+    jobs, _ = Segments.jobs(spans, counts, hop=160, window=400, lengths=lengths)      # the one synchronisation
+    seg_pcm, seg_len = CutRows().run(pcm, lengths, jobs)
+
 torch is imported inside the functions, never at module import.
 """
 import ctypes as C
@@ -1178,6 +1186,170 @@ class EnergyVad(_Handle):
                    _array_ptr(fill), _stream_of(stream, self.device))
         mask = out if out.dtype == torch.bool else out.view(torch.bool)
         return (mask, thr) if want_threshold else mask
+
+
+SEG_MAX_SPAN = 1024                                       # LW_SEG_MAX_SPAN
+
+
+def _device_number(device):
+    if not _is_int(device) or device < 0:
+        raise ValueError("device=%r: a device number" % (device,))
+    return int(device)
+
+
+class Segments(_Handle):
+    """lw_segment: stretches of speech from a frame mask [rows][C][capacity] (EnergyVad's, a neural VAD's) on the GPU (k_segment), by
+    the rule of include/lewton_amd.h ("segments of a frame mask"), pyannote's Binarize on integers: every set frame is padded by
+    pad_onset frames to the front and pad_offset to the back (a Kaldi-style hangover is pad_offset alone), gaps of fewer than
+    min_off frames between two set frames are filled, runs of fewer than min_on frames are dropped; the maximal runs of what remains
+    are the segments.  All four are counts of frames, at most SEG_MAX_SPAN each.  Spans and counts stay on the device; jobs() is the
+    ONE synchronisation of the step.  Parameter errors are ValueError and need no GPU; the object itself lives on cuda:device."""
+
+    _C = "lw_segment"
+
+    def __init__(self, pad_onset=0, pad_offset=0, min_off=0, min_on=0, device=0):
+        for v, what in ((pad_onset, "pad_onset"), (pad_offset, "pad_offset"), (min_off, "min_off"), (min_on, "min_on")):
+            if not _is_int(v) or not 0 <= v <= SEG_MAX_SPAN:
+                raise ValueError("%s=%r: a count of frames in 0 .. %d" % (what, v, SEG_MAX_SPAN))
+        self.pad_onset, self.pad_offset, self.min_off, self.min_on = int(pad_onset), int(pad_offset), int(min_off), int(min_on)
+        self.device = _device_number(device)
+        _gpu()
+        p = N.SegmentParams(self.pad_onset, self.pad_offset, self.min_off, self.min_on, 0)
+        self._create(self.device, C.byref(p))
+
+    @property
+    def tile_frames(self):
+        """frames of a tile (lw_segment_tile_frames)"""
+        return N.lw_segment_tile_frames(self._h)
+
+    def set_tile_frames(self, m):
+        """a test's handle on the seams (lw_segment_set_tile_frames): a multiple of 256 in 256 .. 2048; the result does not depend on it"""
+        if N.lw_segment_set_tile_frames(self._h, int(m)):
+            raise ValueError("tile_frames=%r: a multiple of 256 in 256 .. 2048" % (m,))
+
+    def last_launches(self):
+        """kernels the last call queued: per 65535 rows 2, or 1 where no row has a frame or only the smoothed mask is wanted; 0 when
+        nothing was to be written; -1: no call yet"""
+        return N.lw_segment_last_launches(self._h)
+
+    def run(self, mask, frames, seg_capacity=None, want_mask=False, out_mask=None, fill_to=None, stream=None):
+        """lw_segment_rows: the segments of the frames[i] frames of row i of mask (torch.bool or uint8 [rows][C][capacity]; any
+        non-zero byte is set) -> spans, torch.int64 [rows][C][seg_capacity][2] ON THE DEVICE, (start, end) of segment k < K in
+        frames, entries from K on unwritten (zero), and counts, torch.int64 [rows][C], the true K even where it exceeds
+        seg_capacity.  seg_capacity=None: max(1, (capacity + 1) // 2), which no mask of capacity frames can exceed.  want_mask
+        (or out_mask, a contiguous uint8 or bool tensor of mask's shape; never mask itself): also the smoothed mask as torch.bool,
+        what SelectFrames takes -- selection with a hangover; its positions [frames[i], fill_to[i]) receive 0 (fill_to: None, one
+        count for all rows or one per row), nothing else of it is written.  stream: a hipStream_t value; None = torch's current
+        stream on the object's device.  Asynchronous; returns (spans, counts) or (spans, counts, smooth)."""
+        torch = _gpu()
+        _check_tensor(mask, "mask", "[rows][C][capacity]", self.device, (torch.bool, torch.uint8), (3,))
+        n_rows, ch, cap = mask.shape
+        if seg_capacity is None:
+            seg_capacity = max(1, (cap + 1) // 2)
+        if not _is_int(seg_capacity) or seg_capacity < 1:
+            raise ValueError("seg_capacity=%r: a positive count of segments" % (seg_capacity,))
+        counts, fill = _row_counts(frames, n_rows, "frames"), _row_fill(fill_to, n_rows)
+        if out_mask is None and want_mask:
+            out_mask = torch.zeros((n_rows, ch, cap), dtype=torch.uint8, device=mask.device)
+        if out_mask is not None:
+            _check_tensor(out_mask, "out_mask", "[rows][C][capacity] = %r" % ((n_rows, ch, cap),), self.device, (torch.bool, torch.uint8),
+                          shape=(n_rows, ch, cap))
+            if out_mask.data_ptr() == mask.data_ptr() and mask.numel():
+                raise ValueError("out_mask must not be mask: the pass has no in-place form")
+        spans = torch.zeros((n_rows, ch, int(seg_capacity), 2), dtype=torch.int64, device=mask.device)
+        k = torch.empty((n_rows, ch), dtype=torch.int64, device=mask.device)
+        self._call(N.lw_segment_rows, ch, _tensor_ptr(mask), _tensor_ptr(spans), _tensor_ptr(k), _tensor_ptr(out_mask), n_rows, cap, int(seg_capacity),
+                   _array_ptr(counts), _array_ptr(fill), _stream_of(stream, self.device))
+        if out_mask is None:
+            return spans, k
+        return spans, k, out_mask if out_mask.dtype == torch.bool else out_mask.view(torch.bool)
+
+    @staticmethod
+    def jobs(spans, counts, hop=1, window=0, lengths=None):
+        """the ONE synchronisation of the step: copies spans and counts (run's results) to the host and returns (jobs, out_len) --
+        jobs a numpy uint64 [n][3] array of (row, start, end) for CutRows.run, in ascending (row * C + c, k) order, where row is
+        row * C + c: [B][C][..] read as [B * C][1][..], the same memory, as SelectFrames documents; out_len the n lengths
+        end - start.  The spans are converted from frames to elements in Python integers: start * hop, and end * hop, or with
+        lengths= (the elements of every row of what will be cut) min(lengths[row], (end - 1) * hop + window), the samples the
+        segment's frames were computed from.  ValueError if any count exceeds seg_capacity.  Any policy beyond that -- splitting at
+        30 s, grouping short segments into one window -- stays with the caller: the list is tiny, the caller is synchronised
+        anyway, and jobs is a plain array to edit."""
+        if not _is_int(hop) or hop < 1 or not _is_int(window) or window < 0:
+            raise ValueError("hop=%r, window=%r: a positive and a non-negative count of elements" % (hop, window))
+        sp, k = spans.cpu().numpy(), counts.cpu().numpy()
+        if sp.ndim != 4 or sp.shape[3] != 2 or k.shape != sp.shape[:2]:
+            raise ValueError("spans must be [rows][C][seg_capacity][2] and counts [rows][C], not %r and %r" % (sp.shape, k.shape))
+        n_rows, ch, seg_cap = sp.shape[:3]
+        if lengths is not None:
+            lengths = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+            if len(lengths) != n_rows or any(v < 0 for v in lengths):
+                raise ValueError("lengths= needs one non-negative entry per row")
+        if k.size and int(k.max()) > seg_cap:
+            raise ValueError("%d segments in a row and channel, seg_capacity is %d" % (int(k.max()), seg_cap))
+        jobs = []
+        for r in range(n_rows):
+            for c in range(ch):
+                for a, b in sp[r, c, :int(k[r, c])].tolist():
+                    end = b * hop if lengths is None else min(lengths[r], (b - 1) * hop + window)
+                    jobs.append((r * ch + c, a * hop, max(end, a * hop)))
+        jobs = np.asarray(jobs, np.uint64).reshape(len(jobs), 3)
+        return jobs, (jobs[:, 2] - jobs[:, 1]).astype(np.int64)
+
+
+_CUT_SAMPLES = {"f32": 4, "i16": 2}
+
+
+class CutRows(_Handle):
+    """lw_cut: one output row per job (row, start, end) over rows [rows][C][capacity] or [rows][C][F][capacity] of float32 or int16 on
+    the GPU (k_cut), by the rule of include/lewton_amd.h ("cutting rows into segment rows"): bit copies, the rest of every line up
+    to max(len, fill_to) zeroed -- the waveform or the features of every segment of Segments.jobs as a row of its own, in ONE
+    launch.  Parameter errors are ValueError and need no GPU; the object itself lives on cuda:device."""
+
+    _C = "lw_cut"
+
+    def __init__(self, device=0):
+        self.device = _device_number(device)
+        self._create(self.device)
+
+    def last_launches(self):
+        """kernels the last call queued: 1 per 65535 jobs, 0 when nothing was to be written; -1: no call yet"""
+        return N.lw_cut_last_launches(self._h)
+
+    def run(self, src, lengths, jobs, out=None, fill_to=None, stream=None, samples="f32"):
+        """lw_cut_rows: for job i = (row, start, end) of jobs (array-like [n][3]; 0 <= start <= end <= lengths[row]), elements
+        [start, end) of every line of row `row` of src (samples="f32": float32, "i16": int16; [rows][C][capacity] or
+        [rows][C][F][capacity]) -> the front of the lines of row i of out (None: a zeroed tensor [n][C]([F])[max(longest job,
+        fill_to)]); positions [end - start, fill_to[i]) receive 0 (fill_to: None, one count for all jobs or one per job).  Nothing
+        else of out is written.  A source whose channels were segmented apart is src.reshape(B * C, 1, ...), as Segments.jobs
+        numbers its rows.  stream: a hipStream_t value; None = torch's current stream on the object's device.  Asynchronous;
+        returns (out, out_len), out_len an int64 host tensor with end - start per job: the next pass's lengths."""
+        torch = _gpu()
+        if samples not in _CUT_SAMPLES:
+            raise ValueError("samples=%r: \"f32\" or \"i16\"" % (samples,))
+        dtype = torch.float32 if samples == "f32" else torch.int16
+        _check_tensor(src, "src", "[rows][C][capacity] or [rows][C][F][capacity]", self.device, (dtype,), (3, 4))
+        n_rows, ch = src.shape[:2]
+        F, cap = (1, src.shape[2]) if src.dim() == 3 else (src.shape[2], src.shape[3])
+        lens = _row_counts(lengths, n_rows, "lengths")
+        try:
+            jb = np.ascontiguousarray(np.asarray(jobs if len(jobs) else np.zeros((0, 3)), dtype=np.int64))
+        except (TypeError, ValueError, OverflowError):
+            raise ValueError("jobs= must be [n][3] integers (row, start, end)")
+        if jb.ndim != 2 or jb.shape[1] != 3 or (jb < 0).any():
+            raise ValueError("jobs= must be [n][3] non-negative integers (row, start, end), not %r" % (jb.shape,))
+        jb = jb.astype(np.uint64)
+        n_out = jb.shape[0]
+        fill = _row_fill(fill_to, n_out)
+        out_len = (jb[:, 2].astype(np.int64) - jb[:, 1].astype(np.int64))
+        if out is None:
+            T = max(int(out_len.max()) if n_out else 0, int(fill.max()) if fill is not None and n_out else 0, 0)
+            out = torch.zeros((n_out, ch, T) if src.dim() == 3 else (n_out, ch, F, T), dtype=dtype, device=src.device)
+        _check_tensor(out, "out", "[jobs][C][F][capacity] (three dimensions when src has three)", self.device, (dtype,), (src.dim(),))
+        if out.shape[0] != n_out or tuple(out.shape[1:-1]) != tuple(src.shape[1:-1]):
+            raise ValueError("out must be %r + [capacity], not %r" % ((n_out,) + tuple(src.shape[1:-1]), tuple(out.shape)))
+        self._call(N.lw_cut_rows, ch, F, _CUT_SAMPLES[samples], _tensor_ptr(src), n_rows, cap, _array_ptr(lens), _array_ptr(jb if n_out else None), n_out,
+                   _tensor_ptr(out), out.shape[-1], _array_ptr(fill), _stream_of(stream, self.device))
+        return out, torch.tensor(out_len.tolist(), dtype=torch.int64)
 
 
 CEP_MAX_IN,CEP_MAX_OUT, CEP_MAX_WIDTH = 256, 256, 16     # LW_CEP_MAX_IN, LW_CEP_MAX_OUT, LW_CEP_MAX_WIDTH
