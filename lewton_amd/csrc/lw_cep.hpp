@@ -4,14 +4,7 @@
 // translation unit sees it.
 #pragma once
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#if defined(__HIPCC__) || defined(__HIP__)
-#define LW_CP_HD __host__ __device__ static inline
-#else
-#define LW_CP_HD static inline
-#endif
+#include "lw_lanes.hpp"
 
 #define LW_CP_THREADS 256u  // a workgroup: one frame per lane, halo included
 #define LW_CP_GROUP 32u     // output lines (accumulators) a lane carries at a time
@@ -20,14 +13,14 @@
 
 // ---- the contract's delta step: acc = fmaf(w_n, after - before, acc).  The subtraction is one rounded f32 operation of its own
 // (the units that include this are compiled with -ffp-contract=off, and fmaf is asked for by name).
-LW_CP_HD float lw_cep_delta_step(float w, float after, float before, float acc)
+LW_LANES_HD float lw_cep_delta_step(float w, float after, float before, float acc)
 {
 	const float d = after - before;
 	return __builtin_fmaf(w, d, acc);
 }
 
 // c(i) = min(max(i, 0), n - 1) in signed 64-bit integers (n >= 1)
-LW_CP_HD int64_t lw_cep_clamp(int64_t i, int64_t n)
+LW_LANES_HD int64_t lw_cep_clamp(int64_t i, int64_t n)
 {
 	return i < 0 ? 0 : i >= n ? n - 1 : i;
 }

@@ -4,18 +4,11 @@
 // other translation unit sees it.
 #pragma once
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#if defined(__HIPCC__) || defined(__HIP__)
-#define LW_FT_HD __host__ __device__ static inline
-#else
-#define LW_FT_HD static inline
-#endif
+#include "lw_lanes.hpp"
 
 // ---- LOG (step 2 of the contract).  Every operation below is one IEEE double operation: the units that include this are compiled
 // with -ffp-contract=off, the quotients c_k are folded by the compiler, correctly rounded.  `kind` is LW_FEAT_LOG_*.
-LW_FT_HD float lw_feat_log_value(int kind, float v)
+LW_LANES_HD float lw_feat_log_value(int kind, float v)
 {
 	if (kind == 0 || v == __builtin_inff())
 		return v;
@@ -46,12 +39,12 @@ LW_FT_HD float lw_feat_log_value(int kind, float v)
 
 // ---- the maximum in the total order of the non-NaN floats (+0.0 above -0.0): a float's bits as a signed integer, the negative
 // half reversed, compare as integers
-LW_FT_HD int32_t lw_ft_key(float f)
+LW_LANES_HD int32_t lw_ft_key(float f)
 {
 	const int32_t i = __builtin_bit_cast(int32_t, f);
 	return i < 0 ? i ^ 0x7fffffff : i;
 }
-LW_FT_HD float lw_ft_unkey(int32_t k)
+LW_LANES_HD float lw_ft_unkey(int32_t k)
 {
 	return __builtin_bit_cast(float, k < 0 ? k ^ 0x7fffffff : k);
 }
@@ -64,36 +57,18 @@ struct LwFeatRow {
 };
 static_assert(sizeof(LwFeatRow) == 16, "LwFeatRow is read as four dwords");
 
-// The tile plan.  A RUN is 64 groups of four consecutive frames of one line, a group aligned to 16 bytes in the destination (so a
-// line whose address is not a multiple of 16 has a partial group at its head and one at its tail: the scalar head and tail); lane
-// i of a wave takes group i of a run.  A channel's runs are numbered line-major, run = line * runs_per_line + index.  A workgroup
-// of LW_FT_THREADS lanes (four waves) is a TILE: 4 * per_wave consecutive runs of one (row, channel), wave w taking runs
-// w, w + 4, ... of them, so all of a tile lies in one scope, and a scope of a row has at most about LW_FT_MAX_TILES tiles,
-// whose maxima the second launch reads again.
+// The tile plan: runs of four (lw_lanes.hpp), so all of a tile lies in one scope, and a scope of a row has at most about
+// LW_FT_MAX_TILES tiles, whose maxima the second launch reads again.
 #define LW_FT_THREADS 256u
 #define LW_FT_WAVES 4u
-#define LW_FT_RUN 256u        // frames per run
 #define LW_FT_MAX_TILES 1024u // tiles per row the plan aims at (a channel has at least one)
 
-struct LwFeatPlan {
-	uint32_t runs_per_line; // ceil((span + 3) / 256), span = the call's largest fill_end; at least 1
-	uint32_t runs;          // per channel: F * runs_per_line
-	uint32_t per_wave;      // runs a wave takes
-	uint32_t tiles;         // per channel: ceil(runs / (4 * per_wave))
-};
+typedef LwRunPlan LwFeatPlan;
 
 // false: more runs in a channel than 32 bits count
 static inline bool lw_feat_plan(uint32_t ch, uint32_t F, uint64_t span, LwFeatPlan &p)
 {
-	const uint64_t rpl = (span + 3u + LW_FT_RUN - 1u) / LW_FT_RUN, runs = rpl * F;
-	if (runs > UINT32_MAX)
-		return false;
-	const uint32_t aim = LW_FT_MAX_TILES / ch ? LW_FT_MAX_TILES / ch : 1u; // tiles per channel
-	const uint64_t units = (runs + LW_FT_WAVES - 1u) / LW_FT_WAVES;        // a unit: one run for each wave
-	p.runs_per_line = (uint32_t)rpl, p.runs = (uint32_t)runs;
-	p.per_wave = (uint32_t)((units + aim - 1u) / aim);
-	p.tiles = (uint32_t)((units + p.per_wave - 1u) / p.per_wave);
-	return true;
+	return lw_run_plan(ch, F, span, LW_FT_MAX_TILES, p);
 }
 
 struct LwFeatArgs {

@@ -17,14 +17,10 @@
 // (LW_CEP_HOST) and runs it workgroup by workgroup, the phases in the kernel's order.
 #include "lw_cep.hpp"
 
-#ifdef LW_CEP_HOST
-#define LW_CP_FN static inline
-#define LW_CP_RESTRICT
+#ifdef LW_KERNEL_HOST
 #define LW_CP_LINE_DONE() (void)0
 #else
 #include "lw_kernels.hpp"
-#define LW_CP_FN __device__ __forceinline__
-#define LW_CP_RESTRICT __restrict__
 // Nothing is scheduled across the end of an input line's folds: left alone, the scheduler fetches the weights of all eight lines
 // of a step at once, 256 scalar registers' worth, and spills them lane by lane into vector registers inside the loop.
 #define LW_CP_LINE_DONE() asm volatile("" ::: "memory")
@@ -41,7 +37,7 @@ struct LwCpTile { // what a workgroup works on; the same for all its lanes
 };
 
 // false: the tile lies at or beyond the row's fill_end, nothing to do
-LW_CP_FN bool lw_cp_tile(const LwCepArgs &a, uint32_t bx, uint32_t by, uint32_t bz, LwCpTile &t)
+LW_LANES_FN bool lw_cp_tile(const LwCepArgs &a, uint32_t bx, uint32_t by, uint32_t bz, LwCpTile &t)
 {
 	const uint64_t row = (uint64_t)a.row0 + bz, t0 = (uint64_t)bx * a.plan.tile;
 	const LwCepRow r = a.rows[row];
@@ -54,14 +50,14 @@ LW_CP_FN bool lw_cp_tile(const LwCepArgs &a, uint32_t bx, uint32_t by, uint32_t 
 }
 
 // the frame lane `tid` computes at (the tile has data, so n >= 1)
-LW_CP_FN int64_t lw_cp_frame(const LwCpTile &t, uint32_t tid)
+LW_LANES_FN int64_t lw_cp_frame(const LwCpTile &t, uint32_t tid)
 {
 	return lw_cep_clamp(t.first + (int64_t)tid, (int64_t)t.n);
 }
 
 // ---- the statics of G consecutive outputs from q0 at frame cs: s[j] = the chain over f ascending from +0.0, or the bit copy
 template <int G>
-LW_CP_FN void lw_cp_static(const LwCepArgs &a, const LwCpTile &t, const float *LW_CP_RESTRICT mt, const float *LW_CP_RESTRICT src, uint32_t q0,
+LW_LANES_FN void lw_cp_static(const LwCepArgs &a, const LwCpTile &t, const float *LW_LANES_RESTRICT mt, const float *LW_LANES_RESTRICT src, uint32_t q0,
 		uint32_t g, int64_t cs, float (&s)[G])
 {
 	const float *x = src + t.src_at + (uint64_t)cs;
@@ -99,7 +95,7 @@ LW_CP_FN void lw_cp_static(const LwCepArgs &a, const LwCpTile &t, const float *L
 
 // ---- a lane's values into its column of the LDS image [G][256]
 template <int G>
-LW_CP_FN void lw_cp_put(float *img, uint32_t tid, const float (&v)[G])
+LW_LANES_FN void lw_cp_put(float *img, uint32_t tid, const float (&v)[G])
 {
 #pragma unroll
 	for (int j = 0; j < G; j++)
@@ -107,7 +103,7 @@ LW_CP_FN void lw_cp_put(float *img, uint32_t tid, const float (&v)[G])
 }
 
 // does lane tid compute level `level` (1: delta, 2: delta-delta)?  The lanes level * width and more from either end
-LW_CP_FN bool lw_cp_has(const LwCepArgs &a, uint32_t level, uint32_t tid)
+LW_LANES_FN bool lw_cp_has(const LwCepArgs &a, uint32_t level, uint32_t tid)
 {
 	return tid >= level * a.width && tid < LW_CP_THREADS - level * a.width;
 }
@@ -115,7 +111,7 @@ LW_CP_FN bool lw_cp_has(const LwCepArgs &a, uint32_t level, uint32_t tid)
 // ---- the delta at frame cs of the G lines of the image: n ascending from +0.0; the neighbours are the lanes that stand on the
 // clamped frames c(cs + n) and c(cs - n), which lie in the image (lw_cep.hpp, the tile plan)
 template <int G>
-LW_CP_FN void lw_cp_delta(const LwCepArgs &a, const LwCpTile &t, const float *img, int64_t cs, float (&d)[G])
+LW_LANES_FN void lw_cp_delta(const LwCepArgs &a, const LwCpTile &t, const float *img, int64_t cs, float (&d)[G])
 {
 #pragma unroll
 	for (int j = 0; j < G; j++)
@@ -133,7 +129,7 @@ LW_CP_FN void lw_cp_delta(const LwCepArgs &a, const LwCpTile &t, const float *im
 // ---- the tile's lanes store lines q0 .. q0 + g - 1 of level `level` (0: statics) at their frame: the value below n, +0.0 in
 // [n, fill_end), nothing beyond
 template <int G>
-LW_CP_FN void lw_cp_store(const LwCepArgs &a, const LwCpTile &t, float *LW_CP_RESTRICT dst, uint32_t q0, uint32_t g, uint32_t level, uint32_t tid,
+LW_LANES_FN void lw_cp_store(const LwCepArgs &a, const LwCpTile &t, float *LW_LANES_RESTRICT dst, uint32_t q0, uint32_t g, uint32_t level, uint32_t tid,
 		const float (&v)[G])
 {
 	if (tid < a.plan.halo || tid >= LW_CP_THREADS - a.plan.halo)
@@ -149,7 +145,7 @@ LW_CP_FN void lw_cp_store(const LwCepArgs &a, const LwCpTile &t, float *LW_CP_RE
 			o[(uint64_t)j * a.line_el] = data ? v[j] : 0.0f;
 }
 
-#ifndef LW_CEP_HOST
+#ifndef LW_KERNEL_HOST
 
 // one group of outputs for one lane; every lane of the workgroup comes here (the barriers)
 template <int G>
@@ -211,4 +207,4 @@ hipError_t lw_launch_cep(const LwCepArgs &a, const float *mt, const float *src, 
 	return lw_launch_k(k_cep, dim3(tiles, a.ch, n_rows), dim3(LW_CP_THREADS), (size_t)a.plan.lds, st, a, mt, src, dst);
 }
 
-#endif // LW_CEP_HOST
+#endif // LW_KERNEL_HOST

@@ -13,11 +13,9 @@
 
 #include <string.h>
 
-#ifdef LW_CUT_HOST
-#define LW_CT_FN static inline
-#else
+#include "lw_lanes.hpp"
+#ifndef LW_KERNEL_HOST
 #include "lw_kernels.hpp"
-#define LW_CT_FN __device__ __forceinline__
 #endif
 
 typedef uint32_t LwCtV4 __attribute__((vector_size(16)));
@@ -29,7 +27,7 @@ struct LwCtTile { // what a workgroup works on; the same for all its lanes
 	uint64_t b0, b1;  // the tile's bytes of the line: its share of [0, fill_end)
 };
 
-LW_CT_FN void lw_ct_tile(const LwCutArgs &a, uint32_t bx, uint32_t by, uint32_t bz, LwCtTile &t)
+LW_LANES_FN void lw_ct_tile(const LwCutArgs &a, uint32_t bx, uint32_t by, uint32_t bz, LwCtTile &t)
 {
 	const uint64_t job = (uint64_t)a.job0 + bz;
 	const LwCutJob j = a.jobs[job];
@@ -44,7 +42,7 @@ LW_CT_FN void lw_ct_tile(const LwCutArgs &a, uint32_t bx, uint32_t by, uint32_t 
 
 // the element at byte p of the line: a copy below len_b, zero bits from there on
 template <uint32_t ELEM>
-LW_CT_FN uint32_t lw_ct_elem(const LwCtTile &t, uint64_t p)
+LW_LANES_FN uint32_t lw_ct_elem(const LwCtTile &t, uint64_t p)
 {
 	if (p >= t.len_b)
 		return 0u;
@@ -54,7 +52,7 @@ LW_CT_FN uint32_t lw_ct_elem(const LwCtTile &t, uint64_t p)
 }
 
 template <uint32_t ELEM>
-LW_CT_FN void lw_ct_lane(const LwCtTile &t, uint32_t tid)
+LW_LANES_FN void lw_ct_lane(const LwCtTile &t, uint32_t tid)
 {
 	if (t.b0 >= t.b1)
 		return;
@@ -85,7 +83,7 @@ LW_CT_FN void lw_ct_lane(const LwCtTile &t, uint32_t tid)
 	}
 }
 
-LW_CT_FN void lw_ct_workgroup_lane(const LwCutArgs &a, uint32_t bx, uint32_t by, uint32_t bz, uint32_t tid)
+LW_LANES_FN void lw_ct_workgroup_lane(const LwCutArgs &a, uint32_t bx, uint32_t by, uint32_t bz, uint32_t tid)
 {
 	LwCtTile t;
 	lw_ct_tile(a, bx, by, bz, t);
@@ -95,7 +93,7 @@ LW_CT_FN void lw_ct_workgroup_lane(const LwCutArgs &a, uint32_t bx, uint32_t by,
 		lw_ct_lane<2u>(t, tid);
 }
 
-#ifndef LW_CUT_HOST
+#ifndef LW_KERNEL_HOST
 
 __global__ void __launch_bounds__(LW_CT_THREADS) k_cut(LwCutArgs a)
 {
@@ -110,4 +108,4 @@ hipError_t lw_launch_cut(const LwCutArgs &a, uint32_t n_jobs, hipStream_t st)
 	return lw_launch_k(k_cut, dim3(a.tiles * a.F, a.ch, n_jobs), dim3(LW_CT_THREADS), 0, st, a);
 }
 
-#endif // LW_CUT_HOST
+#endif // LW_KERNEL_HOST

@@ -18,16 +18,11 @@
 // tests/san/feat_host.cpp compiles this file for the host (LW_FEAT_HOST) and runs it workgroup by workgroup, lane by lane.
 #include "lw_feat.hpp"
 
-#ifdef LW_FEAT_HOST
-#define LW_FT_FN static inline
-#else
+#ifndef LW_KERNEL_HOST
 #include "lw_kernels.hpp"
-#define LW_FT_FN __device__ __forceinline__
 #endif
 
-struct alignas(16) LwFtF4 {
-	float v[4];
-};
+static_assert(LW_FT_WAVES == LW_LANES_WAVES, "lw_lanes.hpp's plans count four waves to a workgroup");
 
 struct LwFtTile { // what a workgroup works on; the same for all its lanes
 	uint64_t n, end;  // the row's n_frames and fill_end
@@ -36,7 +31,7 @@ struct LwFtTile { // what a workgroup works on; the same for all its lanes
 	uint64_t run0;    // first run of the tile (64-bit: a tile's last runs may lie behind the channel's, which 32 bits count)
 };
 
-LW_FT_FN void lw_ft_tile(const LwFeatArgs &a, uint32_t bx, uint32_t by, uint32_t bz, LwFtTile &t)
+LW_LANES_FN void lw_ft_tile(const LwFeatArgs &a, uint32_t bx, uint32_t by, uint32_t bz, LwFtTile &t)
 {
 	const uint64_t row = (uint64_t)a.row0 + bz;
 	const LwFeatRow r = a.rows[row];
@@ -47,38 +42,34 @@ LW_FT_FN void lw_ft_tile(const LwFeatArgs &a, uint32_t bx, uint32_t by, uint32_t
 }
 
 // steps 1 and 2, and steps 4 and 5
-LW_FT_FN float lw_ft_log(const LwFeatArgs &a, float x)
+LW_LANES_FN float lw_ft_log(const LwFeatArgs &a, float x)
 {
 	const float v = x > a.floor ? x : a.floor;
 	return lw_feat_log_value(a.log, v);
 }
 
-LW_FT_FN float lw_ft_finish(const LwFeatArgs &a, float l, float tt)
+LW_LANES_FN float lw_ft_finish(const LwFeatArgs &a, float l, float tt)
 {
 	const float y = l > tt ? l : tt;
 	const float s = y + a.add;
 	return s * a.mul;
 }
 
-LW_FT_FN float lw_ft_tt(const LwFeatArgs &a, float M)
+LW_LANES_FN float lw_ft_tt(const LwFeatArgs &a, float M)
 {
 	return a.top == __builtin_inff() ? -__builtin_inff() : M - a.top;
 }
 
-// the lane's group of run `run` of the tile's channel: the line's element offset, the group's first frame (-3 .. at the head of
-// a line that starts off a 16-byte boundary), whether the source line sits like the destination line.  false: no such group
-LW_FT_FN bool lw_ft_group(const LwFeatArgs &a, const LwFtTile &t, uint32_t run, uint32_t lane, uint64_t lim, uint64_t &at, int64_t &t0, bool &same)
+// the lane's group of run `run` of the tile's channel (lw_run_group).  false: no such group below lim
+LW_LANES_FN bool lw_ft_group(const LwFeatArgs &a, const LwFtTile &t, uint32_t run, uint32_t lane, uint64_t lim, uint64_t &at, int64_t &t0, bool &same)
 {
-	const uint32_t line = run / a.plan.runs_per_line, idx = run % a.plan.runs_per_line;
-	at = t.ch_at + (uint64_t)line * a.line_el;
-	const uint32_t sd = (uint32_t)(((uintptr_t)a.dst >> 2) + at) & 3u, ss = (uint32_t)(((uintptr_t)a.src >> 2) + at) & 3u; // (src may be NULL)
-	same = sd == ss;
-	t0 = (int64_t)(((uint64_t)idx * (LW_FT_RUN / 4u) + lane) * 4u) - (int64_t)sd;
+	const LwRunGroup g = lw_run_group(a.plan.runs_per_line, a.src, a.dst, t.ch_at, a.line_el, run, lane);
+	at = g.at, t0 = g.t0, same = g.same;
 	return t0 < (int64_t)lim;
 }
 
 // ---- first launch: one run for one lane.  key: the lane's running maximum of l (lw_ft_key)
-LW_FT_FN void lw_ft_run_log(const LwFeatArgs &a, const LwFtTile &t, uint32_t run, uint32_t lane, int32_t &key)
+LW_LANES_FN void lw_ft_run_log(const LwFeatArgs &a, const LwFtTile &t, uint32_t run, uint32_t lane, int32_t &key)
 {
 	const uint64_t lim = a.final ? t.end : t.n;
 	const float ninf = -__builtin_inff(), fillz = lw_ft_finish(a, a.l0, ninf);
@@ -89,9 +80,9 @@ LW_FT_FN void lw_ft_run_log(const LwFeatArgs &a, const LwFtTile &t, uint32_t run
 		return;
 	if (t0 >= 0 && (uint64_t)t0 + 4u <= t.n) { // all four are data
 		const float *s = a.src + at + t0;
-		LwFtF4 x;
+		LwF4 x;
 		if (same)
-			x = *(const LwFtF4 *)s;
+			x = *(const LwF4 *)s;
 		else
 			x.v[0] = s[0], x.v[1] = s[1], x.v[2] = s[2], x.v[3] = s[3];
 #pragma unroll
@@ -101,11 +92,11 @@ LW_FT_FN void lw_ft_run_log(const LwFeatArgs &a, const LwFtTile &t, uint32_t run
 			key = k > key ? k : key;
 			x.v[j] = a.final ? lw_ft_finish(a, l, ninf) : l;
 		}
-		*(LwFtF4 *)(a.dst + at + t0) = x;
+		*(LwF4 *)(a.dst + at + t0) = x;
 		return;
 	}
 	if (t0 >= 0 && (uint64_t)t0 >= t.n && (uint64_t)t0 + 4u <= t.end) { // all four are fill (only when final: t0 < lim)
-		*(LwFtF4 *)(a.dst + at + t0) = LwFtF4{{fillz, fillz, fillz, fillz}};
+		*(LwF4 *)(a.dst + at + t0) = LwF4{{fillz, fillz, fillz, fillz}};
 		return;
 	}
 	for (int j = 0; j < 4; j++) { // the line's head, the tail of the data, the tail of the fill
@@ -124,7 +115,7 @@ LW_FT_FN void lw_ft_run_log(const LwFeatArgs &a, const LwFtTile &t, uint32_t run
 }
 
 // ---- second launch: one run for one lane; l comes from dst
-LW_FT_FN void lw_ft_run_fin(const LwFeatArgs &a, const LwFtTile &t, uint32_t run, uint32_t lane, float tt, float fillz)
+LW_LANES_FN void lw_ft_run_fin(const LwFeatArgs &a, const LwFtTile &t, uint32_t run, uint32_t lane, float tt, float fillz)
 {
 	uint64_t at;
 	int64_t t0;
@@ -132,15 +123,15 @@ LW_FT_FN void lw_ft_run_fin(const LwFeatArgs &a, const LwFtTile &t, uint32_t run
 	if (!lw_ft_group(a, t, run, lane, t.end, at, t0, same))
 		return;
 	if (t0 >= 0 && (uint64_t)t0 + 4u <= t.n) {
-		LwFtF4 x = *(const LwFtF4 *)(a.dst + at + t0);
+		LwF4 x = *(const LwF4 *)(a.dst + at + t0);
 #pragma unroll
 		for (int j = 0; j < 4; j++)
 			x.v[j] = lw_ft_finish(a, x.v[j], tt);
-		*(LwFtF4 *)(a.dst + at + t0) = x;
+		*(LwF4 *)(a.dst + at + t0) = x;
 		return;
 	}
 	if (t0 >= 0 && (uint64_t)t0 >= t.n && (uint64_t)t0 + 4u <= t.end) {
-		*(LwFtF4 *)(a.dst + at + t0) = LwFtF4{{fillz, fillz, fillz, fillz}};
+		*(LwF4 *)(a.dst + at + t0) = LwF4{{fillz, fillz, fillz, fillz}};
 		return;
 	}
 	for (int j = 0; j < 4; j++) {
@@ -153,7 +144,7 @@ LW_FT_FN void lw_ft_run_fin(const LwFeatArgs &a, const LwFtTile &t, uint32_t run
 
 // ---- the phases of a workgroup, per lane; between them the workgroup's maximum of the lanes' keys
 // first launch: the lane's runs of the tile
-LW_FT_FN int32_t lw_ft_tile_log(const LwFeatArgs &a, const LwFtTile &t, uint32_t tid)
+LW_LANES_FN int32_t lw_ft_tile_log(const LwFeatArgs &a, const LwFtTile &t, uint32_t tid)
 {
 	const uint32_t lane = tid & 63u, wave = tid >> 6;
 	int32_t key = LW_FT_KEY_LOWEST;
@@ -166,13 +157,13 @@ LW_FT_FN int32_t lw_ft_tile_log(const LwFeatArgs &a, const LwFtTile &t, uint32_t
 }
 
 // ... and the tile's maximum into its place (one lane)
-LW_FT_FN void lw_ft_tile_part(const LwFeatArgs &a, const LwFtTile &t, uint32_t bx, int32_t key)
+LW_LANES_FN void lw_ft_tile_part(const LwFeatArgs &a, const LwFtTile &t, uint32_t bx, int32_t key)
 {
 	a.part[t.part_at + bx] = lw_ft_unkey(key);
 }
 
 // second launch: the lane's share of the maxima of the scope's tiles
-LW_FT_FN int32_t lw_ft_scope_key(const LwFeatArgs &a, const LwFtTile &t, uint32_t by, uint32_t tid)
+LW_LANES_FN int32_t lw_ft_scope_key(const LwFeatArgs &a, const LwFtTile &t, uint32_t by, uint32_t tid)
 {
 	const bool row = a.scope == 0; // LW_FEAT_SCOPE_ROW: the channels' tiles lie side by side
 	const float *p = a.part + (row ? t.part_at - (uint64_t)by * a.plan.tiles : t.part_at);
@@ -186,7 +177,7 @@ LW_FT_FN int32_t lw_ft_scope_key(const LwFeatArgs &a, const LwFtTile &t, uint32_
 }
 
 // ... and with the scope's maximum: M (to d_max by the scope's first lane), the clamp, the tile's runs
-LW_FT_FN void lw_ft_tile_fin(const LwFeatArgs &a, const LwFtTile &t, uint32_t bx, uint32_t by, uint32_t bz, uint32_t tid, int32_t key)
+LW_LANES_FN void lw_ft_tile_fin(const LwFeatArgs &a, const LwFtTile &t, uint32_t bx, uint32_t by, uint32_t bz, uint32_t tid, int32_t key)
 {
 	const float M = t.n ? lw_ft_unkey(key) : a.l0; // (an empty scope's tiles all hold -inf)
 	const float tt = lw_ft_tt(a, M), fillz = lw_ft_finish(a, a.l0, tt);
@@ -203,7 +194,7 @@ LW_FT_FN void lw_ft_tile_fin(const LwFeatArgs &a, const LwFtTile &t, uint32_t bx
 	}
 }
 
-#ifndef LW_FEAT_HOST
+#ifndef LW_KERNEL_HOST
 
 // the workgroup's maximum of its lanes' keys, in every lane: butterfly within the wave, then LDS across the waves
 __device__ __forceinline__ int32_t lw_ft_wg_max(int32_t key, int32_t *lds, uint32_t tid)
@@ -265,4 +256,4 @@ hipError_t lw_launch_feat_fin(const LwFeatArgs &a, uint32_t n_rows, hipStream_t 
 	return lw_launch_k(k_feat_fin, dim3(a.plan.tiles, a.ch, n_rows), dim3(LW_FT_THREADS), 0, st, a);
 }
 
-#endif // LW_FEAT_HOST
+#endif // LW_KERNEL_HOST

@@ -30,11 +30,9 @@
 // (profiles/rows_istft_resource_usage.txt).
 #include "lw_istft.hpp"
 
-#ifdef LW_ISTFT_HOST
-#define LW_IS_FN static inline
-#else
+#include "lw_lanes.hpp"
+#ifndef LW_KERNEL_HOST
 #include "lw_kernels.hpp"
-#define LW_IS_FN __device__ __forceinline__
 #endif
 
 struct LwIsTile { // what a workgroup works on; the same for all its lanes
@@ -50,13 +48,10 @@ struct LwIsTile { // what a workgroup works on; the same for all its lanes
 };
 
 struct LwIsLane { // what a lane keeps in registers between the phases of its workgroup
-	float acc[2][16]; // [tile][register]: sample = LW_IS_ROW(register, lane), frame = lane & 31
+	float acc[2][16]; // [tile][register]: sample = LW_MFMA32_ROW(register, lane), frame = lane & 31
 };
 
-// C/D layout of the 32x32 matrix instructions: register r of lane l holds row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31
-#define LW_IS_ROW(r, lane) (((r) & 3u) + 8u * ((r) >> 2) + 4u * ((lane) >> 5))
-
-LW_IS_FN bool lw_is_tile(const LwIstftArgs &a, uint32_t bx, uint32_t by, uint32_t bz, LwIsTile &t)
+LW_LANES_FN bool lw_is_tile(const LwIstftArgs &a, uint32_t bx, uint32_t by, uint32_t bz, LwIsTile &t)
 {
 	const LwIstftRow r = a.rows[(uint64_t)a.row0 + bz];
 	t.T = r.frames, t.out_len = r.out_len;
@@ -76,7 +71,7 @@ LW_IS_FN bool lw_is_tile(const LwIstftArgs &a, uint32_t bx, uint32_t by, uint32_
 }
 
 // the tile's frames [f_lo, f_hi] whose support sample r - f hop lies in [klo, khi): false when there is none
-LW_IS_FN bool lw_is_range(const LwIstftArgs &a, const LwIsTile &t, int32_t r, uint32_t klo, uint32_t khi, uint32_t &f_lo, uint32_t &f_hi)
+LW_LANES_FN bool lw_is_range(const LwIstftArgs &a, const LwIsTile &t, int32_t r, uint32_t klo, uint32_t khi, uint32_t &f_lo, uint32_t &f_hi)
 {
 	if (t.nf == 0 || r < (int32_t)klo)
 		return false;
@@ -91,7 +86,7 @@ struct alignas(16) LwIsF4 {
 	float v[4];
 };
 
-LW_IS_FN void lw_is_zero_acc(LwIsLane &st)
+LW_LANES_FN void lw_is_zero_acc(LwIsLane &st)
 {
 #pragma unroll
 	for (int i = 0; i < 2; i++)
@@ -101,14 +96,14 @@ LW_IS_FN void lw_is_zero_acc(LwIsLane &st)
 }
 
 // xh of the owned span from +0.0; sample i is lane i mod 256's in every phase
-LW_IS_FN void lw_is_zero_span(const LwIsTile &t, uint32_t tid, float *lds)
+LW_LANES_FN void lw_is_zero_span(const LwIsTile &t, uint32_t tid, float *lds)
 {
 	for (uint32_t i = tid; i < t.span; i += LW_IS_THREADS)
 		lds[LW_IS_LDS_H + i] = 0.0f;
 }
 
 // ---- stage: K tile kt of pass `pass` into LDS; all of a lane's loads are in flight before its first store
-LW_IS_FN void lw_is_stage(const LwIstftArgs &a, const LwIsTile &t, uint32_t pass, uint32_t kt, uint32_t tid, float *lds)
+LW_LANES_FN void lw_is_stage(const LwIstftArgs &a, const LwIsTile &t, uint32_t pass, uint32_t kt, uint32_t tid, float *lds)
 {
 	const uint32_t l0 = kt * LW_IS_KT;
 	const LwIsF4 *g = (const LwIsF4 *)(a.table + ((size_t)pass * a.l_pad + l0) * LW_IS_COLS);
@@ -136,21 +131,21 @@ LW_IS_FN void lw_is_stage(const LwIstftArgs &a, const LwIsTile &t, uint32_t pass
 }
 
 // which of a wave's two tiles hold a support sample at all
-LW_IS_FN bool lw_is_tile_live(const LwIstftArgs &a, uint32_t pass, uint32_t wave, uint32_t tt)
+LW_LANES_FN bool lw_is_tile_live(const LwIstftArgs &a, uint32_t pass, uint32_t wave, uint32_t tt)
 {
 	return pass * LW_IS_COLS + wave * 64u + tt * 32u < a.win_length;
 }
 
-#ifndef LW_ISTFT_HOST
+#ifndef LW_KERNEL_HOST
 typedef float lw_is_f16 __attribute__((ext_vector_type(16)));
 #endif
 
 // ---- fold: the 16 source lines of the staged tile into the lane's accumulators, l ascending
-template <int ROUTE> LW_IS_FN void lw_is_mma(const LwIstftArgs &a, uint32_t pass, uint32_t tid, const float *lds, LwIsLane &st)
+template <int ROUTE> LW_LANES_FN void lw_is_mma(const LwIstftArgs &a, uint32_t pass, uint32_t tid, const float *lds, LwIsLane &st)
 {
 	const uint32_t lane = tid & 63u, wave = tid >> 6, f = lane & 31u;
 	const float *as = lds + LW_IS_LDS_A + wave * 64u, *xs = lds + LW_IS_LDS_X;
-#ifndef LW_ISTFT_HOST
+#ifndef LW_KERNEL_HOST
 	if (ROUTE == LW_IS_ROUTE_MFMA) {
 		// A[i = lane & 31][k = lane >> 5] = G[line k][sample i], B[k = lane >> 5][j = lane & 31] = X[line k][frame j]: one f32 each
 		const uint32_t h = lane >> 5;
@@ -181,13 +176,13 @@ template <int ROUTE> LW_IS_FN void lw_is_mma(const LwIstftArgs &a, uint32_t pass
 			const float *row = as + kk * LW_IS_COLS + tt * 32u;
 #pragma unroll
 			for (uint32_t r = 0; r < 16u; r++)
-				st.acc[tt][r] = __builtin_fmaf(b, row[LW_IS_ROW(r, lane)], st.acc[tt][r]);
+				st.acc[tt][r] = __builtin_fmaf(b, row[LW_MFMA32_ROW(r, lane)], st.acc[tt][r]);
 		}
 	}
 }
 
 // ---- y of the pass into LDS, [sample of the pass][frame]
-LW_IS_FN void lw_is_put_y(const LwIstftArgs &a, uint32_t pass, uint32_t tid, float *lds, const LwIsLane &st)
+LW_LANES_FN void lw_is_put_y(const LwIstftArgs &a, uint32_t pass, uint32_t tid, float *lds, const LwIsLane &st)
 {
 	const uint32_t lane = tid & 63u, wave = tid >> 6, f = lane & 31u;
 #pragma unroll
@@ -196,12 +191,12 @@ LW_IS_FN void lw_is_put_y(const LwIstftArgs &a, uint32_t pass, uint32_t tid, flo
 			continue;
 #pragma unroll
 		for (uint32_t r = 0; r < 16u; r++)
-			lds[LW_IS_LDS_Y + (wave * 64u + tt * 32u + LW_IS_ROW(r, lane)) * LW_IS_YS + f] = st.acc[tt][r];
+			lds[LW_IS_LDS_Y + (wave * 64u + tt * 32u + LW_MFMA32_ROW(r, lane)) * LW_IS_YS + f] = st.acc[tt][r];
 	}
 }
 
 // ---- overlap-add: what the pass holds for each owned sample, t ascending, one rounded add each
-LW_IS_FN void lw_is_add(const LwIstftArgs &a, const LwIsTile &t, uint32_t pass, uint32_t tid, float *lds)
+LW_LANES_FN void lw_is_add(const LwIstftArgs &a, const LwIsTile &t, uint32_t pass, uint32_t tid, float *lds)
 {
 	const uint32_t k0 = pass * LW_IS_COLS, k1 = k0 + LW_IS_COLS < a.win_length ? k0 + LW_IS_COLS : a.win_length;
 	for (uint32_t i = tid; i < t.span; i += LW_IS_THREADS) {
@@ -217,7 +212,7 @@ LW_IS_FN void lw_is_add(const LwIstftArgs &a, const LwIsTile &t, uint32_t pass, 
 }
 
 // ---- end: envelope, division, store.  Exactly the samples n = p - pad in [0, out_len) of the span are written
-LW_IS_FN void lw_is_finish(const LwIstftArgs &a, const LwIsTile &t, uint32_t tid, const float *lds)
+LW_LANES_FN void lw_is_finish(const LwIstftArgs &a, const LwIsTile &t, uint32_t tid, const float *lds)
 {
 	for (uint32_t i = tid; i < t.span; i += LW_IS_THREADS) {
 		const uint64_t p = t.s0 + i;
@@ -236,7 +231,7 @@ LW_IS_FN void lw_is_finish(const LwIstftArgs &a, const LwIsTile &t, uint32_t tid
 	}
 }
 
-#ifndef LW_ISTFT_HOST
+#ifndef LW_KERNEL_HOST
 
 template <int ROUTE> __global__ void __launch_bounds__(LW_IS_THREADS) k_istft(LwIstftArgs a)
 {
@@ -291,4 +286,4 @@ hipError_t lw_launch_istft(const LwIstftArgs &a, int route, uint32_t tiles, uint
 	return hipErrorInvalidValue;
 }
 
-#endif // LW_ISTFT_HOST
+#endif // LW_KERNEL_HOST

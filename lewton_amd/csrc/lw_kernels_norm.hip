@@ -23,55 +23,34 @@
 // line written.  tests/san/norm_host.cpp compiles this file for the host (LW_NORM_HOST) and runs it workgroup by workgroup.
 #include "lw_norm.hpp"
 
-#ifdef LW_NORM_HOST
-#define LW_NM_FN static inline
-#else
+#ifndef LW_KERNEL_HOST
 #include "lw_kernels.hpp"
-#define LW_NM_FN __device__ __forceinline__
 #endif
 
-struct alignas(16) LwNmF4 {
-	float v[4];
-};
-typedef float LwNmV4 __attribute__((vector_size(16)));
+static_assert(LW_NM_WAVES == LW_LANES_WAVES, "lw_lanes.hpp's plans and loops count four waves to a workgroup");
 
-// ---- the tree.  On the device every lane brings its entry and leaves with the wave's; the host build runs a wave at a time
-// (lane is 0) and folds the 64 entries as the contract writes it, t[j] = t[2j] + t[2j + 1]
-template <class F>
-LW_NM_FN LwNormTriple lw_nm_wave_tree(uint32_t lane, F entry)
+// ---- a triple's way through lw_wave_tree (lw_wave_add: lw_norm.hpp)
+#ifndef LW_KERNEL_HOST
+LW_LANES_FN LwNormTriple lw_wave_xor(const LwNormTriple &t, int o)
 {
-#ifdef LW_NORM_HOST
-	LwNormTriple t[LW_NM_GROUP];
-	for (uint32_t l = 0; l < LW_NM_GROUP; l++)
-		t[l] = entry(l);
-	for (uint32_t n = LW_NM_GROUP / 2; n; n >>= 1)
-		for (uint32_t j = 0; j < n; j++)
-			t[j] = lw_nm_add(t[2 * j], t[2 * j + 1]);
-	(void)lane;
-	return t[0];
-#else
-	LwNormTriple t = entry(lane);
-#pragma unroll
-	for (int o = 1; o < 64; o <<= 1) {
-		LwNormTriple u;
-		u.s1 = __shfl_xor(t.s1, o, 64), u.s2 = __shfl_xor(t.s2, o, 64), u.pk = (uint32_t)__shfl_xor((int)t.pk, o, 64), u.pad_ = 0;
-		t = lw_nm_add(t, u);
-	}
-	return t;
-#endif
+	LwNormTriple u;
+	u.s1 = __shfl_xor(t.s1, o, 64), u.s2 = __shfl_xor(t.s2, o, 64), u.pk = (uint32_t)__shfl_xor((int)t.pk, o, 64), u.pad_ = 0;
+	return u;
 }
+#endif
 
-// ---- k_norm_sum: lane `lane`'s share of chunk c of the line at element `at`: elements 4 lane .. 4 lane + 3 of the chunk
-LW_NM_FN LwNormTriple lw_nm_chunk_lane(const LwNormArgs &a, uint64_t at, uint64_t n, uint32_t c, uint32_t lane)
+// ---- k_norm_sum: lane `lane`'s share of chunk c of the line at element `at`: elements 4 lane .. 4 lane + 3 of the chunk.  (This
+// load and lw_kernels_vad.hip's stay two: the triple needs the floats again, and one function for both changed either kernel.)
+LW_LANES_FN LwNormTriple lw_nm_chunk_lane(const LwNormArgs &a, uint64_t at, uint64_t n, uint32_t c, uint32_t lane)
 {
-	const uint64_t e0 = (uint64_t)c * LW_NM_CHUNK + lane * 4u;
-	LwNmF4 x = {{0.0f, 0.0f, 0.0f, 0.0f}};
+	const uint64_t e0 = (uint64_t)c * LW_SUM_CHUNK + lane * 4u;
+	LwF4 x = {{0.0f, 0.0f, 0.0f, 0.0f}};
 	if (e0 + 4u <= n) {
 		const float *s = a.src + at + e0;
 		if ((((uintptr_t)a.src >> 2) + at + e0) & 3u)
 			x.v[0] = s[0], x.v[1] = s[1], x.v[2] = s[2], x.v[3] = s[3];
 		else { // ONE 16-byte load (as a vector: four float members the compiler merges with the branch above into 4-byte loads)
-			const LwNmV4 q = *(const LwNmV4 *)s;
+			const LwV4 q = *(const LwV4 *)s;
 			x.v[0] = q[0], x.v[1] = q[1], x.v[2] = q[2], x.v[3] = q[3];
 		}
 	} else {
@@ -93,7 +72,7 @@ LW_NM_FN LwNormTriple lw_nm_chunk_lane(const LwNormArgs &a, uint64_t at, uint64_
 }
 
 // one wave's slots of workgroup bx of row bz
-LW_NM_FN void lw_nm_sum_wave(const LwNormArgs &a, uint32_t bx, uint32_t bz, uint32_t wave, uint32_t lane)
+LW_LANES_FN void lw_nm_sum_wave(const LwNormArgs &a, uint32_t bx, uint32_t bz, uint32_t wave, uint32_t lane)
 {
 	const uint64_t row = (uint64_t)a.row0 + bz, lines = (uint64_t)a.ch * a.F, slots = lines * a.plan.sum_chunks;
 	const LwNormRow r = a.rows[row];
@@ -104,20 +83,20 @@ LW_NM_FN void lw_nm_sum_wave(const LwNormArgs &a, uint32_t bx, uint32_t bz, uint
 		if (c >= r.chunks)
 			continue;
 		const uint64_t at = (row * lines + line) * a.line_el;
-		const LwNormTriple t = lw_nm_wave_tree(lane, [&](uint32_t l) { return lw_nm_chunk_lane(a, at, r.n, c, l); });
+		const LwNormTriple t = lw_wave_tree<LwNormTriple>(lane, [&](uint32_t l) { return lw_nm_chunk_lane(a, at, r.n, c, l); });
 		if (lane == 0)
 			a.part[r.part_at + line * r.chunks + c] = t;
 	}
 }
 
 // ---- k_norm_fold
-LW_NM_FN LwNormTriple lw_nm_entry(const LwNormTriple *list, uint64_t len, uint64_t i)
+LW_LANES_FN LwNormTriple lw_nm_entry(const LwNormTriple *list, uint64_t len, uint64_t i)
 {
 	return i < len ? list[i] : LwNormTriple{0.0, 0.0, 0u, 0u};
 }
 
 // the scope's scalars from its triple, into their two places (one lane)
-LW_NM_FN void lw_nm_scope_out(const LwNormArgs &a, uint64_t row, uint32_t scope, uint64_t n, const LwNormTriple &t)
+LW_LANES_FN void lw_nm_scope_out(const LwNormArgs &a, uint64_t row, uint32_t scope, uint64_t n, const LwNormTriple &t)
 {
 	double m, g;
 	lw_norm_scalars_value(a.center, a.scale, a.eps, a.target, t.s1, t.s2, __builtin_bit_cast(float, t.pk), (uint64_t)a.plan.scope_lines * n, m, g);
@@ -128,14 +107,14 @@ LW_NM_FN void lw_nm_scope_out(const LwNormArgs &a, uint64_t row, uint32_t scope,
 }
 
 // the scope's list, or nothing to fold: plain, or an empty row (lw_norm_scalars_value makes m = +0.0, g = 1.0 of N = 0)
-LW_NM_FN const LwNormTriple *lw_nm_scope_list(const LwNormArgs &a, const LwNormRow &r, uint32_t scope, uint64_t &len)
+LW_LANES_FN const LwNormTriple *lw_nm_scope_list(const LwNormArgs &a, const LwNormRow &r, uint32_t scope, uint64_t &len)
 {
 	len = a.plain ? 0u : (uint64_t)a.plan.scope_lines * r.chunks;
 	return len ? a.part + r.part_at + scope * len : nullptr;
 }
 
 // a wave per scope: every list has at most 64 entries
-LW_NM_FN void lw_nm_fold_wave(const LwNormArgs &a, uint32_t bx, uint32_t bz, uint32_t wave, uint32_t lane)
+LW_LANES_FN void lw_nm_fold_wave(const LwNormArgs &a, uint32_t bx, uint32_t bz, uint32_t wave, uint32_t lane)
 {
 	const uint64_t row = (uint64_t)a.row0 + bz;
 	const uint32_t scope = bx * LW_NM_WAVES + wave;
@@ -148,49 +127,37 @@ LW_NM_FN void lw_nm_fold_wave(const LwNormArgs &a, uint32_t bx, uint32_t bz, uin
 	if (len == 1)
 		t = list[0];
 	else if (len > 1)
-		t = lw_nm_wave_tree(lane, [&](uint32_t l) { return lw_nm_entry(list, len, l); });
+		t = lw_wave_tree<LwNormTriple>(lane, [&](uint32_t l) { return lw_nm_entry(list, len, l); });
 	if (lane == 0)
 		lw_nm_scope_out(a, row, scope, len ? r.n : 0u, t);
 }
 
-// a workgroup per scope.  The lists of the levels: the scope's part of a.part, then in turn the two halves of its scratch,
-// ceil(longest / 64) and ceil(longest / 4096) triples (level 3's list is no longer than level 1's, level 4's than level 2's)
-struct LwNmLevels {
-	const LwNormTriple *in;
-	LwNormTriple *out, *other;
-	uint64_t len, n;
+// a workgroup per scope: the levels of lw_lanes.hpp over the scope's part of a.part and fold_scratch triples of its own
+struct LwNmLevels : LwLevels<LwNormTriple> {
+	uint64_t n;
 };
 
-LW_NM_FN void lw_nm_levels(const LwNormArgs &a, uint32_t bx, uint32_t bz, LwNmLevels &v)
+LW_LANES_FN void lw_nm_levels(const LwNormArgs &a, uint32_t bx, uint32_t bz, LwNmLevels &v)
 {
 	const uint64_t row = (uint64_t)a.row0 + bz;
 	const LwNormRow r = a.rows[row];
-	v.in = lw_nm_scope_list(a, r, bx, v.len);
-	v.n = v.len ? r.n : 0u;
-	v.out = a.scratch + (row * a.plan.scopes + bx) * a.plan.fold_scratch;
-	v.other = v.out + ((uint64_t)a.plan.scope_lines * a.plan.sum_chunks + 63u) / 64u;
+	uint64_t len;
+	const LwNormTriple *list = lw_nm_scope_list(a, r, bx, len);
+	lw_levels(v, list, len, a.scratch + (row * a.plan.scopes + bx) * a.plan.fold_scratch, (uint64_t)a.plan.scope_lines * a.plan.sum_chunks);
+	v.n = len ? r.n : 0u;
 }
 
-// one wave's groups of one level: group j of the list -> entry j of the next
-LW_NM_FN void lw_nm_level_wave(const LwNmLevels &v, uint32_t wave, uint32_t lane)
+LW_LANES_FN void lw_nm_level_wave(const LwNmLevels &v, uint32_t wave, uint32_t lane) // one wave's groups of one level
 {
-	const uint64_t groups = (v.len + LW_NM_GROUP - 1u) / LW_NM_GROUP;
-	for (uint64_t j = wave; j < groups; j += LW_NM_WAVES) {
-		const LwNormTriple t = lw_nm_wave_tree(lane, [&](uint32_t l) { return lw_nm_entry(v.in, v.len, j * LW_NM_GROUP + l); });
-		if (lane == 0)
-			v.out[j] = t;
-	}
+	lw_level_wave(v, wave, lane);
 }
 
-// ... and behind the level's barrier
-LW_NM_FN void lw_nm_level_next(LwNmLevels &v)
+LW_LANES_FN void lw_nm_level_next(LwNmLevels &v) // ... and behind the level's barrier
 {
-	LwNormTriple *was = v.out;
-	v.len = (v.len + LW_NM_GROUP - 1u) / LW_NM_GROUP;
-	v.in = was, v.out = v.other, v.other = was;
+	lw_level_next(v);
 }
 
-LW_NM_FN void lw_nm_levels_out(const LwNormArgs &a, uint32_t bx, uint32_t bz, const LwNmLevels &v)
+LW_LANES_FN void lw_nm_levels_out(const LwNormArgs &a, uint32_t bx, uint32_t bz, const LwNmLevels &v)
 {
 	lw_nm_scope_out(a, (uint64_t)a.row0 + bz, bx, v.n, v.len ? v.in[0] : LwNormTriple{0.0, 0.0, 0u, 0u});
 }
@@ -203,7 +170,7 @@ struct LwNmTile { // what a workgroup works on; the same for all its lanes
 	uint64_t run0;   // first run of the tile
 };
 
-LW_NM_FN void lw_nm_tile(const LwNormArgs &a, uint32_t bx, uint32_t by, uint32_t bz, LwNmTile &t)
+LW_LANES_FN void lw_nm_tile(const LwNormArgs &a, uint32_t bx, uint32_t by, uint32_t bz, LwNmTile &t)
 {
 	const uint64_t row = (uint64_t)a.row0 + bz;
 	const LwNormRow r = a.rows[row];
@@ -214,34 +181,33 @@ LW_NM_FN void lw_nm_tile(const LwNormArgs &a, uint32_t bx, uint32_t by, uint32_t
 }
 
 // one run for one lane
-LW_NM_FN void lw_nm_run(const LwNormArgs &a, const LwNmTile &t, uint32_t by, uint32_t run, uint32_t lane)
+LW_LANES_FN void lw_nm_run(const LwNormArgs &a, const LwNmTile &t, uint32_t by, uint32_t run, uint32_t lane)
 {
-	const uint32_t line = run / a.plan.runs_per_line, idx = run % a.plan.runs_per_line;
-	const uint64_t at = t.ch_at + (uint64_t)line * a.line_el;
-	const uint32_t sd = (uint32_t)(((uintptr_t)a.dst >> 2) + at) & 3u, ss = (uint32_t)(((uintptr_t)a.src >> 2) + at) & 3u; // (src may be NULL)
-	const int64_t t0 = (int64_t)(((uint64_t)idx * (LW_NM_CHUNK / 4u) + lane) * 4u) - (int64_t)sd;
+	const LwRunGroup gr = lw_run_group(a.plan.runs_per_line, a.src, a.dst, t.ch_at, a.line_el, run, lane);
+	const uint64_t at = gr.at;
+	const int64_t t0 = gr.t0;
 	if (t0 >= (int64_t)t.end)
 		return;
 	double m = 0.0, g = 1.0;
 	if (!a.plain) {
-		const uint64_t scope = a.scope == 0 ? 0u : a.scope == 1 ? by : (uint64_t)by * a.F + line;
+		const uint64_t scope = a.scope == 0 ? 0u : a.scope == 1 ? by : (uint64_t)by * a.F + gr.line;
 		m = a.sc[t.sc_at + scope * 2u], g = a.sc[t.sc_at + scope * 2u + 1u];
 	}
 	if (t0 >= 0 && (uint64_t)t0 + 4u <= t.n) { // all four are data
 		const float *s = a.src + at + t0;
-		LwNmF4 x;
-		if (sd == ss)
-			x = *(const LwNmF4 *)s;
+		LwF4 x;
+		if (gr.same)
+			x = *(const LwF4 *)s;
 		else
 			x.v[0] = s[0], x.v[1] = s[1], x.v[2] = s[2], x.v[3] = s[3];
 #pragma unroll
 		for (int j = 0; j < 4; j++)
 			x.v[j] = lw_norm_apply_value(x.v[j], m, g);
-		*(LwNmF4 *)(a.dst + at + t0) = x;
+		*(LwF4 *)(a.dst + at + t0) = x;
 		return;
 	}
 	if (t0 >= 0 && (uint64_t)t0 >= t.n && (uint64_t)t0 + 4u <= t.end) { // all four are fill
-		*(LwNmF4 *)(a.dst + at + t0) = LwNmF4{{0.0f, 0.0f, 0.0f, 0.0f}};
+		*(LwF4 *)(a.dst + at + t0) = LwF4{{0.0f, 0.0f, 0.0f, 0.0f}};
 		return;
 	}
 	for (int j = 0; j < 4; j++) { // the line's head, the tail of the data, the tail of the fill
@@ -253,7 +219,7 @@ LW_NM_FN void lw_nm_run(const LwNormArgs &a, const LwNmTile &t, uint32_t by, uin
 }
 
 // the lane's runs of the tile
-LW_NM_FN void lw_nm_tile_apply(const LwNormArgs &a, const LwNmTile &t, uint32_t by, uint32_t tid)
+LW_LANES_FN void lw_nm_tile_apply(const LwNormArgs &a, const LwNmTile &t, uint32_t by, uint32_t tid)
 {
 	const uint32_t lane = tid & 63u, wave = tid >> 6;
 	for (uint32_t i = 0; i < a.plan.per_wave; i++) {
@@ -263,7 +229,7 @@ LW_NM_FN void lw_nm_tile_apply(const LwNormArgs &a, const LwNmTile &t, uint32_t 
 	}
 }
 
-#ifndef LW_NORM_HOST
+#ifndef LW_KERNEL_HOST
 
 __global__ void __launch_bounds__(LW_NM_THREADS) k_norm_sum(LwNormArgs a)
 {
@@ -324,4 +290,4 @@ hipError_t lw_launch_norm_apply(const LwNormArgs &a, uint32_t n_rows, hipStream_
 	return lw_launch_k(k_norm_apply, dim3(a.plan.tiles, a.ch, n_rows), dim3(LW_NM_THREADS), 0, st, a);
 }
 
-#endif // LW_NORM_HOST
+#endif // LW_KERNEL_HOST

@@ -19,14 +19,10 @@
 // workgroup, the phases in the kernel's order.
 #include "lw_pack.hpp"
 
-#ifdef LW_PACK_HOST
+#ifdef LW_KERNEL_HOST
 #include <cstring>
-#define LW_PK_FN static inline
-#define LW_PK_RESTRICT
 #else
 #include "lw_kernels.hpp"
-#define LW_PK_FN __device__ __forceinline__
-#define LW_PK_RESTRICT __restrict__
 #endif
 
 struct LwPkTile { // what a workgroup works on; the same for all its lanes
@@ -42,7 +38,7 @@ struct LwPkTile { // what a workgroup works on; the same for all its lanes
 };
 
 // false: the tile lies at or beyond the row's fill_end, nothing to do
-LW_PK_FN bool lw_pk_tile(const LwPackArgs &a, uint32_t bx, uint32_t by, uint32_t bz, LwPkTile &t)
+LW_LANES_FN bool lw_pk_tile(const LwPackArgs &a, uint32_t bx, uint32_t by, uint32_t bz, LwPkTile &t)
 {
 	const uint64_t row = (uint64_t)a.row0 + bz;
 	const LwPackRow r = a.rows[row];
@@ -64,7 +60,7 @@ LW_PK_FN bool lw_pk_tile(const LwPackArgs &a, uint32_t bx, uint32_t by, uint32_t
 // E consecutive converted elements from element `at` of the destination: one store of 16 bytes (E = 4: f32; E = 8: two to a
 // dword), or of one element (E = 1)
 template <int E>
-LW_PK_FN void lw_pk_put(const LwPackArgs &a, void *LW_PK_RESTRICT dst, uint64_t at, const uint32_t (&c)[E])
+LW_LANES_FN void lw_pk_put(const LwPackArgs &a, void *LW_LANES_RESTRICT dst, uint64_t at, const uint32_t (&c)[E])
 {
 	if (E == 1) {
 		if (a.dtype == LW_PK_F32)
@@ -77,7 +73,7 @@ LW_PK_FN void lw_pk_put(const LwPackArgs &a, void *LW_PK_RESTRICT dst, uint64_t 
 #pragma unroll
 	for (int i = 0; i < 4; i++)
 		w[i] = E == 4 ? c[i] : (c[(2 * i) % E] | (c[(2 * i + 1) % E] << 16));
-#ifdef LW_PACK_HOST
+#ifdef LW_KERNEL_HOST
 	memcpy((char *)dst + at * (E == 4 ? 4u : 2u), w, 16);
 #else
 	*(uint4 *)((char *)dst + at * (E == 4 ? 4u : 2u)) = make_uint4(w[0], w[1], w[2], w[3]);
@@ -85,7 +81,7 @@ LW_PK_FN void lw_pk_put(const LwPackArgs &a, void *LW_PK_RESTRICT dst, uint64_t 
 }
 
 // ---- the mask of the tile's frames: the lanes of channel 0
-LW_PK_FN void lw_pk_mask(const LwPackArgs &a, const LwPkTile &t, uint8_t *LW_PK_RESTRICT mask, uint32_t tid)
+LW_LANES_FN void lw_pk_mask(const LwPackArgs &a, const LwPkTile &t, uint8_t *LW_LANES_RESTRICT mask, uint32_t tid)
 {
 	if (tid < t.fill_hi)
 		mask[t.mask_at + t.u0 + tid] = tid < t.nu ? 1u : 0u;
@@ -93,7 +89,7 @@ LW_PK_FN void lw_pk_mask(const LwPackArgs &a, const LwPkTile &t, uint8_t *LW_PK_
 
 // ---- pad into frames [fill_lo, fill_hi) of the tile: one contiguous run of the destination
 template <int E>
-LW_PK_FN void lw_pk_fill(const LwPackArgs &a, const LwPkTile &t, void *LW_PK_RESTRICT dst, uint32_t tid)
+LW_LANES_FN void lw_pk_fill(const LwPackArgs &a, const LwPkTile &t, void *LW_LANES_RESTRICT dst, uint32_t tid)
 {
 	uint32_t c[E];
 #pragma unroll
@@ -106,7 +102,7 @@ LW_PK_FN void lw_pk_fill(const LwPackArgs &a, const LwPkTile &t, void *LW_PK_RES
 }
 
 // ---- lines f0 .. f0 + G - 1 of the tile's span into the image: wave w takes lines w, w + 4, ..., its lanes the frames
-LW_PK_FN void lw_pk_load(const LwPackArgs &a, const LwPkTile &t, const uint32_t *LW_PK_RESTRICT src, uint32_t *img, uint32_t f0, uint32_t G,
+LW_LANES_FN void lw_pk_load(const LwPackArgs &a, const LwPkTile &t, const uint32_t *LW_LANES_RESTRICT src, uint32_t *img, uint32_t f0, uint32_t G,
 		uint32_t tid)
 {
 	for (uint32_t s = tid & 63u; s < t.span; s += 64u) {
@@ -122,7 +118,7 @@ LW_PK_FN void lw_pk_load(const LwPackArgs &a, const LwPkTile &t, const uint32_t 
 
 // ---- the image into the destination: unit L = (q = L % (32 / E), p = L / (32 / E)), p = (u, k) = (p / W, p % W)
 template <int E>
-LW_PK_FN void lw_pk_store(const LwPackArgs &a, const LwPkTile &t, const uint32_t *img, void *LW_PK_RESTRICT dst, uint32_t f0, uint32_t G, uint32_t tid)
+LW_LANES_FN void lw_pk_store(const LwPackArgs &a, const LwPkTile &t, const uint32_t *img, void *LW_LANES_RESTRICT dst, uint32_t f0, uint32_t G, uint32_t tid)
 {
 	const uint32_t Q = LW_PK_GROUP / (uint32_t)E, units = t.nu * a.W * Q;
 	for (uint32_t L = tid; L < units; L += LW_PK_THREADS) {
@@ -165,7 +161,7 @@ LW_PK_FN void lw_pk_store(const LwPackArgs &a, const LwPkTile &t, const uint32_t
 	}
 }
 
-#ifndef LW_PACK_HOST
+#ifndef LW_KERNEL_HOST
 
 template <int E>
 __device__ __forceinline__ void lw_pk_block(const LwPackArgs &a, const LwPkTile &t, const uint32_t *__restrict__ src, void *__restrict__ dst,
@@ -214,4 +210,4 @@ hipError_t lw_launch_pack(const LwPackArgs &a, const float *src, void *dst, uint
 	return lw_launch_k(k_pack, dim3(tiles, a.ch, n_rows), dim3(LW_PK_THREADS), (size_t)a.plan.lds, st, a, bits, dst, mask);
 }
 
-#endif // LW_PACK_HOST
+#endif // LW_KERNEL_HOST

@@ -27,11 +27,9 @@
 // arguments, so tests/san/resample_host.cpp compiles this file for the host (LW_RESAMPLE_HOST) and runs it lane by lane.
 #include "lw_resample.hpp"
 
-#ifdef LW_RESAMPLE_HOST
-#define LW_RS_FN static inline
-#else
+#include "lw_lanes.hpp"
+#ifndef LW_KERNEL_HOST
 #include "lw_kernels.hpp"
-#define LW_RS_FN __device__ __forceinline__
 #endif
 
 struct LwRsTile { // what a workgroup works on; the same for all its lanes
@@ -42,7 +40,7 @@ struct LwRsTile { // what a workgroup works on; the same for all its lanes
 	uint64_t d_at; // ... of the destination row and channel
 };
 
-LW_RS_FN bool lw_rs_tile(const LwResampleArgs &a, uint32_t tile_outputs, uint32_t bx, uint32_t by, uint32_t bz, LwRsTile &t)
+LW_LANES_FN bool lw_rs_tile(const LwResampleArgs &a, uint32_t tile_outputs, uint32_t bx, uint32_t by, uint32_t bz, LwRsTile &t)
 {
 	const LwResampleRow r = a.rows[(uint64_t)a.row0 + bz];
 	t.len = r.len, t.out_len = r.out_len;
@@ -57,7 +55,7 @@ LW_RS_FN bool lw_rs_tile(const LwResampleArgs &a, uint32_t tile_outputs, uint32_
 
 // x[i] of the tile's row and channel, +0.0 outside [0, len): the load goes to a clamped index (len >= 1 wherever a tile exists), so
 // it is branch-free, never leaves [0, len), and what lies between len and the capacity is never fetched
-LW_RS_FN float lw_rs_x(const LwResampleArgs &a, const LwRsTile &t, int64_t i)
+LW_LANES_FN float lw_rs_x(const LwResampleArgs &a, const LwRsTile &t, int64_t i)
 {
 	const bool in = i >= 0 && (uint64_t)i < t.len;
 	const uint64_t c = i < 0 ? 0 : (uint64_t)i < t.len ? (uint64_t)i : t.len - 1;
@@ -70,7 +68,7 @@ struct alignas(16) LwRsF4 {
 };
 
 // ---- stage: span (and table) into LDS; lds = [span][new * K]; eight independent loads in flight per lane
-template <int ROUTE> LW_RS_FN void lw_rs_stage(const LwResampleArgs &a, const LwRsTile &t, uint32_t span, uint32_t tid, uint32_t nthreads, float *lds)
+template <int ROUTE> LW_LANES_FN void lw_rs_stage(const LwResampleArgs &a, const LwRsTile &t, uint32_t span, uint32_t tid, uint32_t nthreads, float *lds)
 {
 	for (uint32_t s0 = tid; s0 < span; s0 += 8u * nthreads) {
 		float v[8];
@@ -111,7 +109,7 @@ template <int ROUTE> LW_RS_FN void lw_rs_stage(const LwResampleArgs &a, const Lw
 // U is a multiple of new, so they share n mod new (which selects the taps) and their inputs lie M * orig apart.  Returns n, its
 // n mod new and the index of x[base(n) - W] in the span.  Consecutive lanes take consecutive outputs: their x reads are
 // orig / new words apart.
-LW_RS_FN uint64_t lw_rs_unit(const LwResampleArgs &a, const LwRsTile &t, uint32_t u, uint32_t &i, uint32_t &x_at)
+LW_LANES_FN uint64_t lw_rs_unit(const LwResampleArgs &a, const LwRsTile &t, uint32_t u, uint32_t &i, uint32_t &x_at)
 {
 	const uint32_t m = u / a.new_;
 	i = u - m * a.new_;
@@ -120,7 +118,7 @@ LW_RS_FN uint64_t lw_rs_unit(const LwResampleArgs &a, const LwRsTile &t, uint32_
 }
 
 // ---- fold: J outputs of one phase per lane and pass
-template <int ROUTE, int J> LW_RS_FN void lw_rs_fold(const LwResampleArgs &a, const LwRsTile &t, uint32_t span, uint32_t tid, uint32_t nthreads, const float *lds)
+template <int ROUTE, int J> LW_LANES_FN void lw_rs_fold(const LwResampleArgs &a, const LwRsTile &t, uint32_t span, uint32_t tid, uint32_t nthreads, const float *lds)
 {
 	const uint32_t nw = a.new_, K = a.k_taps;
 	const float *hs = ROUTE == LW_RS_ROUTE_LDS ? lds + span : a.taps;
@@ -158,14 +156,14 @@ template <int ROUTE, int J> LW_RS_FN void lw_rs_fold(const LwResampleArgs &a, co
 }
 
 // ---- route GLOBAL: one output per lane, nothing staged (tile = nthreads outputs, any start)
-LW_RS_FN int64_t lw_rs_global_index(const LwResampleArgs &a, uint64_t n, uint32_t &i) // base(n) - W and n mod new
+LW_LANES_FN int64_t lw_rs_global_index(const LwResampleArgs &a, uint64_t n, uint32_t &i) // base(n) - W and n mod new
 {
 	const uint64_t q = n / a.new_;
 	i = (uint32_t)(n - q * a.new_);
 	return (int64_t)(q * a.orig + (uint64_t)i * a.orig / a.new_) - (int64_t)a.half_width;
 }
 
-LW_RS_FN void lw_rs_fold_global(const LwResampleArgs &a, const LwRsTile &t, uint32_t tid)
+LW_LANES_FN void lw_rs_fold_global(const LwResampleArgs &a, const LwRsTile &t, uint32_t tid)
 {
 	const uint64_t n = t.n0 + tid;
 	if (n >= t.out_len)
@@ -182,7 +180,7 @@ LW_RS_FN void lw_rs_fold_global(const LwResampleArgs &a, const LwRsTile &t, uint
 }
 
 // ---- route COPY (orig == new): bits of [0, len), four per lane
-LW_RS_FN void lw_rs_copy(const LwResampleArgs &a, const LwRsTile &t, uint32_t tid, uint32_t nthreads)
+LW_LANES_FN void lw_rs_copy(const LwResampleArgs &a, const LwRsTile &t, uint32_t tid, uint32_t nthreads)
 {
 	const uint32_t *s = (const uint32_t *)a.src;
 	uint32_t *d = (uint32_t *)a.dst;
@@ -193,7 +191,7 @@ LW_RS_FN void lw_rs_copy(const LwResampleArgs &a, const LwRsTile &t, uint32_t ti
 	}
 }
 
-#ifndef LW_RESAMPLE_HOST
+#ifndef LW_KERNEL_HOST
 
 template <int ROUTE, int J> __global__ void __launch_bounds__(LW_RS_THREADS) k_resample(LwResampleArgs a, uint32_t span)
 {
@@ -254,4 +252,4 @@ hipError_t lw_launch_resample(const LwResampleArgs &a, const LwResamplePlan &p, 
 	return hipErrorInvalidValue;
 }
 
-#endif // LW_RESAMPLE_HOST
+#endif // LW_KERNEL_HOST

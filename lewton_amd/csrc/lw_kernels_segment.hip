@@ -23,12 +23,12 @@
 // kernels' order.
 #include "lw_segment.hpp"
 
-#ifdef LW_SEGMENT_HOST
-#define LW_SG_FN static inline
-#else
+#include "lw_lanes.hpp"
+#ifndef LW_KERNEL_HOST
 #include "lw_kernels.hpp"
-#define LW_SG_FN __device__ __forceinline__
 #endif
+
+static_assert(LW_SG_WAVES == LW_LANES_WAVES, "lw_lanes.hpp's loops count four waves to a workgroup");
 
 struct LwSgLds { // the LDS of a workgroup
 	uint64_t bits[2][LW_SG_WORDS]; // the passes alternate: bit j of a list is frame t0 - halo + j
@@ -52,7 +52,7 @@ struct LwSgTile { // what a workgroup works on; the same for all its lanes
 	uint64_t cnt_at;  // entry of the row and channel in d_counts; times seg_capacity: its first span
 };
 
-LW_SG_FN void lw_sg_tile(const LwSegmentArgs &a, uint32_t tile_i, uint32_t by, uint32_t bz, LwSgTile &t)
+LW_LANES_FN void lw_sg_tile(const LwSegmentArgs &a, uint32_t tile_i, uint32_t by, uint32_t bz, LwSgTile &t)
 {
 	const uint64_t row = (uint64_t)a.row0 + bz;
 	const LwSegmentRow r = a.rows[row];
@@ -70,176 +70,108 @@ LW_SG_FN void lw_sg_tile(const LwSegmentArgs &a, uint32_t tile_i, uint32_t by, u
 }
 
 // what of a tile's work is owed (the same in every lane)
-LW_SG_FN bool lw_sg_owes_count(const LwSegmentArgs &a, const LwSgTile &t)
+LW_LANES_FN bool lw_sg_owes_count(const LwSegmentArgs &a, const LwSgTile &t)
 {
 	return a.d_counts && t.tile_i == 0;
 }
-LW_SG_FN bool lw_sg_owes_spans(const LwSegmentArgs &a, const LwSgTile &t)
+LW_LANES_FN bool lw_sg_owes_spans(const LwSegmentArgs &a, const LwSgTile &t)
 {
 	return a.d_spans && t.nt;
 }
-LW_SG_FN bool lw_sg_owes_smooth(const LwSegmentArgs &a, const LwSgTile &t)
+LW_LANES_FN bool lw_sg_owes_smooth(const LwSegmentArgs &a, const LwSgTile &t)
 {
 	return a.d_smooth && t.t0 < t.fill_end;
 }
-LW_SG_FN bool lw_sg_passes(const LwSegmentArgs &a, const LwSgTile &t) // the rule is evaluated: the tile holds a frame somebody wants
+LW_LANES_FN bool lw_sg_passes(const LwSegmentArgs &a, const LwSgTile &t) // the rule is evaluated: the tile holds a frame somebody wants
 {
 	return t.nt && (a.d_spans || a.d_smooth);
 }
 
-// ---- the wave's ballot: bit l is lane l's decision.  The host build runs a wave at a time (lane is 0)
+// ---- the set bits of [lo, hi) of a word list, which may be empty (the searches: lw_lanes.hpp, in this file's index type)
+LW_LANES_FN uint32_t lw_sg_count(const uint64_t *b, int32_t lo, int32_t hi)
+{
+	return lo < hi ? lw_bits_count<int32_t>(b, lo, hi, 0u) : 0u;
+}
+
+// ---- the passes: one wave's words of a list (lw_bits_fill).  decision(j, f) is asked for the bits of the window that are frames of the line
 template <class P>
-LW_SG_FN uint64_t lw_sg_ballot(uint32_t lane, P decision)
+LW_LANES_FN void lw_sg_pass(const LwSgTile &t, uint64_t *out, uint32_t wave, uint32_t lane, P decision)
 {
-#ifdef LW_SEGMENT_HOST
-	uint64_t w = 0;
-	for (uint32_t l = 0; l < 64u; l++)
-		w |= (uint64_t)(decision(l) ? 1u : 0u) << l;
-	(void)lane;
-	return w;
-#else
-	return __ballot(decision(lane));
-#endif
+	lw_bits_fill(out, t.span, t.words, (int64_t)t.t0 - (int64_t)t.halo, t.n, wave, lane, decision);
 }
 
-// ---- searches in a word list; lo and hi are bit numbers of the window, inv is ~0 to look for unset bits
-LW_SG_FN bool lw_sg_bit(const uint64_t *b, int32_t j)
-{
-	return (b[j >> 6] >> (j & 63)) & 1u;
-}
-
-// the words of [lo, hi), lo < hi, masked to it
-LW_SG_FN uint64_t lw_sg_word(const uint64_t *b, int32_t w, int32_t lo, int32_t hi, uint64_t inv)
-{
-	uint64_t m = b[w] ^ inv;
-	if (w == lo >> 6)
-		m &= ~(uint64_t)0 << (lo & 63);
-	if (w == (hi - 1) >> 6 && (hi & 63))
-		m &= ((uint64_t)1 << (hi & 63)) - 1u;
-	return m;
-}
-
-LW_SG_FN int32_t lw_sg_last(const uint64_t *b, int32_t lo, int32_t hi, uint64_t inv) // the largest in [lo, hi), or -1
-{
-	if (lo >= hi)
-		return -1;
-	for (int32_t w = (hi - 1) >> 6; w >= lo >> 6; w--) {
-		const uint64_t m = lw_sg_word(b, w, lo, hi, inv);
-		if (m)
-			return w * 64 + 63 - (int32_t)__builtin_clzll(m);
-	}
-	return -1;
-}
-
-LW_SG_FN int32_t lw_sg_first(const uint64_t *b, int32_t lo, int32_t hi, uint64_t inv) // the smallest in [lo, hi), or -1
-{
-	if (lo >= hi)
-		return -1;
-	for (int32_t w = lo >> 6; w <= (hi - 1) >> 6; w++) {
-		const uint64_t m = lw_sg_word(b, w, lo, hi, inv);
-		if (m)
-			return w * 64 + (int32_t)__builtin_ctzll(m);
-	}
-	return -1;
-}
-
-LW_SG_FN uint32_t lw_sg_count(const uint64_t *b, int32_t lo, int32_t hi) // the set bits of [lo, hi)
-{
-	uint32_t c = 0;
-	if (lo < hi)
-		for (int32_t w = lo >> 6; w <= (hi - 1) >> 6; w++)
-			c += (uint32_t)__builtin_popcountll(lw_sg_word(b, w, lo, hi, 0u));
-	return c;
-}
-
-// ---- the passes: one wave's words of a list.  decision(j) is asked for the bits of the window that are frames of the line
-template <class P>
-LW_SG_FN void lw_sg_pass(const LwSgTile &t, uint64_t *out, uint32_t wave, uint32_t lane, P decision)
-{
-	const int64_t base = (int64_t)t.t0 - (int64_t)t.halo;
-	for (uint32_t w = wave; w < t.words; w += LW_SG_WAVES) {
-		const uint64_t word = lw_sg_ballot(lane, [&](uint32_t i) {
-			const uint32_t j = w * 64u + i;
-			const int64_t f = base + (int64_t)j;
-			return j < t.span && f >= 0 && (uint64_t)f < t.n && decision((int32_t)j, (uint64_t)f);
-		});
-		if (lane == 0)
-			out[w] = word;
-	}
-}
-
-LW_SG_FN void lw_sg_load(const LwSegmentArgs &a, const LwSgTile &t, LwSgLds &l, uint32_t wave, uint32_t lane)
+LW_LANES_FN void lw_sg_load(const LwSegmentArgs &a, const LwSgTile &t, LwSgLds &l, uint32_t wave, uint32_t lane)
 {
 	lw_sg_pass(t, l.bits[0], wave, lane, [&](int32_t, uint64_t f) { return a.mask[t.mask_at + f] != 0; });
 }
 
 // (each behind a barrier) bits[0] -> bits[1] -> bits[0] -> bits[1]: O is bits[1]
-LW_SG_FN void lw_sg_pad(const LwSegmentArgs &a, const LwSgTile &t, LwSgLds &l, uint32_t wave, uint32_t lane)
+LW_LANES_FN void lw_sg_pad(const LwSegmentArgs &a, const LwSgTile &t, LwSgLds &l, uint32_t wave, uint32_t lane)
 {
 	const uint64_t *m = l.bits[0];
 	const int32_t span = (int32_t)t.span;
 	lw_sg_pass(t, l.bits[1], wave, lane, [&](int32_t j, uint64_t) {
 		const int32_t lo = j - (int32_t)a.pad_offset, hi = j + (int32_t)a.pad_onset + 1;
-		return lw_sg_first(m, lo < 0 ? 0 : lo, hi > span ? span : hi, 0u) >= 0;
+		return lw_bits_first<int32_t>(m, lo < 0 ? 0 : lo, hi > span ? span : hi, 0u) >= 0;
 	});
 }
 
-LW_SG_FN void lw_sg_fill(const LwSegmentArgs &a, const LwSgTile &t, LwSgLds &l, uint32_t wave, uint32_t lane)
+LW_LANES_FN void lw_sg_fill(const LwSegmentArgs &a, const LwSgTile &t, LwSgLds &l, uint32_t wave, uint32_t lane)
 {
 	const uint64_t *p = l.bits[1];
 	const int32_t span = (int32_t)t.span, reach = (int32_t)a.min_off;
 	lw_sg_pass(t, l.bits[0], wave, lane, [&](int32_t j, uint64_t) {
-		if (lw_sg_bit(p, j))
+		if (lw_bits_bit(p, j))
 			return true;
 		if (reach < 2)
 			return false; // (a gap that holds t has a frame)
 		const int32_t lo = j - reach + 1, hi = j + reach;
-		const int32_t before = lw_sg_last(p, lo < 0 ? 0 : lo, j, 0u);
+		const int32_t before = lw_bits_last<int32_t>(p, lo < 0 ? 0 : lo, j, 0u);
 		if (before < 0)
 			return false;
-		const int32_t behind = lw_sg_first(p, j + 1, hi > span ? span : hi, 0u);
+		const int32_t behind = lw_bits_first<int32_t>(p, j + 1, hi > span ? span : hi, 0u);
 		return behind >= 0 && behind - before - 1 < reach;
 	});
 }
 
-LW_SG_FN void lw_sg_drop(const LwSegmentArgs &a, const LwSgTile &t, LwSgLds &l, uint32_t wave, uint32_t lane)
+LW_LANES_FN void lw_sg_drop(const LwSegmentArgs &a, const LwSgTile &t, LwSgLds &l, uint32_t wave, uint32_t lane)
 {
 	const uint64_t *c = l.bits[0];
 	const int32_t span = (int32_t)t.span, need = (int32_t)a.min_on;
 	lw_sg_pass(t, l.bits[1], wave, lane, [&](int32_t j, uint64_t) {
-		if (!lw_sg_bit(c, j))
+		if (!lw_bits_bit(c, j))
 			return false;
 		if (need < 2)
 			return true;
 		// the nearest unset frames either side, as far as they matter: a side without one within need - 1 frames is long enough
 		// by itself, and the window's edge counts as unset (it is, where it lies outside the line)
 		const int32_t lo = j - need + 1, hi = j + need;
-		int32_t before = lw_sg_last(c, lo < 0 ? 0 : lo, j, ~(uint64_t)0);
+		int32_t before = lw_bits_last<int32_t>(c, lo < 0 ? 0 : lo, j, ~(uint64_t)0);
 		if (before < 0)
 			before = lo <= 0 ? -1 : lo - 1;
-		int32_t behind = lw_sg_first(c, j + 1, hi > span ? span : hi, ~(uint64_t)0);
+		int32_t behind = lw_bits_first<int32_t>(c, j + 1, hi > span ? span : hi, ~(uint64_t)0);
 		if (behind < 0)
 			behind = hi >= span ? span : hi;
 		return behind - before - 1 >= need;
 	});
 }
 
-LW_SG_FN void lw_sg_edges(const LwSgTile &t, LwSgLds &l, uint32_t wave, uint32_t lane)
+LW_LANES_FN void lw_sg_edges(const LwSgTile &t, LwSgLds &l, uint32_t wave, uint32_t lane)
 {
 	const uint64_t *o = l.bits[1];
 	const int32_t h = (int32_t)t.halo, end = h + (int32_t)t.nt;
-	lw_sg_pass(t, l.starts, wave, lane, [&](int32_t j, uint64_t) { return j >= h && j < end && lw_sg_bit(o, j) && !lw_sg_bit(o, j - 1); });
-	lw_sg_pass(t, l.ends, wave, lane, [&](int32_t j, uint64_t) { return j >= h && j < end && lw_sg_bit(o, j) && !lw_sg_bit(o, j + 1); });
+	lw_sg_pass(t, l.starts, wave, lane, [&](int32_t j, uint64_t) { return j >= h && j < end && lw_bits_bit(o, j) && !lw_bits_bit(o, j - 1); });
+	lw_sg_pass(t, l.ends, wave, lane, [&](int32_t j, uint64_t) { return j >= h && j < end && lw_bits_bit(o, j) && !lw_bits_bit(o, j + 1); });
 }
 
 // (behind a barrier) the tile's starts
-LW_SG_FN uint32_t lw_sg_starts(const LwSgTile &t, const LwSgLds &l)
+LW_LANES_FN uint32_t lw_sg_starts(const LwSgTile &t, const LwSgLds &l)
 {
 	return lw_sg_count(l.starts, (int32_t)t.halo, (int32_t)(t.halo + t.nt));
 }
 
 // ---- base and K: partial sums of the row's tile counts -- those in front of the tile, all of them in tile 0
-LW_SG_FN void lw_sg_partial(const LwSegmentArgs &a, const LwSgTile &t, LwSgLds &l, uint32_t tid)
+LW_LANES_FN void lw_sg_partial(const LwSegmentArgs &a, const LwSgTile &t, LwSgLds &l, uint32_t tid)
 {
 	const uint32_t lim = t.tile_i == 0 || t.tile_i > t.n_tiles ? t.n_tiles : t.tile_i;
 	uint64_t s = 0;
@@ -249,7 +181,7 @@ LW_SG_FN void lw_sg_partial(const LwSegmentArgs &a, const LwSgTile &t, LwSgLds &
 }
 
 // (behind a barrier) sixteen lanes fold sixteen partial sums each
-LW_SG_FN void lw_sg_fold(LwSgLds &l, uint32_t tid)
+LW_LANES_FN void lw_sg_fold(LwSgLds &l, uint32_t tid)
 {
 	if (tid >= 16u)
 		return;
@@ -260,7 +192,7 @@ LW_SG_FN void lw_sg_fold(LwSgLds &l, uint32_t tid)
 }
 
 // (behind a barrier)
-LW_SG_FN uint64_t lw_sg_sum(const LwSgLds &l)
+LW_LANES_FN uint64_t lw_sg_sum(const LwSgLds &l)
 {
 	uint64_t s = 0;
 	for (uint32_t k = 0; k < 16u; k++)
@@ -269,20 +201,20 @@ LW_SG_FN uint64_t lw_sg_sum(const LwSgLds &l)
 }
 
 // ---- (behind the edges and a barrier) the lane's frames of the tile: the halves of the spans that lie in it
-LW_SG_FN void lw_sg_spans(const LwSegmentArgs &a, const LwSgTile &t, const LwSgLds &l, uint64_t base, uint32_t tid)
+LW_LANES_FN void lw_sg_spans(const LwSegmentArgs &a, const LwSgTile &t, const LwSgLds &l, uint64_t base, uint32_t tid)
 {
 	const int32_t h = (int32_t)t.halo;
 	// an end belongs to the tile of the run's last frame: a run that crosses the tile's start has started in front of it and ends here
-	const uint64_t base_ends = base - (lw_sg_bit(l.bits[1], h - 1) && lw_sg_bit(l.bits[1], h) ? 1u : 0u);
+	const uint64_t base_ends = base - (lw_bits_bit(l.bits[1], h - 1) && lw_bits_bit(l.bits[1], h) ? 1u : 0u);
 	uint64_t *spans = a.d_spans + t.cnt_at * a.seg_capacity * 2u;
 	for (uint32_t i = tid; i < t.nt; i += LW_SG_THREADS) {
 		const int32_t j = h + (int32_t)i;
-		if (lw_sg_bit(l.starts, j)) {
+		if (lw_bits_bit(l.starts, j)) {
 			const uint64_t k = base + lw_sg_count(l.starts, h, j);
 			if (k < a.seg_capacity)
 				spans[2u * k] = t.t0 + i;
 		}
-		if (lw_sg_bit(l.ends, j)) {
+		if (lw_bits_bit(l.ends, j)) {
 			const uint64_t k = base_ends + lw_sg_count(l.ends, h, j);
 			if (k < a.seg_capacity)
 				spans[2u * k + 1u] = t.t0 + i + 1u;
@@ -290,15 +222,16 @@ LW_SG_FN void lw_sg_spans(const LwSegmentArgs &a, const LwSgTile &t, const LwSgL
 	}
 }
 
-// ---- the lane's groups of four bytes of the tile's share of [0, fill_end) of the smoothed mask; passes: O is in LDS
-LW_SG_FN void lw_sg_smooth(const LwSegmentArgs &a, const LwSgTile &t, const LwSgLds &l, bool passes, uint32_t tid)
+// ---- the lane's groups of four bytes of the tile's share of [0, fill_end) of the smoothed mask; passes: O is in LDS.  (The loop
+// is lw_mask_write's, kept here: through that function the compiler no longer branches on `passes`, and k_segment's code changes.)
+LW_LANES_FN void lw_sg_smooth(const LwSegmentArgs &a, const LwSgTile &t, const LwSgLds &l, bool passes, uint32_t tid)
 {
 	const uint64_t end = t.t0 + a.tile < t.fill_end ? t.t0 + a.tile : t.fill_end;
 	if (t.t0 >= end)
 		return;
 	uint8_t *m = a.d_smooth + t.mask_at;
 	const int64_t base = (int64_t)t.t0 - (int64_t)t.halo;
-	const auto byte = [&](uint64_t f) { return passes && f < t.n && lw_sg_bit(l.bits[1], (int32_t)((int64_t)f - base)) ? 1u : 0u; };
+	const auto byte = [&](uint64_t f) { return passes && f < t.n && lw_bits_bit(l.bits[1], (int32_t)((int64_t)f - base)) ? 1u : 0u; };
 	const uint32_t head = (uint32_t)((uintptr_t)(m + t.t0) & 3u);
 	const uint32_t groups = (uint32_t)((end - t.t0 + head + 3u) / 4u);
 	for (uint32_t g = tid; g < groups; g += LW_SG_THREADS) {
@@ -317,10 +250,10 @@ LW_SG_FN void lw_sg_smooth(const LwSegmentArgs &a, const LwSgTile &t, const LwSg
 	}
 }
 
-#ifndef LW_SEGMENT_HOST
+#ifndef LW_KERNEL_HOST
 
 // the passes of a workgroup, each behind the barrier of the one before; O and the edges are complete behind the last barrier
-LW_SG_FN void lw_sg_rule(const LwSegmentArgs &a, const LwSgTile &t, LwSgLds &l)
+LW_LANES_FN void lw_sg_rule(const LwSegmentArgs &a, const LwSgTile &t, LwSgLds &l)
 {
 	const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
 	lw_sg_load(a, t, l, wave, lane);
@@ -397,4 +330,4 @@ hipError_t lw_launch_segment(const LwSegmentArgs &a, uint32_t n_rows, hipStream_
 	return lw_launch_k(k_segment, dim3(a.tiles, a.ch, n_rows), dim3(LW_SG_THREADS), 0, st, a);
 }
 
-#endif // LW_SEGMENT_HOST
+#endif // LW_KERNEL_HOST

@@ -17,13 +17,9 @@
 // host (LW_SELECT_HOST) and runs it workgroup by workgroup, the phases in the kernels' order.
 #include "lw_select.hpp"
 
-#ifdef LW_SELECT_HOST
-#define LW_SE_FN static inline
-#define LW_SE_RESTRICT
-#else
+#include "lw_lanes.hpp"
+#ifndef LW_KERNEL_HOST
 #include "lw_kernels.hpp"
-#define LW_SE_FN __device__ __forceinline__
-#define LW_SE_RESTRICT __restrict__
 #endif
 
 struct LwSeLds { // the LDS of a workgroup
@@ -47,7 +43,7 @@ struct LwSeTile { // what a workgroup works on; the same for all its lanes
 	uint64_t cnt_at;  // entry of the row and channel in d_counts
 };
 
-LW_SE_FN void lw_se_tile(const LwSelectArgs &a, uint32_t tile_i, uint32_t grp, uint32_t by, uint32_t bz, LwSeTile &t)
+LW_LANES_FN void lw_se_tile(const LwSelectArgs &a, uint32_t tile_i, uint32_t grp, uint32_t by, uint32_t bz, LwSeTile &t)
 {
 	const uint64_t row = (uint64_t)a.row0 + bz;
 	const LwSelectRow r = a.rows[row];
@@ -65,7 +61,7 @@ LW_SE_FN void lw_se_tile(const LwSelectArgs &a, uint32_t tile_i, uint32_t grp, u
 }
 
 // ---- the kept frames among the lane's tile / 256 consecutive frames
-LW_SE_FN uint32_t lw_se_lane_count(const LwSelectArgs &a, const LwSeTile &t, const uint8_t *LW_SE_RESTRICT mask, uint32_t tid)
+LW_LANES_FN uint32_t lw_se_lane_count(const LwSelectArgs &a, const LwSeTile &t, const uint8_t *LW_LANES_RESTRICT mask, uint32_t tid)
 {
 	const uint32_t per = a.tile / LW_SE_THREADS, lo = tid * per;
 	uint32_t c = 0;
@@ -74,13 +70,13 @@ LW_SE_FN uint32_t lw_se_lane_count(const LwSelectArgs &a, const LwSeTile &t, con
 	return c;
 }
 
-LW_SE_FN void lw_se_count(const LwSelectArgs &a, const LwSeTile &t, const uint8_t *LW_SE_RESTRICT mask, LwSeLds &l, uint32_t tid)
+LW_LANES_FN void lw_se_count(const LwSelectArgs &a, const LwSeTile &t, const uint8_t *LW_LANES_RESTRICT mask, LwSeLds &l, uint32_t tid)
 {
 	l.cnt[tid] = lw_se_lane_count(a, t, mask, tid);
 }
 
 // (behind a barrier) the totals of the groups of 16 lanes; cnt becomes the exclusive prefix within the group
-LW_SE_FN void lw_se_groups(LwSeLds &l, uint32_t tid)
+LW_LANES_FN void lw_se_groups(LwSeLds &l, uint32_t tid)
 {
 	if (tid >= 16u)
 		return;
@@ -94,7 +90,7 @@ LW_SE_FN void lw_se_groups(LwSeLds &l, uint32_t tid)
 }
 
 // (behind a barrier) the tile's total
-LW_SE_FN uint32_t lw_se_total(const LwSeLds &l)
+LW_LANES_FN uint32_t lw_se_total(const LwSeLds &l)
 {
 	uint32_t s = 0;
 	for (uint32_t k = 0; k < 16u; k++)
@@ -103,7 +99,7 @@ LW_SE_FN uint32_t lw_se_total(const LwSeLds &l)
 }
 
 // ---- base and K: partial sums of the row's tile counts
-LW_SE_FN void lw_se_partial(const LwSelectArgs &a, const LwSeTile &t, LwSeLds &l, uint32_t tid)
+LW_LANES_FN void lw_se_partial(const LwSelectArgs &a, const LwSeTile &t, LwSeLds &l, uint32_t tid)
 {
 	uint64_t before = 0, all = 0;
 	for (uint32_t j = tid; j < t.n_tiles; j += LW_SE_THREADS) {
@@ -116,7 +112,7 @@ LW_SE_FN void lw_se_partial(const LwSelectArgs &a, const LwSeTile &t, LwSeLds &l
 }
 
 // (behind a barrier) sixteen lanes fold sixteen partial sums each, of both kinds
-LW_SE_FN void lw_se_fold(LwSeLds &l, uint32_t tid)
+LW_LANES_FN void lw_se_fold(LwSeLds &l, uint32_t tid)
 {
 	if (tid >= 32u)
 		return;
@@ -127,7 +123,7 @@ LW_SE_FN void lw_se_fold(LwSeLds &l, uint32_t tid)
 }
 
 // (behind a barrier) which = 0: base, 1: K
-LW_SE_FN uint64_t lw_se_sum(const LwSeLds &l, uint32_t which)
+LW_LANES_FN uint64_t lw_se_sum(const LwSeLds &l, uint32_t which)
 {
 	uint64_t s = 0;
 	for (uint32_t k = 0; k < 16u; k++)
@@ -136,7 +132,7 @@ LW_SE_FN uint64_t lw_se_sum(const LwSeLds &l, uint32_t which)
 }
 
 // ---- (behind lw_se_groups and a barrier) the places of the lane's kept frames into the compacted list
-LW_SE_FN void lw_se_places(const LwSelectArgs &a, const LwSeTile &t, const uint8_t *LW_SE_RESTRICT mask, LwSeLds &l, uint32_t tid)
+LW_LANES_FN void lw_se_places(const LwSelectArgs &a, const LwSeTile &t, const uint8_t *LW_LANES_RESTRICT mask, LwSeLds &l, uint32_t tid)
 {
 	const uint32_t per = a.tile / LW_SE_THREADS, lo = tid * per;
 	uint32_t at = l.cnt[tid];
@@ -148,7 +144,7 @@ LW_SE_FN void lw_se_places(const LwSelectArgs &a, const LwSeTile &t, const uint8
 }
 
 // ---- (behind a barrier) the copy of the tile's kept frames and the tile's share of the tail
-LW_SE_FN void lw_se_copy(const LwSelectArgs &a, const LwSeTile &t, const uint32_t *LW_SE_RESTRICT src, uint32_t *LW_SE_RESTRICT dst, const LwSeLds &l,
+LW_LANES_FN void lw_se_copy(const LwSelectArgs &a, const LwSeTile &t, const uint32_t *LW_LANES_RESTRICT src, uint32_t *LW_LANES_RESTRICT dst, const LwSeLds &l,
 		uint64_t base, uint64_t K, uint32_t kept, uint32_t tid)
 {
 	const uint64_t end = t.t0 + a.tile < t.fill_end ? t.t0 + a.tile : t.fill_end;
@@ -163,7 +159,7 @@ LW_SE_FN void lw_se_copy(const LwSelectArgs &a, const LwSeTile &t, const uint32_
 	}
 }
 
-#ifndef LW_SELECT_HOST
+#ifndef LW_KERNEL_HOST
 
 __global__ void __launch_bounds__(LW_SE_THREADS) k_select_count(LwSelectArgs a, const uint8_t *__restrict__ mask)
 {
@@ -224,4 +220,4 @@ hipError_t lw_launch_select(const LwSelectArgs &a, const uint32_t *src, const ui
 	return lw_launch_k(k_select, dim3(a.tiles * a.groups, a.ch, n_rows), dim3(LW_SE_THREADS), 0, st, a, src, mask, dst);
 }
 
-#endif // LW_SELECT_HOST
+#endif // LW_KERNEL_HOST

@@ -20,13 +20,8 @@
 // workgroup, the phases in the kernel's order.
 #include "lw_slide.hpp"
 
-#ifdef LW_SLIDE_HOST
-#define LW_SL_FN static inline
-#define LW_SL_RESTRICT
-#else
+#ifndef LW_KERNEL_HOST
 #include "lw_kernels.hpp"
-#define LW_SL_FN __device__ __forceinline__
-#define LW_SL_RESTRICT __restrict__
 #endif
 
 #define LW_SL_AT(i) ((i) + ((i) >> 5)) // the dword of element i of an image line
@@ -43,7 +38,7 @@ struct LwSlTile { // what a workgroup works on; the same for all its lanes
 };
 
 // false: the tile lies at or beyond the row's fill_end, nothing to do
-LW_SL_FN bool lw_sl_tile(const LwSlideArgs &a, uint32_t bx, uint32_t by, uint32_t bz, LwSlTile &t)
+LW_LANES_FN bool lw_sl_tile(const LwSlideArgs &a, uint32_t bx, uint32_t by, uint32_t bz, LwSlTile &t)
 {
 	const uint64_t row = (uint64_t)a.row0 + bz;
 	const LwSlideRow r = a.rows[row];
@@ -69,7 +64,7 @@ LW_SL_FN bool lw_sl_tile(const LwSlideArgs &a, uint32_t bx, uint32_t by, uint32_
 }
 
 // ---- +0.0 into frames [fill_lo, fill_hi) of the tile, every line of the group
-LW_SL_FN void lw_sl_fill(const LwSlideArgs &a, const LwSlTile &t, float *LW_SL_RESTRICT dst, uint32_t tid)
+LW_LANES_FN void lw_sl_fill(const LwSlideArgs &a, const LwSlTile &t, float *LW_LANES_RESTRICT dst, uint32_t tid)
 {
 	for (uint32_t g = 0; g < t.G; g++) {
 		float *y = dst + t.at + (uint64_t)g * a.line_el + t.t0;
@@ -79,7 +74,7 @@ LW_SL_FN void lw_sl_fill(const LwSlideArgs &a, const LwSlTile &t, float *LW_SL_R
 }
 
 // ---- frames [lo, lo + len) of the group's lines into the image
-LW_SL_FN void lw_sl_load(const LwSlideArgs &a, const LwSlTile &t, const float *LW_SL_RESTRICT src, float *xf, uint32_t tid)
+LW_LANES_FN void lw_sl_load(const LwSlideArgs &a, const LwSlTile &t, const float *LW_LANES_RESTRICT src, float *xf, uint32_t tid)
 {
 	for (uint32_t g = 0; g < t.G; g++) {
 		const float *x = src + t.at + (uint64_t)g * a.line_el + t.lo;
@@ -91,7 +86,7 @@ LW_SL_FN void lw_sl_load(const LwSlideArgs &a, const LwSlTile &t, const float *L
 
 // ---- rule 2 for the blocks that lie wholly in the image: bs[(2 g + 0) * nb + b] = A, bs[(2 g + 1) * nb + b] = Q
 template <bool NV>
-LW_SL_FN void lw_sl_blocks(const LwSlideArgs &a, const LwSlTile &t, const float *xf, double *bs, uint32_t tid)
+LW_LANES_FN void lw_sl_blocks(const LwSlideArgs &a, const LwSlTile &t, const float *xf, double *bs, uint32_t tid)
 {
 	const uint32_t nbk = t.len / LW_SL_BLOCK, items = t.G * nbk;
 	for (uint32_t it = tid; it < items; it += LW_SL_THREADS) {
@@ -114,7 +109,7 @@ LW_SL_FN void lw_sl_blocks(const LwSlideArgs &a, const LwSlTile &t, const float 
 // ---- rules 3 and 4 for one frame of NL lines at once: the lines' accumulators are independent chains with the same terms, so
 // NL loads are in flight for every step of a chain (the order of every line's additions is the contract's)
 template <bool NV, int NL>
-LW_SL_FN void lw_sl_frame(const LwSlideArgs &a, const float *img, const double *Ab, float *LW_SL_RESTRICT y, uint32_t ls, uint32_t le, uint32_t at,
+LW_LANES_FN void lw_sl_frame(const LwSlideArgs &a, const float *img, const double *Ab, float *LW_LANES_RESTRICT y, uint32_t ls, uint32_t le, uint32_t at,
 		uint64_t n)
 {
 	const uint32_t b0 = (ls + LW_SL_BLOCK - 1u) / LW_SL_BLOCK, b1 = le / LW_SL_BLOCK;
@@ -162,7 +157,7 @@ LW_SL_FN void lw_sl_frame(const LwSlideArgs &a, const float *img, const double *
 
 // ---- rules 1, 3 and 4 for the tile's frames: consecutive lanes on consecutive frames, the group's lines four, two or one at a time
 template <bool NV>
-LW_SL_FN void lw_sl_apply(const LwSlideArgs &a, const LwSlTile &t, const float *xf, const double *bs, float *LW_SL_RESTRICT dst, uint32_t tid)
+LW_LANES_FN void lw_sl_apply(const LwSlideArgs &a, const LwSlTile &t, const float *xf, const double *bs, float *LW_LANES_RESTRICT dst, uint32_t tid)
 {
 	for (uint32_t i = tid; i < t.nt; i += LW_SL_THREADS) {
 		int64_t s, e;
@@ -182,7 +177,7 @@ LW_SL_FN void lw_sl_apply(const LwSlideArgs &a, const LwSlTile &t, const float *
 	}
 }
 
-#ifndef LW_SLIDE_HOST
+#ifndef LW_KERNEL_HOST
 
 template <bool NV>
 __global__ void __launch_bounds__(LW_SL_THREADS) k_slide(LwSlideArgs a, const float *__restrict__ src, float *__restrict__ dst)
@@ -218,4 +213,4 @@ hipError_t lw_launch_slide(const LwSlideArgs &a, const float *src, float *dst, u
 	return lw_launch_k(k_slide<false>, grid, dim3(LW_SL_THREADS), (size_t)p.lds, st, a, src, dst);
 }
 
-#endif // LW_SLIDE_HOST
+#endif // LW_KERNEL_HOST

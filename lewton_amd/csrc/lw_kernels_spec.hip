@@ -37,11 +37,9 @@
 // 32-bit relative to the tile.  Plain vector loads and stores, no scratch (profiles/rows_spec_resource_usage.txt).
 #include "lw_spec.hpp"
 
-#ifdef LW_SPEC_HOST
-#define LW_SP_FN static inline
-#else
+#include "lw_lanes.hpp"
+#ifndef LW_KERNEL_HOST
 #include "lw_kernels.hpp"
-#define LW_SP_FN __device__ __forceinline__
 #endif
 
 struct LwSpTile { // what a workgroup works on; the same for all its lanes
@@ -53,14 +51,11 @@ struct LwSpTile { // what a workgroup works on; the same for all its lanes
 };
 
 struct LwSpLane { // what a lane keeps in registers between the phases of its workgroup
-	float acc[4][16]; // [2 * tile + sine][register]: bin = LW_SP_ROW(register, lane), frame = lane & 31
+	float acc[4][16]; // [2 * tile + sine][register]: bin = LW_MFMA32_ROW(register, lane), frame = lane & 31
 	float mel[8][4];  // band 4 * ((tid >> 5) + 8 * b) + i of frame tid & 31
 };
 
-// C/D layout of the 32x32 matrix instructions: register r of lane l holds row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31
-#define LW_SP_ROW(r, lane) (((r) & 3u) + 8u * ((r) >> 2) + 4u * ((lane) >> 5))
-
-LW_SP_FN bool lw_sp_tile(const LwSpecArgs &a, uint32_t bx, uint32_t by, uint32_t bz, LwSpTile &t)
+LW_LANES_FN bool lw_sp_tile(const LwSpecArgs &a, uint32_t bx, uint32_t by, uint32_t bz, LwSpTile &t)
 {
 	const LwSpecRow r = a.rows[(uint64_t)a.row0 + bz];
 	t.len = r.len, t.n_frames = r.n_frames;
@@ -74,14 +69,14 @@ LW_SP_FN bool lw_sp_tile(const LwSpecArgs &a, uint32_t bx, uint32_t by, uint32_t
 }
 
 // input index of support sample k of the tile's frame f
-LW_SP_FN int64_t lw_sp_index(const LwSpecArgs &a, const LwSpTile &t, uint32_t f, uint32_t k)
+LW_LANES_FN int64_t lw_sp_index(const LwSpecArgs &a, const LwSpTile &t, uint32_t f, uint32_t k)
 {
 	return t.x0 + (int64_t)((uint64_t)f * a.hop) + (int64_t)k;
 }
 
 // where x[i] is read under reflect padding: i itself inside [0, len), -i below, 2 (len - 1) - i from len on, in 64-bit integers
 // (one reflection: the host has refused rows for which a support sample would need a second one).  Selects, no branch
-LW_SP_FN int64_t lw_sp_reflect(const LwSpTile &t, int64_t i)
+LW_LANES_FN int64_t lw_sp_reflect(const LwSpTile &t, int64_t i)
 {
 	const int64_t up = i < 0 ? -i : i;
 	return (uint64_t)up >= t.len ? 2 * ((int64_t)t.len - 1) - up : up;
@@ -95,13 +90,13 @@ LW_SP_FN int64_t lw_sp_reflect(const LwSpTile &t, int64_t i)
 #define LW_SP_PAD_ARGS (-1)
 // where x[i] is read under symmetric padding (LW_SPEC_PAD_SYMMETRIC, Kaldi's frames without snip_edges): the edge sample is
 // repeated, -i - 1 below 0 and 2 len - 1 - i from len on (one reflection, as above)
-LW_SP_FN int64_t lw_sp_symmetric(const LwSpTile &t, int64_t i)
+LW_LANES_FN int64_t lw_sp_symmetric(const LwSpTile &t, int64_t i)
 {
 	const int64_t up = i < 0 ? -i - 1 : i;
 	return (uint64_t)up >= t.len ? 2 * (int64_t)t.len - 1 - up : up;
 }
 
-template <int PAD> LW_SP_FN float lw_sp_x(const LwSpecArgs &a, const LwSpTile &t, int64_t i)
+template <int PAD> LW_LANES_FN float lw_sp_x(const LwSpecArgs &a, const LwSpTile &t, int64_t i)
 {
 	if (PAD == 1 || (PAD == LW_SP_PAD_ARGS && a.pad_mode == 1))
 		i = lw_sp_reflect(t, i);
@@ -117,7 +112,7 @@ struct alignas(16) LwSpF4 {
 	float v[4];
 };
 
-LW_SP_FN void lw_sp_zero_acc(LwSpLane &st)
+LW_LANES_FN void lw_sp_zero_acc(LwSpLane &st)
 {
 #pragma unroll
 	for (int i = 0; i < 4; i++)
@@ -126,7 +121,7 @@ LW_SP_FN void lw_sp_zero_acc(LwSpLane &st)
 			st.acc[i][r] = 0.0f;
 }
 
-LW_SP_FN void lw_sp_zero_mel(LwSpLane &st)
+LW_LANES_FN void lw_sp_zero_mel(LwSpLane &st)
 {
 #pragma unroll
 	for (int b = 0; b < 8; b++)
@@ -139,7 +134,7 @@ LW_SP_FN void lw_sp_zero_mel(LwSpLane &st)
 // PRO (the per-frame prologue ran): x'_k = x_k - mu, one rounded subtraction, of the padded sample and before the tail's zeros;
 // mu0 / mu1 are the means of the lane's two frames (lw_sp_pro_mu), +0.0 without remove_dc, which leaves every x as it is
 template <int PAD = LW_SP_PAD_ARGS, int PRO = 0>
-LW_SP_FN void lw_sp_stage(const LwSpecArgs &a, const LwSpTile &t, uint32_t pass, uint32_t kt, uint32_t tid, float *lds, float mu0 = 0.0f, float mu1 = 0.0f)
+LW_LANES_FN void lw_sp_stage(const LwSpecArgs &a, const LwSpTile &t, uint32_t pass, uint32_t kt, uint32_t tid, float *lds, float mu0 = 0.0f, float mu1 = 0.0f)
 {
 	const uint32_t k0 = kt * LW_SP_KT;
 	const LwSpF4 *g = (const LwSpF4 *)(a.basis + ((size_t)pass * a.k_pad + k0) * (2u * LW_SP_COLS));
@@ -170,21 +165,21 @@ LW_SP_FN void lw_sp_stage(const LwSpecArgs &a, const LwSpTile &t, uint32_t pass,
 }
 
 // which of a wave's two tiles hold a bin at all
-LW_SP_FN bool lw_sp_tile_live(const LwSpecArgs &a, uint32_t pass, uint32_t wave, uint32_t tt)
+LW_LANES_FN bool lw_sp_tile_live(const LwSpecArgs &a, uint32_t pass, uint32_t wave, uint32_t tt)
 {
 	return pass * LW_SP_COLS + wave * 64u + tt * 32u < a.bins;
 }
 
-#ifndef LW_SPEC_HOST
+#ifndef LW_KERNEL_HOST
 typedef float lw_sp_f16 __attribute__((ext_vector_type(16)));
 #endif
 
 // ---- fold: the 16 support samples of the staged tile into the lane's accumulators, k ascending
-template <int ROUTE> LW_SP_FN void lw_sp_mma(const LwSpecArgs &a, uint32_t pass, uint32_t tid, const float *lds, LwSpLane &st)
+template <int ROUTE> LW_LANES_FN void lw_sp_mma(const LwSpecArgs &a, uint32_t pass, uint32_t tid, const float *lds, LwSpLane &st)
 {
 	const uint32_t lane = tid & 63u, wave = tid >> 6, f = lane & 31u;
 	const float *as = lds + LW_SP_LDS_A + wave * 64u, *xs = lds + LW_SP_LDS_X;
-#ifndef LW_SPEC_HOST
+#ifndef LW_KERNEL_HOST
 	if (ROUTE == LW_SP_ROUTE_MFMA) {
 		// A[i = lane & 31][k = lane >> 5] = basis[k][bin i], B[k = lane >> 5][j = lane & 31] = x of frame j: one f32 each
 		const uint32_t h = lane >> 5;
@@ -219,7 +214,7 @@ template <int ROUTE> LW_SP_FN void lw_sp_mma(const LwSpecArgs &a, uint32_t pass,
 			const float *row = as + kk * (2u * LW_SP_COLS) + tt * 32u;
 #pragma unroll
 			for (uint32_t r = 0; r < 16u; r++) {
-				const uint32_t i = LW_SP_ROW(r, lane);
+				const uint32_t i = LW_MFMA32_ROW(r, lane);
 				st.acc[2 * tt][r] = __builtin_fmaf(b, row[i], st.acc[2 * tt][r]);
 				st.acc[2 * tt + 1][r] = __builtin_fmaf(b, row[LW_SP_COLS + i], st.acc[2 * tt + 1][r]);
 			}
@@ -228,7 +223,7 @@ template <int ROUTE> LW_SP_FN void lw_sp_mma(const LwSpecArgs &a, uint32_t pass,
 }
 
 // ---- power: P = fmaf(im, im, re * re) of the pass into LDS, [bin of the pass][frame]
-LW_SP_FN void lw_sp_power(const LwSpecArgs &a, uint32_t pass, uint32_t tid, float *lds, const LwSpLane &st)
+LW_LANES_FN void lw_sp_power(const LwSpecArgs &a, uint32_t pass, uint32_t tid, float *lds, const LwSpLane &st)
 {
 	const uint32_t lane = tid & 63u, wave = tid >> 6, f = lane & 31u;
 #pragma unroll
@@ -239,13 +234,13 @@ LW_SP_FN void lw_sp_power(const LwSpecArgs &a, uint32_t pass, uint32_t tid, floa
 		for (uint32_t r = 0; r < 16u; r++) {
 			const float re = st.acc[2 * tt][r], im = st.acc[2 * tt + 1][r];
 			const float sq = re * re;
-			lds[LW_SP_LDS_P + (wave * 64u + tt * 32u + LW_SP_ROW(r, lane)) * LW_SP_TF + f] = __builtin_fmaf(im, im, sq);
+			lds[LW_SP_LDS_P + (wave * 64u + tt * 32u + LW_MFMA32_ROW(r, lane)) * LW_SP_TF + f] = __builtin_fmaf(im, im, sq);
 		}
 	}
 }
 
 // ---- the pass's bins from the P region of LDS to the lines line0 + bin, consecutive lanes on consecutive frames
-LW_SP_FN void lw_sp_store_lines(const LwSpecArgs &a, const LwSpTile &t, uint32_t pass, uint32_t tid, const float *lds, uint32_t line0)
+LW_LANES_FN void lw_sp_store_lines(const LwSpecArgs &a, const LwSpTile &t, uint32_t pass, uint32_t tid, const float *lds, uint32_t line0)
 {
 	const uint32_t f = tid % LW_SP_TF;
 	if (t.f0 + f >= t.n_frames)
@@ -259,7 +254,7 @@ LW_SP_FN void lw_sp_store_lines(const LwSpecArgs &a, const LwSpTile &t, uint32_t
 }
 
 // ---- without a mel matrix: the power (PRO: the lines follow the energy line when there is one)
-template <int PRO = 0> LW_SP_FN void lw_sp_store_power(const LwSpecArgs &a, const LwSpTile &t, uint32_t pass, uint32_t tid, const float *lds)
+template <int PRO = 0> LW_LANES_FN void lw_sp_store_power(const LwSpecArgs &a, const LwSpTile &t, uint32_t pass, uint32_t tid, const float *lds)
 {
 	lw_sp_store_lines(a, t, pass, tid, lds, PRO ? a.energy : 0u);
 }
@@ -267,7 +262,7 @@ template <int PRO = 0> LW_SP_FN void lw_sp_store_power(const LwSpecArgs &a, cons
 // ---- complex output (LW_SPEC_OUT_COMPLEX; OUT = 1 in the kernel): re (SINE = 0) or im (SINE = 1) of the pass into the P region,
 // laid out as lw_sp_power lays out P, and from there to the lines line0 + bin: re[j] on line j, im[j] on line B + j, the two
 // chains themselves and nothing formed from them
-template <int SINE> LW_SP_FN void lw_sp_part(const LwSpecArgs &a, uint32_t pass, uint32_t tid, float *lds, const LwSpLane &st)
+template <int SINE> LW_LANES_FN void lw_sp_part(const LwSpecArgs &a, uint32_t pass, uint32_t tid, float *lds, const LwSpLane &st)
 {
 	const uint32_t lane = tid & 63u, wave = tid >> 6, f = lane & 31u;
 #pragma unroll
@@ -276,12 +271,12 @@ template <int SINE> LW_SP_FN void lw_sp_part(const LwSpecArgs &a, uint32_t pass,
 			continue;
 #pragma unroll
 		for (uint32_t r = 0; r < 16u; r++)
-			lds[LW_SP_LDS_P + (wave * 64u + tt * 32u + LW_SP_ROW(r, lane)) * LW_SP_TF + f] = st.acc[2 * tt + SINE][r];
+			lds[LW_SP_LDS_P + (wave * 64u + tt * 32u + LW_MFMA32_ROW(r, lane)) * LW_SP_TF + f] = st.acc[2 * tt + SINE][r];
 	}
 }
 
 // ---- mel: slice jc (32 bins) of the pass; the matrix slice [32][mel_pad] into the basis tile's place, then the fold
-LW_SP_FN void lw_sp_stage_fb(const LwSpecArgs &a, uint32_t pass, uint32_t jc, uint32_t tid, float *lds)
+LW_LANES_FN void lw_sp_stage_fb(const LwSpecArgs &a, uint32_t pass, uint32_t jc, uint32_t tid, float *lds)
 {
 	const uint32_t j0 = pass * LW_SP_COLS + jc * LW_SP_JT, n = LW_SP_JT * a.mel_pad / 4u; // <= 8 per lane
 	const LwSpF4 *g = (const LwSpF4 *)(a.fb + (size_t)j0 * a.mel_pad);
@@ -300,7 +295,7 @@ LW_SP_FN void lw_sp_stage_fb(const LwSpecArgs &a, uint32_t pass, uint32_t jc, ui
 	}
 }
 
-LW_SP_FN void lw_sp_mel(const LwSpecArgs &a, uint32_t pass, uint32_t jc, uint32_t tid, const float *lds, LwSpLane &st)
+LW_LANES_FN void lw_sp_mel(const LwSpecArgs &a, uint32_t pass, uint32_t jc, uint32_t tid, const float *lds, LwSpLane &st)
 {
 	const uint32_t f = tid % LW_SP_TF, g = tid / LW_SP_TF, nb = a.mel_pad / 32u;
 	const uint32_t j0 = pass * LW_SP_COLS + jc * LW_SP_JT, nj = a.bins - j0 < LW_SP_JT ? a.bins - j0 : LW_SP_JT;
@@ -319,7 +314,7 @@ LW_SP_FN void lw_sp_mel(const LwSpecArgs &a, uint32_t pass, uint32_t jc, uint32_
 	}
 }
 
-template <int PRO = 0> LW_SP_FN void lw_sp_store_mel(const LwSpecArgs &a, const LwSpTile &t, uint32_t tid, const LwSpLane &st)
+template <int PRO = 0> LW_LANES_FN void lw_sp_store_mel(const LwSpecArgs &a, const LwSpTile &t, uint32_t tid, const LwSpLane &st)
 {
 	const uint32_t f = tid % LW_SP_TF, g = tid / LW_SP_TF, line0 = PRO ? a.energy : 0u;
 	if (t.f0 + f >= t.n_frames)
@@ -335,7 +330,7 @@ template <int PRO = 0> LW_SP_FN void lw_sp_store_mel(const LwSpecArgs &a, const 
 }
 
 // slices of the mel matrix that pass `pass` folds
-LW_SP_FN uint32_t lw_sp_slices(const LwSpecArgs &a, uint32_t pass)
+LW_LANES_FN uint32_t lw_sp_slices(const LwSpecArgs &a, uint32_t pass)
 {
 	const uint32_t left = a.bins - pass * LW_SP_COLS, n = left < LW_SP_COLS ? left : LW_SP_COLS;
 	return (n + LW_SP_JT - 1u) / LW_SP_JT;
@@ -353,19 +348,19 @@ LW_SP_FN uint32_t lw_sp_slices(const LwSpecArgs &a, uint32_t pass)
 #define LW_SP_PRO_MU (LW_SP_LDS_X + 4u * LW_SP_TF)  // [32] floats
 static_assert(5u * LW_SP_TF <= LW_SP_KT * LW_SP_XS && LW_SP_LDS_X % 2u == 0, "the prologue's sums fit the frame tile's place, 8-byte aligned");
 
-LW_SP_FN void lw_sp_put_d(float *at, double v)
+LW_LANES_FN void lw_sp_put_d(float *at, double v)
 {
 	__builtin_memcpy(at, &v, sizeof v);
 }
 
-LW_SP_FN double lw_sp_get_d(const float *at)
+LW_LANES_FN double lw_sp_get_d(const float *at)
 {
 	double v;
 	__builtin_memcpy(&v, at, sizeof v);
 	return v;
 }
 
-template <int PAD = LW_SP_PAD_ARGS> LW_SP_FN void lw_sp_pro_span(const LwSpecArgs &a, const LwSpTile &t, uint32_t tid, float *lds)
+template <int PAD = LW_SP_PAD_ARGS> LW_LANES_FN void lw_sp_pro_span(const LwSpecArgs &a, const LwSpTile &t, uint32_t tid, float *lds)
 {
 	// eight loads of a lane in flight before its first store (a load beyond the span goes to a clamped index like any other)
 	for (uint32_t s0 = tid; s0 < a.span; s0 += 8u * LW_SP_THREADS) {
@@ -382,7 +377,7 @@ template <int PAD = LW_SP_PAD_ARGS> LW_SP_FN void lw_sp_pro_span(const LwSpecArg
 	}
 }
 
-template <int PAD = LW_SP_PAD_ARGS> LW_SP_FN void lw_sp_pro_sums(const LwSpecArgs &a, const LwSpTile &t, uint32_t tid, float *lds)
+template <int PAD = LW_SP_PAD_ARGS> LW_LANES_FN void lw_sp_pro_sums(const LwSpecArgs &a, const LwSpTile &t, uint32_t tid, float *lds)
 {
 	const uint32_t wave = tid >> 6, f = tid & 63u;
 	if (wave > 1u || f >= LW_SP_TF)
@@ -414,7 +409,7 @@ template <int PAD = LW_SP_PAD_ARGS> LW_SP_FN void lw_sp_pro_sums(const LwSpecArg
 
 // mu of the tile's frames into LDS (+0.0 without remove_dc), and E of the frames that exist to line 0: every operation one
 // rounding (the unit is compiled with -ffp-contract=off), Ed = 0 unless Ed > 0 (a NaN too)
-LW_SP_FN void lw_sp_pro_finish(const LwSpecArgs &a, const LwSpTile &t, uint32_t tid, float *lds)
+LW_LANES_FN void lw_sp_pro_finish(const LwSpecArgs &a, const LwSpTile &t, uint32_t tid, float *lds)
 {
 	if (tid >= LW_SP_TF)
 		return;
@@ -434,19 +429,19 @@ LW_SP_FN void lw_sp_pro_finish(const LwSpecArgs &a, const LwSpTile &t, uint32_t 
 }
 
 // the means of the two frames a lane stages in every K tile (frame e / LW_SP_KT of e = tid + q * 256)
-LW_SP_FN void lw_sp_pro_mu(uint32_t tid, const float *lds, float &mu0, float &mu1)
+LW_LANES_FN void lw_sp_pro_mu(uint32_t tid, const float *lds, float &mu0, float &mu1)
 {
 	mu0 = lds[LW_SP_PRO_MU + tid / LW_SP_KT];
 	mu1 = lds[LW_SP_PRO_MU + tid / LW_SP_KT + LW_SP_THREADS / LW_SP_KT];
 }
 
-#ifndef LW_SPEC_HOST
+#ifndef LW_KERNEL_HOST
 
 // The body of both kernels.  OUT is the object's output (LW_SPEC_OUT_*) as a compile-time constant, for PAD's reason: k_spec is
 // the body with OUT = 0, the kernel it was before the complex output existed (profiles/rows_spec_resource_usage.txt), and
 // k_spec_complex the body with OUT = 1 and no prologue.
 // PRO = 0 is the kernel without the prologue, to the instruction: what every object without remove_dc and energy runs
-template <int ROUTE, int PAD, int PRO, int OUT> LW_SP_FN void lw_sp_body(const LwSpecArgs &a, float *lw_sp_lds)
+template <int ROUTE, int PAD, int PRO, int OUT> LW_LANES_FN void lw_sp_body(const LwSpecArgs &a, float *lw_sp_lds)
 {
 	LwSpTile t;
 	if (!lw_sp_tile(a, blockIdx.x, blockIdx.y, blockIdx.z, t))
@@ -562,4 +557,4 @@ hipError_t lw_launch_spec(const LwSpecArgs &a, int route, uint32_t tiles, uint32
 	return hipErrorInvalidValue;
 }
 
-#endif // LW_SPEC_HOST
+#endif // LW_KERNEL_HOST

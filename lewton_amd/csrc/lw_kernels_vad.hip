@@ -27,19 +27,14 @@
 // kernels' order.
 #include "lw_vad.hpp"
 
-#ifdef LW_VAD_HOST
-#define LW_VD_FN static inline
-#define LW_VD_RESTRICT
-#else
+#ifndef LW_KERNEL_HOST
 #include "lw_kernels.hpp"
-#define LW_VD_FN __device__ __forceinline__
-#define LW_VD_RESTRICT __restrict__
 #endif
 
-typedef float LwVdV4 __attribute__((vector_size(16)));
+static_assert(LW_VD_WAVES == LW_LANES_WAVES && LW_VD_THREADS == LW_LANES_WAVES * 64u, "lw_lanes.hpp's plans and loops count four waves to a workgroup");
 
 struct LwVdLds { // the LDS of a workgroup
-	double sum[LW_VD_GROUP];    // the line's chunk sums (k_vad)
+	double sum[LW_SUM_GROUP];    // the line's chunk sums (k_vad)
 	uint64_t bits[LW_VD_WORDS]; // raw decisions: bit j of the list is frame t0 - ctx + j
 };
 static_assert(sizeof(LwVdLds) == LW_VD_LDS, "LW_VD_LDS is the structure's size");
@@ -55,7 +50,7 @@ struct LwVdTile { // what a workgroup works on; the same for all its lanes
 	uint64_t thr_at;  // entry of the row and channel in d_thr and a.thr
 };
 
-LW_VD_FN void lw_vd_tile(const LwVadArgs &a, uint32_t tile_i, uint32_t by, uint32_t bz, LwVdTile &t)
+LW_LANES_FN void lw_vd_tile(const LwVadArgs &a, uint32_t tile_i, uint32_t by, uint32_t bz, LwVdTile &t)
 {
 	const uint64_t row = (uint64_t)a.row0 + bz;
 	const LwVadRow r = a.rows[row];
@@ -67,56 +62,19 @@ LW_VD_FN void lw_vd_tile(const LwVadArgs &a, uint32_t tile_i, uint32_t by, uint3
 	t.thr_at = row * a.ch + by;
 }
 
-// ---- the tree.  On the device every lane brings its entry and leaves with the wave's; the host build runs a wave at a time
-// (lane is 0) and folds the 64 entries as the contract writes it, t[j] = t[2j] + t[2j + 1]
-template <class E>
-LW_VD_FN double lw_vd_wave_tree(uint32_t lane, E entry)
-{
-#ifdef LW_VAD_HOST
-	double t[LW_VD_GROUP];
-	for (uint32_t l = 0; l < LW_VD_GROUP; l++)
-		t[l] = entry(l);
-	for (uint32_t n = LW_VD_GROUP / 2; n; n >>= 1)
-		for (uint32_t j = 0; j < n; j++)
-			t[j] = t[2 * j] + t[2 * j + 1];
-	(void)lane;
-	return t[0];
-#else
-	double t = entry(lane);
-#pragma unroll
-	for (int o = 1; o < 64; o <<= 1)
-		t = t + __shfl_xor(t, o, 64);
-	return t;
-#endif
-}
-
-// ... and the wave's ballot: bit l is lane l's decision
-template <class P>
-LW_VD_FN uint64_t lw_vd_wave_ballot(uint32_t lane, P decision)
-{
-#ifdef LW_VAD_HOST
-	uint64_t w = 0;
-	for (uint32_t l = 0; l < 64u; l++)
-		w |= (uint64_t)(decision(l) ? 1u : 0u) << l;
-	(void)lane;
-	return w;
-#else
-	return __ballot(decision(lane));
-#endif
-}
-
 // ---- the chunk sum ("normalising rows", step 1, the sum alone): lane `lane`'s share of chunk c of the line at element `at` --
-// frames 4 lane .. 4 lane + 3 of the chunk, those at or beyond n as +0.0
-LW_VD_FN double lw_vd_chunk_lane(const float *LW_VD_RESTRICT src, uint64_t at, uint64_t n, uint32_t c, uint32_t lane)
+// frames 4 lane .. 4 lane + 3 of the chunk, those at or beyond n as +0.0.  (This load and lw_kernels_norm.hip's stay two: one
+// function for both, which hands the four floats on, changed either kernel's code.)
+LW_LANES_FN double lw_vd_chunk_lane(const float *LW_LANES_RESTRICT src, uint64_t at, uint64_t n, uint32_t c, uint32_t lane)
 {
-	const uint64_t e0 = (uint64_t)c * LW_VD_CHUNK + lane * 4u;
+	const uint64_t e0 = (uint64_t)c * LW_SUM_CHUNK + lane * 4u;
 	float x0 = 0.0f, x1 = 0.0f, x2 = 0.0f, x3 = 0.0f;
 	if (e0 + 4u <= n) {
 		const float *s = src + at + e0;
 		if ((((uintptr_t)src >> 2) + at + e0) & 3u)
 			x0 = s[0], x1 = s[1], x2 = s[2], x3 = s[3];
 		else { // ONE 16-byte load
-			const LwVdV4 q = *(const LwVdV4 *)s;
+			const LwV4 q = *(const LwV4 *)s;
 			x0 = q[0], x1 = q[1], x2 = q[2], x3 = q[3];
 		}
 	} else {
@@ -130,15 +88,15 @@ LW_VD_FN double lw_vd_chunk_lane(const float *LW_VD_RESTRICT src, uint64_t at, u
 	return (((double)x0 + (double)x1) + (double)x2) + (double)x3;
 }
 
-LW_VD_FN double lw_vd_chunk(const float *LW_VD_RESTRICT src, uint64_t at, uint64_t n, uint32_t c, uint32_t lane)
+LW_LANES_FN double lw_vd_chunk(const float *LW_LANES_RESTRICT src, uint64_t at, uint64_t n, uint32_t c, uint32_t lane)
 {
-	return lw_vd_wave_tree(lane, [&](uint32_t l) { return lw_vd_chunk_lane(src, at, n, c, l); });
+	return lw_wave_tree<double>(lane, [&](uint32_t l) { return lw_vd_chunk_lane(src, at, n, c, l); });
 }
 
 // ---- k_vad: one wave's chunks of the line into the workgroup's list
-LW_VD_FN void lw_vd_sum_lds(const LwVadArgs &a, const LwVdTile &t, LwVdLds &l, uint32_t wave, uint32_t lane)
+LW_LANES_FN void lw_vd_sum_lds(const LwVadArgs &a, const LwVdTile &t, LwVdLds &l, uint32_t wave, uint32_t lane)
 {
-	for (uint32_t c = wave; c < t.chunks && c < LW_VD_GROUP; c += LW_VD_WAVES) { // (the host admits rows of at most 64 chunks here)
+	for (uint32_t c = wave; c < t.chunks && c < LW_SUM_GROUP; c += LW_VD_WAVES) { // (the host admits rows of at most 64 chunks here)
 		const double s = lw_vd_chunk(a.src, t.src_at, t.n, c, lane);
 		if (lane == 0)
 			l.sum[c] = s;
@@ -146,15 +104,15 @@ LW_VD_FN void lw_vd_sum_lds(const LwVadArgs &a, const LwVdTile &t, LwVdLds &l, u
 }
 
 // (behind a barrier) S of a list of at most 64 entries: the entry itself, or ONE tree padded with +0.0
-LW_VD_FN double lw_vd_fold_lds(const LwVdLds &l, uint32_t chunks, uint32_t lane)
+LW_LANES_FN double lw_vd_fold_lds(const LwVdLds &l, uint32_t chunks, uint32_t lane)
 {
 	if (chunks == 1u)
 		return l.sum[0];
-	return lw_vd_wave_tree(lane, [&](uint32_t i) { return i < chunks ? l.sum[i] : 0.0; });
+	return lw_wave_tree<double>(lane, [&](uint32_t i) { return i < chunks ? l.sum[i] : 0.0; });
 }
 
 // ---- k_vad_sum: one wave's chunks of workgroup bx of a row and channel into the row's chunk list
-LW_VD_FN void lw_vd_sum_wave(const LwVadArgs &a, uint32_t bx, uint32_t by, uint32_t bz, uint32_t wave, uint32_t lane)
+LW_LANES_FN void lw_vd_sum_wave(const LwVadArgs &a, uint32_t bx, uint32_t by, uint32_t bz, uint32_t wave, uint32_t lane)
 {
 	LwVdTile t;
 	lw_vd_tile(a, 0u, by, bz, t);
@@ -166,48 +124,32 @@ LW_VD_FN void lw_vd_sum_wave(const LwVadArgs &a, uint32_t bx, uint32_t by, uint3
 	}
 }
 
-// ---- k_vad_fold: a workgroup per row and channel.  The lists of the levels: the row and channel's part of a.part, then in turn
-// the two halves of its scratch, ceil(longest / 64) and ceil(longest / 4096) doubles
-struct LwVdLevels {
-	const double *in;
-	double *out, *other;
-	uint64_t len, n, thr_at;
+// ---- k_vad_fold: a workgroup per row and channel: the levels of lw_lanes.hpp over the row and channel's part of a.part and
+// fold_scratch doubles of its own
+struct LwVdLevels : LwLevels<double> {
+	uint64_t n, thr_at;
 };
 
-LW_VD_FN void lw_vd_levels(const LwVadArgs &a, uint32_t by, uint32_t bz, LwVdLevels &v)
+LW_LANES_FN void lw_vd_levels(const LwVadArgs &a, uint32_t by, uint32_t bz, LwVdLevels &v)
 {
 	LwVdTile t;
 	lw_vd_tile(a, 0u, by, bz, t);
-	v.len = t.chunks, v.n = t.n, v.thr_at = t.thr_at;
-	v.in = v.len ? a.part + t.list_at : nullptr;
-	v.out = a.scratch + t.thr_at * a.fold_scratch;
-	v.other = v.out + ((uint64_t)a.sum_chunks + 63u) / 64u;
+	lw_levels(v, t.chunks ? a.part + t.list_at : (const double *)nullptr, (uint64_t)t.chunks, a.scratch + t.thr_at * a.fold_scratch, (uint64_t)a.sum_chunks);
+	v.n = t.n, v.thr_at = t.thr_at;
 }
 
-// one wave's groups of one level: group j of the list -> entry j of the next
-LW_VD_FN void lw_vd_level_wave(const LwVdLevels &v, uint32_t wave, uint32_t lane)
+LW_LANES_FN void lw_vd_level_wave(const LwVdLevels &v, uint32_t wave, uint32_t lane) // one wave's groups of one level
 {
-	const uint64_t groups = (v.len + LW_VD_GROUP - 1u) / LW_VD_GROUP;
-	for (uint64_t j = wave; j < groups; j += LW_VD_WAVES) {
-		const double s = lw_vd_wave_tree(lane, [&](uint32_t i) {
-			const uint64_t e = j * LW_VD_GROUP + i;
-			return e < v.len ? v.in[e] : 0.0;
-		});
-		if (lane == 0)
-			v.out[j] = s;
-	}
+	lw_level_wave(v, wave, lane);
 }
 
-// ... and behind the level's barrier
-LW_VD_FN void lw_vd_level_next(LwVdLevels &v)
+LW_LANES_FN void lw_vd_level_next(LwVdLevels &v) // ... and behind the level's barrier
 {
-	double *was = v.out;
-	v.len = (v.len + LW_VD_GROUP - 1u) / LW_VD_GROUP;
-	v.in = was, v.out = v.other, v.other = was;
+	lw_level_next(v);
 }
 
 // the threshold into its two places (one lane)
-LW_VD_FN void lw_vd_levels_out(const LwVadArgs &a, const LwVdLevels &v)
+LW_LANES_FN void lw_vd_levels_out(const LwVadArgs &a, const LwVdLevels &v)
 {
 	const float thr = lw_vad_threshold_value(a.energy_threshold, a.energy_mean_scale, v.len ? v.in[0] : 0.0, v.n);
 	a.thr[v.thr_at] = thr;
@@ -216,72 +158,29 @@ LW_VD_FN void lw_vd_levels_out(const LwVadArgs &a, const LwVdLevels &v)
 }
 
 // ---- the decide phase.  One wave's words of the raw decisions: bit j of the list is frame t0 - ctx + j, 0 outside [0, T)
-LW_VD_FN void lw_vd_stage_wave(const LwVadArgs &a, const LwVdTile &t, float thr, LwVdLds &l, uint32_t wave, uint32_t lane)
+LW_LANES_FN void lw_vd_stage_wave(const LwVadArgs &a, const LwVdTile &t, float thr, LwVdLds &l, uint32_t wave, uint32_t lane)
 {
 	const uint32_t span = a.tile + 2u * a.ctx, words = (span + 63u) / 64u;
-	const int64_t base = (int64_t)t.t0 - (int64_t)a.ctx;
-	for (uint32_t w = wave; w < words; w += LW_VD_WAVES) {
-		const uint64_t word = lw_vd_wave_ballot(lane, [&](uint32_t i) {
-			const uint32_t j = w * 64u + i;
-			const int64_t f = base + (int64_t)j;
-			return j < span && f >= 0 && (uint64_t)f < t.n && a.src[t.src_at + (uint64_t)f] > thr;
-		});
-		if (lane == 0)
-			l.bits[w] = word;
-	}
-}
-
-// the decisions set among bits [lo, hi) of the list, lo < hi
-LW_VD_FN uint32_t lw_vd_count(const LwVdLds &l, uint32_t lo, uint32_t hi)
-{
-	const uint32_t w0 = lo >> 6, w1 = (hi - 1u) >> 6;
-	uint32_t c = 0;
-	for (uint32_t w = w0; w <= w1; w++) {
-		uint64_t m = l.bits[w];
-		if (w == w0)
-			m &= ~(uint64_t)0 << (lo & 63u);
-		if (w == w1 && (hi & 63u))
-			m &= ((uint64_t)1 << (hi & 63u)) - 1u;
-		c += (uint32_t)__builtin_popcountll(m);
-	}
-	return c;
+	lw_bits_fill(l.bits, span, words, (int64_t)t.t0 - (int64_t)a.ctx, t.n, wave, lane, [&](uint32_t, uint64_t f) { return a.src[t.src_at + f] > thr; });
 }
 
 // rules 3 and 4 for one frame of the tile: the mask's byte
-LW_VD_FN uint32_t lw_vd_byte(const LwVadArgs &a, const LwVdTile &t, const LwVdLds &l, uint64_t f)
+LW_LANES_FN uint32_t lw_vd_byte(const LwVadArgs &a, const LwVdTile &t, const LwVdLds &l, uint64_t f)
 {
 	if (f >= t.n)
 		return 0u;
 	const int64_t base = (int64_t)t.t0 - (int64_t)a.ctx;
 	const int64_t lo = (int64_t)f - (int64_t)a.ctx < 0 ? 0 : (int64_t)f - (int64_t)a.ctx;
 	const int64_t hi = (int64_t)f + (int64_t)a.ctx + 1 > (int64_t)t.n ? (int64_t)t.n : (int64_t)f + (int64_t)a.ctx + 1;
-	const uint32_t num = lw_vd_count(l, (uint32_t)(lo - base), (uint32_t)(hi - base));
+	const uint32_t num = lw_bits_count<uint32_t>(l.bits, (uint32_t)(lo - base), (uint32_t)(hi - base), 0u); // (lo < hi: f is in it)
 	return lw_vad_voiced_value(num, (uint64_t)(hi - lo), a.proportion_threshold) ? 1u : 0u;
 }
 
 // (behind a barrier) the lane's groups of four mask bytes of the tile's share of [0, fill_end)
-LW_VD_FN void lw_vd_write(const LwVadArgs &a, const LwVdTile &t, const LwVdLds &l, uint32_t tid)
+LW_LANES_FN void lw_vd_write(const LwVadArgs &a, const LwVdTile &t, const LwVdLds &l, uint32_t tid)
 {
 	const uint64_t end = t.t0 + a.tile < t.fill_end ? t.t0 + a.tile : t.fill_end;
-	if (t.t0 >= end)
-		return;
-	uint8_t *m = a.mask + t.mask_at;
-	const uint32_t head = (uint32_t)((uintptr_t)(m + t.t0) & 3u);
-	const uint32_t groups = (uint32_t)((end - t.t0 + head + 3u) / 4u);
-	for (uint32_t g = tid; g < groups; g += LW_VD_THREADS) {
-		const int64_t f0 = (int64_t)t.t0 - (int64_t)head + (int64_t)g * 4;
-		if (f0 >= (int64_t)t.t0 && (uint64_t)f0 + 4u <= end) { // all four are the tile's: ONE dword
-			uint32_t v = 0;
-#pragma unroll
-			for (uint32_t k = 0; k < 4u; k++)
-				v |= lw_vd_byte(a, t, l, (uint64_t)f0 + k) << (8u * k);
-			*(uint32_t *)(m + f0) = v;
-			continue;
-		}
-		for (int64_t f = f0; f < f0 + 4; f++) // the ragged head and tail of the span
-			if (f >= (int64_t)t.t0 && (uint64_t)f < end)
-				m[f] = (uint8_t)lw_vd_byte(a, t, l, (uint64_t)f);
-	}
+	lw_mask_write(a.mask + t.mask_at, t.t0, end, tid, [&](uint64_t f) { return lw_vd_byte(a, t, l, f); });
 }
 
 // what a decide workgroup does, in this order (k_vad and k_vad_decide below; tests/san/vad_host.cpp on the host)
@@ -290,15 +189,15 @@ LW_VD_FN void lw_vd_write(const LwVadArgs &a, const LwVdTile &t, const LwVdLds &
 //           decided or d_thr is owed, and the row has a frame; otherwise a.thr's entry, or energy_threshold
 //   stage   where the tile holds a frame: lw_vd_stage_wave, barrier
 //   write   lw_vd_write
-LW_VD_FN bool lw_vd_owes_thr(const LwVadArgs &a, const LwVdTile &t)
+LW_LANES_FN bool lw_vd_owes_thr(const LwVadArgs &a, const LwVdTile &t)
 {
 	return a.thr_out && a.d_thr && t.tile_i == 0;
 }
 
-#ifndef LW_VAD_HOST
+#ifndef LW_KERNEL_HOST
 
 template <bool SUMS>
-LW_VD_FN void lw_vd_workgroup(const LwVadArgs &a, LwVdLds &l)
+LW_LANES_FN void lw_vd_workgroup(const LwVadArgs &a, LwVdLds &l)
 {
 	LwVdTile t;
 	lw_vd_tile(a, blockIdx.x, blockIdx.y, blockIdx.z, t);
@@ -410,4 +309,4 @@ hipError_t lw_launch_vad_fill(float *d_thr, uint64_t n, float value, hipStream_t
 	return lw_launch_k(k_vad_fill, dim3(1), dim3(LW_VD_THREADS), 0, st, d_thr, n, value);
 }
 
-#endif // LW_VAD_HOST
+#endif // LW_KERNEL_HOST

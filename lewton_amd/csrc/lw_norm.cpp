@@ -93,7 +93,7 @@ int lw_norm_rows(lw_norm *nm, uint32_t ch, uint32_t F, const void *d_src, void *
 	uint64_t parts = 0;
 	LwFillSpan m;
 	if (int rc = lw_stage_fill_rows(n_rows, n, fill_to, capacity, d_src, d_dst, m, [&](uint64_t n_i, uint64_t fill_end) {
-		    const uint64_t chunks = (n_i + LW_NM_CHUNK - 1u) / LW_NM_CHUNK;
+		    const uint64_t chunks = (n_i + LW_SUM_CHUNK - 1u) / LW_SUM_CHUNK;
 		    if (lines * chunks > UINT32_MAX) // (chunks < 2^56, lines < 2^24: the product cannot wrap)
 			    return LW_ERR_CAPACITY;
 		    nm->rows.push_back(LwNormRow{n_i, fill_end, parts, (uint32_t)chunks, 0u});

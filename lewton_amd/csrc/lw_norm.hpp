@@ -4,21 +4,14 @@
 // per-row records and the plan.  Kept out of lw_kernels.hpp: no other translation unit sees it.
 #pragma once
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#if defined(__HIPCC__) || defined(__HIP__)
-#define LW_NM_HD __host__ __device__ static inline
-#else
-#define LW_NM_HD static inline
-#endif
+#include "lw_lanes.hpp"
 
 // ---- steps 3 and 4 of the contract.  Every operation below is one IEEE double operation: the units that include this are
 // compiled with -ffp-contract=off.  `scale` is LW_NORM_SCALE_* (0 none, 1 std, 2 rms, 3 peak); peak is |x| of the scope's largest
 // bit pattern.  sqrt: the host's is correctly rounded; the device's expansion (an rsq estimate refined with fma, which gfx950 has in
 // place of a correctly rounded instruction) gave the host's bits on all of 2^24 doubles it was compared on, and the GPU suite
 // compares (m, g) of a million scopes with numpy: no correction step is needed here (DESIGN 3.19 says where one would go).
-LW_NM_HD void lw_norm_scalars_value(int center, int scale, double eps, double target, double S1, double S2, float peak, uint64_t N, double &m,
+LW_LANES_HD void lw_norm_scalars_value(int center, int scale, double eps, double target, double S1, double S2, float peak, uint64_t N, double &m,
 		double &g)
 {
 	m = 0.0, g = 1.0;
@@ -39,7 +32,7 @@ LW_NM_HD void lw_norm_scalars_value(int center, int scale, double eps, double ta
 		g = peak == 0.0f ? 1.0 : target / (double)peak;
 }
 
-LW_NM_HD float lw_norm_apply_value(float x, double m, double g)
+LW_LANES_HD float lw_norm_apply_value(float x, double m, double g)
 {
 	const double c = (double)x - m;
 	return (float)(c * g);
@@ -52,7 +45,7 @@ struct LwNormTriple {
 };
 static_assert(sizeof(LwNormTriple) == 24, "LwNormTriple is stored as three 8-byte words");
 
-LW_NM_HD LwNormTriple lw_nm_add(const LwNormTriple &a, const LwNormTriple &b)
+LW_LANES_HD LwNormTriple lw_wave_add(const LwNormTriple &a, const LwNormTriple &b) // (lw_wave_tree's addition)
 {
 	return LwNormTriple{a.s1 + b.s1, a.s2 + b.s2, a.pk > b.pk ? a.pk : b.pk, 0u};
 }
@@ -69,24 +62,20 @@ static_assert(sizeof(LwNormRow) == 32, "LwNormRow is read as eight dwords");
 
 #define LW_NM_THREADS 256u
 #define LW_NM_WAVES 4u
-#define LW_NM_CHUNK 256u      // elements per chunk, and per run of the apply pass
-#define LW_NM_GROUP 64u       // list entries one tree folds
 #define LW_NM_MAX_TILES 2048u // workgroups per row the plans aim at
 
-// The plan.  k_norm_sum: the chunk slots of a row are numbered line-major over the call's largest chunk count, slot = line *
-// sum_chunks + chunk (a row with fewer chunks leaves its other slots alone); a wave takes sum_per_wave consecutive slots, a
-// workgroup four waves' worth.  Which slot a wave takes decides nothing about the bits: a chunk is summed by one wave on its own.
-// k_norm_fold: one scope per wave (fold_wave, every list of the call has at most 64 entries) or per workgroup, which then keeps
-// the lists of its levels in fold_scratch triples of its own.  k_norm_apply: runs and tiles exactly as lw_feat_plan's.
+// The plan.  k_norm_sum: lw_sum_plan over the chunk slots of all lines of a row (a row with fewer chunks leaves its other slots
+// alone).  k_norm_fold: one scope per wave (fold_wave, every list of the call has at most 64 entries) or per workgroup, which then
+// keeps the lists of its levels in fold_scratch triples of its own.  k_norm_apply: runs of four, lw_run_plan.
 struct LwNormPlan {
-	uint32_t sum_chunks;    // ceil(largest n / 256)
-	uint32_t sum_per_wave;  // slots a wave takes
-	uint32_t sum_tiles;     // workgroups per row
-	uint32_t scopes;        // per row: 1, ch or ch * F
-	uint32_t scope_lines;   // lines per scope: ch * F, F or 1
-	uint32_t fold_wave;     // 1: a wave per scope
-	uint64_t fold_scratch;  // triples per scope (0 under fold_wave)
-	uint32_t runs_per_line; // apply: ceil((span + 3) / 256), at least 1
+	uint32_t sum_chunks;   // ceil(largest n / 256)
+	uint32_t sum_per_wave; // slots a wave takes
+	uint32_t sum_tiles;    // workgroups per row
+	uint32_t scopes;       // per row: 1, ch or ch * F
+	uint32_t scope_lines;  // lines per scope: ch * F, F or 1
+	uint32_t fold_wave;    // 1: a wave per scope
+	uint64_t fold_scratch; // triples per scope (0 under fold_wave)
+	uint32_t runs_per_line; // apply, a LwRunPlan's four: ceil((span + 3) / 256), at least 1
 	uint32_t runs;          // per channel: F * runs_per_line
 	uint32_t per_wave;      // runs a wave takes
 	uint32_t tiles;         // per channel
@@ -95,24 +84,17 @@ struct LwNormPlan {
 // false: a chunk list, or a channel's runs, that 32 bits cannot count
 static inline bool lw_norm_plan(uint32_t ch, uint32_t F, int scope, uint64_t most, uint64_t span, LwNormPlan &p)
 {
-	const uint64_t lines = (uint64_t)ch * F, chunks = (most + LW_NM_CHUNK - 1u) / LW_NM_CHUNK, slots = lines * chunks;
-	const uint64_t rpl = (span + 3u + LW_NM_CHUNK - 1u) / LW_NM_CHUNK, runs = rpl * F;
-	if (chunks > UINT32_MAX || slots > UINT32_MAX || runs > UINT32_MAX)
-		return false;
-	p.sum_chunks = (uint32_t)chunks;
-	const uint64_t sunits = (slots + LW_NM_WAVES - 1u) / LW_NM_WAVES;
-	p.sum_per_wave = (uint32_t)((sunits + LW_NM_MAX_TILES - 1u) / LW_NM_MAX_TILES);
-	p.sum_tiles = p.sum_per_wave ? (uint32_t)((sunits + p.sum_per_wave - 1u) / p.sum_per_wave) : 0u;
+	const uint64_t lines = (uint64_t)ch * F;
 	p.scope_lines = scope == 0 ? (uint32_t)lines : scope == 1 ? F : 1u;
 	p.scopes = (uint32_t)(lines / p.scope_lines);
-	const uint64_t longest = (uint64_t)p.scope_lines * chunks;
-	p.fold_wave = longest <= LW_NM_GROUP;
-	p.fold_scratch = p.fold_wave ? 0u : (longest + 63u) / 64u + (longest + 4095u) / 4096u;
-	const uint32_t aim = LW_NM_MAX_TILES / ch ? LW_NM_MAX_TILES / ch : 1u;
-	const uint64_t units = (runs + LW_NM_WAVES - 1u) / LW_NM_WAVES;
-	p.runs_per_line = (uint32_t)rpl, p.runs = (uint32_t)runs;
-	p.per_wave = (uint32_t)((units + aim - 1u) / aim);
-	p.tiles = (uint32_t)((units + p.per_wave - 1u) / p.per_wave);
+	LwSumPlan s;
+	LwRunPlan r;
+	if (!lw_sum_plan(most, lines, p.scope_lines, LW_NM_MAX_TILES, s) || !lw_run_plan(ch, F, span, LW_NM_MAX_TILES, r))
+		return false;
+	p.runs_per_line = r.runs_per_line, p.runs = r.runs, p.per_wave = r.per_wave, p.tiles = r.tiles;
+	p.sum_chunks = s.chunks, p.sum_per_wave = s.per_wave, p.sum_tiles = s.tiles;
+	p.fold_wave = s.longest <= LW_SUM_GROUP;
+	p.fold_scratch = p.fold_wave ? 0u : s.fold_scratch;
 	return true;
 }
 

@@ -4,14 +4,7 @@
 // launcher.  Kept out of lw_kernels.hpp: no other translation unit sees it.
 #pragma once
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#if defined(__HIPCC__) || defined(__HIP__)
-#define LW_PK_HD __host__ __device__ static inline
-#else
-#define LW_PK_HD static inline
-#endif
+#include "lw_lanes.hpp"
 
 #define LW_PK_THREADS 256u // a workgroup
 #define LW_PK_GROUP 32u    // feature lines in the LDS image at a time: one line per bank
@@ -24,14 +17,14 @@
 #define LW_PK_VALID 1
 
 // ---- the contract's conversions of an f32 bit pattern
-LW_PK_HD uint32_t lw_pack_bf16(uint32_t u)
+LW_LANES_HD uint32_t lw_pack_bf16(uint32_t u)
 {
 	if ((u & 0x7fffffffu) > 0x7f800000u) // a NaN first: the rounding below would carry some into infinity or zero
 		return (u >> 16) | 0x40u;
 	return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
 }
 
-LW_PK_HD uint32_t lw_pack_f16(uint32_t u)
+LW_LANES_HD uint32_t lw_pack_f16(uint32_t u)
 {
 	const uint32_t s = (u >> 16) & 0x8000u, a = u & 0x7fffffffu;
 	if (a > 0x7f800000u)
@@ -51,13 +44,13 @@ LW_PK_HD uint32_t lw_pack_f16(uint32_t u)
 	return s | r;
 }
 
-LW_PK_HD uint32_t lw_pack_cvt(int dtype, uint32_t u)
+LW_LANES_HD uint32_t lw_pack_cvt(int dtype, uint32_t u)
 {
 	return dtype == LW_PK_BF16 ? lw_pack_bf16(u) : dtype == LW_PK_F16 ? lw_pack_f16(u) : u;
 }
 
 // T_out of a row of T frames
-LW_PK_HD uint64_t lw_pack_out_frames(int edge, uint32_t W, uint32_t stride, uint64_t T)
+LW_LANES_HD uint64_t lw_pack_out_frames(int edge, uint32_t W, uint32_t stride, uint64_t T)
 {
 	if (edge == LW_PK_VALID)
 		return T < W ? 0u : (T - W) / stride + 1u;

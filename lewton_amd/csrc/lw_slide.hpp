@@ -5,14 +5,7 @@
 // plan, the kernel's arguments and the launcher.  Kept out of lw_kernels.hpp: no other translation unit sees it.
 #pragma once
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#if defined(__HIPCC__) || defined(__HIP__)
-#define LW_SL_HD __host__ __device__ static inline
-#else
-#define LW_SL_HD static inline
-#endif
+#include "lw_lanes.hpp"
 
 #define LW_SL_THREADS 256u        // a workgroup
 #define LW_SL_BLOCK 16u           // frames of a block sum (rule 2)
@@ -25,7 +18,7 @@
 #define LW_SL_MAX_TILES 0xffffffu // workgroups in a grid's first dimension: tiles * line groups * 256 lanes stays below 2^32
 
 // ---- rule 1: the window [s, e) of frame t of a line of T frames (t < T)
-LW_SL_HD void lw_slide_window_value(uint32_t W, uint32_t min_window, int center, uint64_t t, uint64_t T, int64_t &s, int64_t &e)
+LW_LANES_HD void lw_slide_window_value(uint32_t W, uint32_t min_window, int center, uint64_t t, uint64_t T, int64_t &s, int64_t &e)
 {
 	const int64_t it = (int64_t)t, iT = (int64_t)T;
 	if (center) {
@@ -51,7 +44,7 @@ LW_SL_HD void lw_slide_window_value(uint32_t W, uint32_t min_window, int center,
 
 // ---- rule 4: from the window's sums to the output value.  Every operation is one IEEE double operation.  sqrt: as lw_norm.hpp
 // says of the device's expansion.
-LW_SL_HD float lw_slide_value(int norm_vars, float x, double S, double Q, uint64_t n)
+LW_LANES_HD float lw_slide_value(int norm_vars, float x, double S, double Q, uint64_t n)
 {
 	const double dn = (double)n;
 	const double mu = S / dn;

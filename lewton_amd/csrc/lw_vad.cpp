@@ -128,7 +128,7 @@ int lw_vad_rows(lw_vad *v, uint32_t ch, uint32_t F, const void *d_src, uint8_t *
 	LwFillSpan span;
 	uint64_t list = 0; // doubles of the chunk lists: every row's [ch][chunks]
 	if (int rc = lw_stage_fill_rows(n_rows, n_frames, fill_to, frame_capacity, d_src, d_mask, span, [&](uint64_t n, uint64_t fill_end) {
-			const uint64_t chunks = (n + LW_VD_CHUNK - 1u) / LW_VD_CHUNK;
+			const uint64_t chunks = (n + LW_SUM_CHUNK - 1u) / LW_SUM_CHUNK;
 			if (chunks > UINT32_MAX)
 				return LW_ERR_CAPACITY;
 			v->rows.push_back(LwVadRow{n, fill_end, list, (uint32_t)chunks, 0u});

@@ -5,19 +5,11 @@
 // no other translation unit sees it.
 #pragma once
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#if defined(__HIPCC__) || defined(__HIP__)
-#define LW_VD_HD __host__ __device__ static inline
-#else
-#define LW_VD_HD static inline
-#endif
+#include "lw_lanes.hpp"
 
 #define LW_VD_THREADS 256u        // a workgroup
 #define LW_VD_WAVES 4u
-#define LW_VD_CHUNK 256u          // frames per chunk of the sum
-#define LW_VD_GROUP 64u           // list entries one tree folds
+#define LW_VD_CHUNK LW_SUM_CHUNK   // frames per chunk of the sum: the one of "normalising rows"
 #define LW_VD_TILE 1024u          // frames of a tile unless a test says otherwise: a multiple of 256 in 256 .. 2048
 #define LW_VD_MAX_TILE 2048u
 #define LW_VD_MAX_CONTEXT 256u    // LW_VAD_MAX_CONTEXT
@@ -26,11 +18,11 @@
 #define LW_VD_SUM_TILES 2048u     // workgroups per row and channel k_vad_sum's plan aims at
 #define LW_VD_WORDS ((LW_VD_MAX_TILE + 2u * LW_VD_MAX_CONTEXT) / 64u) // ballot words of a tile and its context either side
 // LDS of k_vad, static: 64 chunk sums + the raw decisions of the tile and its context
-#define LW_VD_LDS (LW_VD_GROUP * 8u + LW_VD_WORDS * 8u)
+#define LW_VD_LDS (LW_SUM_GROUP * 8u + LW_VD_WORDS * 8u)
 
 // ---- rule 1, behind the sum.  Every operation is ONE IEEE f32 operation: the units that include this are compiled with
 // -ffp-contract=off.  (float)T is the round-to-nearest-even conversion of the uint64.
-LW_VD_HD float lw_vad_threshold_value(float energy_threshold, float energy_mean_scale, double S, uint64_t T)
+LW_LANES_HD float lw_vad_threshold_value(float energy_threshold, float energy_mean_scale, double S, uint64_t T)
 {
 	if (energy_mean_scale == 0.0f || T == 0)
 		return energy_threshold;
@@ -41,7 +33,7 @@ LW_VD_HD float lw_vad_threshold_value(float energy_threshold, float energy_mean_
 }
 
 // ---- rule 3: ONE rounded f32 multiply, as Kaldi's int * BaseFloat
-LW_VD_HD bool lw_vad_voiced_value(uint64_t num, uint64_t den, float proportion_threshold)
+LW_LANES_HD bool lw_vad_voiced_value(uint64_t num, uint64_t den, float proportion_threshold)
 {
 	const float need = (float)den * proportion_threshold;
 	return (float)num >= need;
@@ -86,14 +78,10 @@ static inline bool lw_vad_tile_ok(uint32_t tile)
 // k_vad_sum's plan from the call's longest row: false where 32 bits cannot count the chunks
 static inline bool lw_vad_sum_plan(uint64_t most, LwVadArgs &a)
 {
-	const uint64_t chunks = (most + LW_VD_CHUNK - 1u) / LW_VD_CHUNK;
-	if (chunks > UINT32_MAX)
+	LwSumPlan s;
+	if (!lw_sum_plan(most, 1u, 1u, LW_VD_SUM_TILES, s))
 		return false;
-	const uint64_t units = (chunks + LW_VD_WAVES - 1u) / LW_VD_WAVES;
-	a.sum_chunks = (uint32_t)chunks;
-	a.sum_per_wave = (uint32_t)((units + LW_VD_SUM_TILES - 1u) / LW_VD_SUM_TILES);
-	a.sum_tiles = a.sum_per_wave ? (uint32_t)((units + a.sum_per_wave - 1u) / a.sum_per_wave) : 0u;
-	a.fold_scratch = (chunks + 63u) / 64u + (chunks + 4095u) / 4096u;
+	a.sum_chunks = s.chunks, a.sum_per_wave = s.per_wave, a.sum_tiles = s.tiles, a.fold_scratch = s.fold_scratch;
 	return true;
 }
 

@@ -1,4 +1,4 @@
-// What every host program that runs a KERNEL source on the CPU shares (cep, fbank, feat, istft, norm, pack, resample, select, slide,
+// What every host program that runs a KERNEL source on the CPU shares (cep, fbank, feat, istft, lanes, norm, pack, resample, select, slide,
 // spec, spec_complex, spec_reflect), included behind hip_standins.inc: the lw_hip_ok stand-in, the launch log, guarded buffers,
 // sentinel fills, files that are read and written whole or not at all, and the exit codes.  rows_host, rows_mix_host and fmt_host
 // take the file helpers alone.  tests/san/kernel_host_selftest.cpp holds the guarded buffer against ASan itself.  Test
