@@ -1093,6 +1093,80 @@ int lw_cut_rows(lw_cut *c, uint32_t ch, uint32_t F, uint32_t elem_bytes, const v
 		const uint64_t *jobs, size_t n_out, void *d_dst, size_t out_capacity, const uint64_t *fill_to, void *hip_stream);
 int lw_cut_last_launches(const lw_cut *c);
 
+/* ---- masking feature rows -----------------------------------------------------------------------------------------------------
+ * SpecAugment (Park et al. 2019) without its time warp, on the GPU, as a pass of its own (k_specaug): a few time masks and a few
+ * frequency masks per utterance, the step every training recipe puts between the normalised features and the model.  Source and
+ * destination are f32 [row][ch][F][frame_capacity], the layout of every stage before it; a planar waveform is F = 1, so time
+ * masks on waveforms are the same call.  Row i has T = n_frames[i] frames and an id ids[i]; ids is a HOST uint64 array, NULL means
+ * id = the row's index.  The library draws its random numbers from a counter-based generator, Philox4x32-10 (Salmon et al., SC'11;
+ * lewton_amd/csrc/lw_rng.hpp, plain integer arithmetic, no state): an utterance's masks are a pure function of (seed, id) -- the same
+ * in any batch, at any row position, on any grid, and reproducible from a log line that holds the two numbers.
+ * A GROUP g is channel c when per_channel is set, else 0: then all channels of a row share their masks.  Mask k of kind d (0 = a
+ * time mask over n = T, 1 = a frequency mask over n = F) of group g, all in unsigned 64-bit integers:
+ *   x     = philox(counter = (id & 0xffffffff, id >> 32, k | g << 16, d), key = (seed & 0xffffffff, seed >> 32))
+ *   W     = min(max_d, n);  for d == 0 and ratio_den != 0:  W = min(W, (n / ratio_den) * ratio_num + ((n % ratio_den) * ratio_num) / ratio_den)
+ *   lo    = min(min_d, W)
+ *   w     = lo + ((uint64)x[0] * (W - lo + 1) >> 32)
+ *   start = the high 64 bits of the 128-bit product ((uint64)x[1] << 32 | x[2]) * (n - w + 1);   end = start + w      (x[3] is not used)
+ * Philox: multipliers 0xD2511F53 (on counter word 0) and 0xCD9E8D57 (on word 2), ten rounds, 0x9E3779B9 / 0xBB67AE85 added to the
+ * key words before every round but the first; one round maps (c0, c1, c2, c3) to (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^
+ * k1, lo(M0 c0)).  Both draws are multiply-high without rejection: biased by at most (W + 1) / 2^32 and (n + 1) / 2^64.
+ * Known answers, seed 2024, k = 0, g = 0, widths 0 .. 50:  id 0, T = 3000: [797, 827);  id 1, T = 3000: [1300, 1317);  id 0, a
+ * frequency mask of 0 .. 10 over F = 80: [40, 40), an empty mask;  id 7, T = 100, ratio 1/5: [78, 84);  id 7, T = 3, min 5: [0, 3);
+ * T = 0: [0, 0);  id 0, T = 2^32 + 2^20 + 5: [1153752137, 1153752167);  id 6099, k = 18, the same T, widths 0 .. 65535:
+ * [4294953827, 4294968123), a mask that straddles frame 2^32.
+ * The width is drawn first and the start over what it leaves, so a mask lies WHOLLY inside the row: torchaudio's form (mask_along_axis),
+ * not WeNet's, which draws the start over the whole row and cuts the mask at the row's end.  ratio_num / ratio_den is torchaudio's p
+ * and the upper end of ESPnet's time_mask_width_ratio_range: no time mask is wider than that share of the row's own length.
+ * Element (c, f, t) with t < T is MASKED when some time mask of its group has start <= t < end or some frequency mask has start <=
+ * f < end; masks may overlap and may be empty.  dst = masked ? fill : src, both sides BIT COPIES: fill's own bits, NaN payloads
+ * and -0.0 included.  Positions [T, max(T, fill_to[row])) of every line receive +0.0.  Nothing else of d_dst is written; nothing
+ * of d_src at or beyond T is read.  d_src == d_dst is allowed (any other overlap is the caller's error): then only the masked
+ * elements and the fill span are written, and nothing is read.  d_spans, when given, receives (start, end) as int64 pairs
+ * [n_rows][G][num_t + num_f][2], time masks first, G = ch with per_channel, else 1; rows with T == 0 are included.
+ *
+ * lw_specaug_rows: n_frames, fill_to (may be NULL: nothing is filled) and ids are HOST arrays, copied during the call.
+ * Asynchronous on hip_stream; calls on one object may be queued back to back.  ONE kernel launch per 65535 rows: a workgroup of 256
+ * lanes takes a tile of lw_specaug_tile_frames frames (2048) of one line; its first num_t + num_f lanes each draw one mask of the
+ * group into LDS (no list travels between launches: the masks are drawn again wherever they are needed), then the tile streams
+ * through in groups of four frames, 16-byte loads and stores where the line's address allows and dwords at the ragged head and
+ * tail; a group that is all fill is not loaded.  In place a workgroup whose tile meets no mask and no fill span returns without
+ * touching memory.  There is no launch without rows or when nothing can be written: out of place no row has a position below
+ * max(T, fill_to); in place no masks are configured or no row has a frame, and no row has a fill span; in both cases no d_spans.
+ * No atomics, no workgroup waits on another.  A workgroup needs 1024 bytes of LDS.
+ * lw_specaug_plan: the rule on the host, from the same source as the kernel's: spans receives the num_t + num_f pairs of one
+ * group of an utterance of T frames and F bins.  lw_specaug_set_tile_frames: a test's handle on the seams, a multiple of 256 in
+ * 256 .. 2048.  lw_specaug_last_launches: the kernels the last accepted call queued, -1 = no call yet.
+ * Refusals, decided on the host before anything is queued:
+ *   LW_ERR_NULL_ARG     sa, p or spans NULL, n_frames NULL with rows, d_src NULL with frames to read, d_dst NULL with elements to write
+ *   LW_ERR_UNSUPPORTED  (create) min_t > max_t or min_f > max_f; num_t or num_f > LW_SPECAUG_MAX_MASKS; max_t or max_f >
+ *                       LW_SPECAUG_MAX_WIDTH; ratio_num > ratio_den; ratio_den > 65535; per_channel not 0 or 1; reserved != 0;
+ *                       (set_tile_frames) a tile that is no multiple of 256 in 256 .. 2048
+ *   LW_ERR_DEVICE       (create) no such device
+ *   LW_ERR_CAPACITY     n_frames[i] or fill_to[i] > frame_capacity, ch == 0 or > 255, F == 0 or > 65535, a buffer that 64 bits of
+ *                       bytes cannot address, more than 2^24 - 1 workgroups (tiles * F) in a channel; (plan) group or F > 65535,
+ *                       T > 2^63 - 1 (its spans are int64) */
+#define LW_SPECAUG_MAX_MASKS 32    /* per kind */
+#define LW_SPECAUG_MAX_WIDTH 65535 /* frames or bins of one mask */
+typedef struct lw_specaug lw_specaug;
+typedef struct {
+	uint64_t seed;
+	uint32_t num_t, min_t, max_t; /* time masks: how many, and the least and the largest width in frames */
+	uint32_t ratio_num, ratio_den; /* ... none wider than ratio_num / ratio_den of the row's frames; ratio_den 0: no such limit */
+	uint32_t num_f, min_f, max_f; /* frequency masks, in bins */
+	uint32_t per_channel;         /* 1: every channel draws masks of its own */
+	float fill;                   /* what a masked element receives, bit for bit */
+	uint32_t reserved;            /* 0 */
+} lw_specaug_params;
+lw_specaug *lw_specaug_create(int device, const lw_specaug_params *p, int *err);
+void lw_specaug_destroy(lw_specaug *sa);
+int lw_specaug_rows(lw_specaug *sa, uint32_t ch, uint32_t F, const void *d_src, void *d_dst, size_t n_rows, size_t frame_capacity,
+		const uint64_t *n_frames, const uint64_t *fill_to, const uint64_t *ids, int64_t *d_spans, void *hip_stream);
+int lw_specaug_plan(const lw_specaug *sa, uint64_t id, uint32_t group, uint64_t T, uint32_t F, int64_t *spans);
+uint32_t lw_specaug_tile_frames(const lw_specaug *sa);
+int lw_specaug_set_tile_frames(lw_specaug *sa, uint32_t tile);
+int lw_specaug_last_launches(const lw_specaug *sa);
+
 /* ---- staging ring (BASELINE north_star: "pinned hipMemcpyAsync staging ring so entropy decode of packet N+1 overlaps
  * GPU synthesis of packet N") ------------------------------------------------------------------------------------------
  * A ring of `slots` staging slots on the decoder's device; a slot = one batch object (pinned records + device mirror), a device

@@ -91,6 +91,12 @@ class SegmentParams(C.Structure):
     _fields_ = [("pad_onset", C.c_uint32), ("pad_offset", C.c_uint32), ("min_off", C.c_uint32), ("min_on", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class SpecAugParams(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("num_t", C.c_uint32), ("min_t", C.c_uint32), ("max_t", C.c_uint32), ("ratio_num", C.c_uint32),
+                ("ratio_den", C.c_uint32), ("num_f", C.c_uint32), ("min_f", C.c_uint32), ("max_f", C.c_uint32), ("per_channel", C.c_uint32),
+                ("fill", C.c_uint32), ("reserved", C.c_uint32)]   # fill: the float's bits (a c_float would pass a NaN through a double)
+
+
 class OggPacket(C.Structure):
     _fields_ = [("data", C.c_void_p), ("len", C.c_size_t), ("stream_serial", C.c_uint32), ("absgp_page", C.c_uint64),
                 ("first_in_stream", C.c_uint8), ("last_in_stream", C.c_uint8), ("first_in_page", C.c_uint8),
@@ -283,6 +289,14 @@ SYMBOLS = {
     "lw_cut_rows": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
                               C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "lw_cut_last_launches": (C.c_int, [C.c_void_p]),
+    "lw_specaug_create": (C.c_void_p, [C.c_int, C.POINTER(SpecAugParams), intp]),
+    "lw_specaug_destroy": (None, [C.c_void_p]),
+    "lw_specaug_rows": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lw_specaug_plan": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(C.c_int64)]),
+    "lw_specaug_tile_frames": (C.c_uint32, [C.c_void_p]),
+    "lw_specaug_set_tile_frames": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "lw_specaug_last_launches": (C.c_int, [C.c_void_p]),
     "lw_ring_create": (C.c_void_p, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, intp]),
     "lw_ring_destroy": (None, [C.c_void_p]),
     "lw_ring_stage": (C.c_int, [C.c_void_p, C.POINTER(Packet), C.c_size_t, C.c_int]),

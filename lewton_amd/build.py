@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "_lib")
 LIB = os.path.join(LIBDIR, "liblewton_amd.so")
-SOURCES = ["lw_headers.cpp", "lw_entropy.cpp", "lw_dev_entropy.cpp", "lw_pool.cpp", "lw_runtime.cpp", "lw_batch.cpp", "lw_packet.cpp", "lw_fast.cpp", "lw_ring.cpp", "lw_shard.cpp", "lw_ogg.cpp", "lw_rows.cpp", "lw_rows_mix.cpp", "lw_resample.cpp", "lw_spec.cpp", "lw_istft.cpp", "lw_feat.cpp", "lw_norm.cpp", "lw_cep.cpp", "lw_pack.cpp", "lw_slide.cpp", "lw_select.cpp", "lw_vad.cpp", "lw_segment.cpp", "lw_cut.cpp", "lw_capi.cpp", "lw_kernels.hip", "lw_kernels_long.hip", "lw_kernels_big.hip", "lw_kernels_entropy.hip", "lw_kernels_rows.hip", "lw_kernels_rows_mix.hip", "lw_kernels_resample.hip", "lw_kernels_spec.hip", "lw_kernels_istft.hip", "lw_kernels_feat.hip", "lw_kernels_norm.hip", "lw_kernels_cep.hip", "lw_kernels_pack.hip", "lw_kernels_slide.hip", "lw_kernels_select.hip", "lw_kernels_vad.hip", "lw_kernels_segment.hip", "lw_kernels_cut.hip"]
+SOURCES = ["lw_headers.cpp", "lw_entropy.cpp", "lw_dev_entropy.cpp", "lw_pool.cpp", "lw_runtime.cpp", "lw_batch.cpp", "lw_packet.cpp", "lw_fast.cpp", "lw_ring.cpp", "lw_shard.cpp", "lw_ogg.cpp", "lw_rows.cpp", "lw_rows_mix.cpp", "lw_resample.cpp", "lw_spec.cpp", "lw_istft.cpp", "lw_feat.cpp", "lw_norm.cpp", "lw_cep.cpp", "lw_pack.cpp", "lw_slide.cpp", "lw_select.cpp", "lw_vad.cpp", "lw_segment.cpp", "lw_cut.cpp", "lw_specaug.cpp", "lw_capi.cpp", "lw_kernels.hip", "lw_kernels_long.hip", "lw_kernels_big.hip", "lw_kernels_entropy.hip", "lw_kernels_rows.hip", "lw_kernels_rows_mix.hip", "lw_kernels_resample.hip", "lw_kernels_spec.hip", "lw_kernels_istft.hip", "lw_kernels_feat.hip", "lw_kernels_norm.hip", "lw_kernels_cep.hip", "lw_kernels_pack.hip", "lw_kernels_slide.hip", "lw_kernels_select.hip", "lw_kernels_vad.hip", "lw_kernels_segment.hip", "lw_kernels_cut.hip", "lw_kernels_specaug.hip"]
 ARCH = os.environ.get("LW_OFFLOAD_ARCH", "gfx950")  # e.g. gfx950:xnack- for an experiment
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-Wall",
          "-Wno-unused-result", "-pthread"]

@@ -72,6 +72,11 @@ speaker-embedding extractor or a diarizer gets its segments with one synchronisa
     jobs, _ = Segments.jobs(spans, counts, hop=160, window=400, lengths=lengths)      # the one synchronisation
     seg_pcm, seg_len = CutRows().run(pcm, lengths, jobs)
 
+SpecAugment is the one step a training loader puts between the normalised features and the model (lw_specaug_rows, k_specaug: time
+and frequency masks drawn by a counter-based generator, so an utterance's masks depend on (seed, id) alone, bit for bit):
+
+    SpecAugment.wenet(seed=epoch).run(feats, frames, ids=utterance_ids)     # in place
+
 torch is imported inside the functions, never at module import.
 """
 import ctypes as C
@@ -1350,6 +1355,123 @@ class CutRows(_Handle):
         self._call(N.lw_cut_rows, ch, F, _CUT_SAMPLES[samples], _tensor_ptr(src), n_rows, cap, _array_ptr(lens), _array_ptr(jb if n_out else None), n_out,
                    _tensor_ptr(out), out.shape[-1], _array_ptr(fill), _stream_of(stream, self.device))
         return out, torch.tensor(out_len.tolist(), dtype=torch.int64)
+
+
+SPECAUG_MAX_MASKS, SPECAUG_MAX_WIDTH = 32, 65535          # LW_SPECAUG_MAX_MASKS, LW_SPECAUG_MAX_WIDTH
+
+
+def _specaug_params(num_time_masks, time_mask_param, num_freq_masks, freq_mask_param, min_time, min_freq, p, per_channel, fill, seed, device):
+    """(the fields of lw_specaug_params in the structure's order, device), or ValueError for what lw_specaug_create refuses"""
+    from fractions import Fraction
+    for v, what, most in ((num_time_masks, "num_time_masks", SPECAUG_MAX_MASKS), (num_freq_masks, "num_freq_masks", SPECAUG_MAX_MASKS),
+                          (time_mask_param, "time_mask_param", SPECAUG_MAX_WIDTH), (freq_mask_param, "freq_mask_param", SPECAUG_MAX_WIDTH),
+                          (min_time, "min_time", SPECAUG_MAX_WIDTH), (min_freq, "min_freq", SPECAUG_MAX_WIDTH), (seed, "seed", (1 << 64) - 1)):
+        if not _is_int(v) or not 0 <= v <= most:
+            raise ValueError("%s=%r: an integer in 0 .. %d" % (what, v, most))
+    if min_time > time_mask_param or min_freq > freq_mask_param:
+        raise ValueError("min_time=%r, min_freq=%r: at most time_mask_param=%r, freq_mask_param=%r" % (min_time, min_freq, time_mask_param, freq_mask_param))
+    if isinstance(p, (bool, np.bool_)) or not isinstance(p, (int, float, np.integer, np.floating, Fraction)) or not 0 <= p <= 1:
+        raise ValueError("p=%r: a share of the row's frames in [0, 1]" % (p,))
+    ratio = (p if isinstance(p, Fraction) else Fraction(float(p))).limit_denominator(65535)
+    num, den = (0, 0) if p == 1.0 else (ratio.numerator, ratio.denominator)      # 1.0: no limit from the row's length
+    if not isinstance(per_channel, (bool, np.bool_)):
+        raise ValueError("per_channel=%r: True or False" % (per_channel,))
+    if isinstance(fill, (bool, np.bool_)) or not isinstance(fill, (int, float, np.integer, np.floating)):
+        raise ValueError("fill=%r: a number" % (fill,))
+    with np.errstate(over="ignore"):
+        fill_bits = int(np.array(fill, np.float32).view(np.uint32))               # a float32 scalar keeps its own bits
+    return (int(seed), int(num_time_masks), int(min_time), int(time_mask_param), num, den, int(num_freq_masks), int(min_freq), int(freq_mask_param),
+            int(bool(per_channel)), fill_bits, 0), _device_number(device)
+
+
+class SpecAugment(_Handle):
+    """lw_specaug: SpecAugment's time and frequency masks (Park et al. 2019, without the time warp) over feature rows
+    [rows][C][F][capacity] or waveforms [rows][C][capacity] on the GPU (k_specaug), by the rule of include/lewton_amd.h ("masking
+    feature rows"), a contract on bits.  The masks of an utterance are a pure function of (seed, id): the same in any batch, at any
+    row position, on any grid -- log the two numbers and the augmentation can be run again.  num_time_masks masks of min_time ..
+    time_mask_param frames (none wider than p times the row's own frames; p = 1.0: no such limit) and num_freq_masks masks of
+    min_freq .. freq_mask_param bins, each wholly inside the row (torchaudio's form); masked elements receive fill, bit for bit.
+    per_channel: every channel draws masks of its own.  Parameter errors are ValueError and need no GPU; the object itself lives
+    on cuda:device."""
+
+    _C = "lw_specaug"
+
+    def __init__(self, num_time_masks=2, time_mask_param=50, num_freq_masks=2, freq_mask_param=10, min_time=0, min_freq=0, p=1.0, per_channel=False,
+                 fill=0.0, seed=0, device=0):
+        fields, self.device = _specaug_params(num_time_masks, time_mask_param, num_freq_masks, freq_mask_param, min_time, min_freq, p, per_channel, fill,
+                                              seed, device)
+        self.seed, self.num_time_masks, self.num_freq_masks, self.per_channel = fields[0], fields[1], fields[6], bool(fields[9])
+        _gpu()
+        params = N.SpecAugParams(*fields)
+        self._create(self.device, C.byref(params))
+
+    @classmethod
+    def paper(cls, policy="LD", **kw):
+        """the LibriSpeech policies of the paper without their time warp: F = 27, T = 100, p = 1.0; "LB" one mask of each kind,
+        "LD" two"""
+        if policy not in ("LB", "LD"):
+            raise ValueError("policy=%r: \"LB\" or \"LD\"" % (policy,))
+        m = 1 if policy == "LB" else 2
+        return cls(num_time_masks=m, time_mask_param=100, num_freq_masks=m, freq_mask_param=27, p=1.0, **kw)
+
+    @classmethod
+    def wenet(cls, **kw):
+        """WeNet's spec_aug defaults: two time masks of 1 .. 50 frames and two frequency masks of 1 .. 10 bins (inside the row, where
+        WeNet cuts a mask at the row's end)"""
+        return cls(num_time_masks=2, time_mask_param=50, num_freq_masks=2, freq_mask_param=10, min_time=1, min_freq=1, **kw)
+
+    @property
+    def tile_frames(self):
+        """frames of a tile (lw_specaug_tile_frames)"""
+        return N.lw_specaug_tile_frames(self._h)
+
+    def set_tile_frames(self, m):
+        """a test's handle on the seams (lw_specaug_set_tile_frames): a multiple of 256 in 256 .. 2048; the result does not depend on it"""
+        if not _is_int(m) or not 0 <= m < 1 << 32 or N.lw_specaug_set_tile_frames(self._h, int(m)):
+            raise ValueError("tile_frames=%r: a multiple of 256 in 256 .. 2048" % (m,))
+
+    def last_launches(self):
+        """kernels the last call queued: 1 per 65535 rows, 0 when nothing could be written; -1: no call yet"""
+        return N.lw_specaug_last_launches(self._h)
+
+    def plan(self, id, T, F, group=0):
+        """the rule on the host (lw_specaug_plan): [(start, end)] of the num_time_masks + num_freq_masks masks, time masks first, of
+        group `group` (a channel with per_channel, else 0) of utterance id with T frames and F bins"""
+        for v, what, most in ((id, "id", (1 << 64) - 1), (T, "T", (1 << 63) - 1), (F, "F", 65535), (group, "group", 65535)):
+            if not _is_int(v) or not 0 <= v <= most:
+                raise ValueError("%s=%r: an integer in 0 .. %d" % (what, v, most))
+        n = self.num_time_masks + self.num_freq_masks
+        spans = (C.c_int64 * (2 * n + 1))()
+        self._call(N.lw_specaug_plan, int(id), int(group), int(T), int(F), spans)
+        return [(spans[2 * i], spans[2 * i + 1]) for i in range(n)]
+
+    def run(self, feats, frames, ids=None, out=None, fill_to=None, want_spans=False, stream=None):
+        """lw_specaug_rows: the frames[i] frames of row i of feats (float32 [rows][C][F][capacity], or a waveform [rows][C][capacity]:
+        F = 1) masked as utterance ids[i] (None: the row's index) -> out (None: IN PLACE, and feats is returned; else a tensor of
+        feats' shape on its device); positions [frames[i], fill_to[i]) of every line receive 0 (fill_to: None, one count for all
+        rows or one per row).  Nothing else of out is written; in place only the masked elements and the fill span are.  stream: a
+        hipStream_t value; None = torch's current stream on the object's device.  Asynchronous; returns out, and with want_spans
+        (out, spans), spans an int64 [rows][G][masks][2] device tensor of (start, end), G = C with per_channel, else 1."""
+        torch = _gpu()
+        _check_tensor(feats, "feats", "[rows][C][F][capacity] or [rows][C][capacity]", self.device, (torch.float32,), (3, 4))
+        n_rows, ch = feats.shape[:2]
+        F, cap = (1, feats.shape[2]) if feats.dim() == 3 else (feats.shape[2], feats.shape[3])
+        if out is None:
+            out = feats
+        _check_tensor(out, "out", "of feats' shape %r" % (tuple(feats.shape),), self.device, (torch.float32,), shape=tuple(feats.shape))
+        counts, fill = _row_counts(frames, n_rows, "frames"), _row_fill(fill_to, n_rows)
+        if ids is not None:
+            ids = [int(v) for v in (ids.tolist() if hasattr(ids, "tolist") else ids)]
+            if len(ids) != n_rows or any(not 0 <= v < 1 << 64 for v in ids):
+                raise ValueError("ids= needs one utterance id in 0 .. 2^64 - 1 per row")
+            ids = np.asarray(ids, np.uint64)
+        spans = None
+        if want_spans:
+            spans = torch.empty((n_rows, ch if self.per_channel else 1, self.num_time_masks + self.num_freq_masks, 2), dtype=torch.int64,
+                                device=feats.device)
+        self._call(N.lw_specaug_rows, ch, F, _tensor_ptr(feats), _tensor_ptr(out), n_rows, cap, _array_ptr(counts), _array_ptr(fill), _array_ptr(ids),
+                   _tensor_ptr(spans), _stream_of(stream, self.device))
+        return (out, spans) if want_spans else out
 
 
 CEP_MAX_IN,CEP_MAX_OUT, CEP_MAX_WIDTH = 256, 256, 16     # LW_CEP_MAX_IN, LW_CEP_MAX_OUT, LW_CEP_MAX_WIDTH
