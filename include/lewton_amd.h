@@ -98,6 +98,36 @@ void lw_decoder_destroy(lw_decoder *d);
 const char *lw_last_device_error(void);
 
 /* ---- PreviousWindowRight (src/audio.rs:847-861) ------------------------------------------- */
+/* A handle is a slot of the decoder's state pool, [slot][2 parities][ch][n1 / 2] floats on the device, and three host fields:
+ * whether a right part is stored, its length, and which of the slot's two buffers holds it (lw_pwr_state below).  Planning a batch
+ * (lw_batch_entropy, lw_ring_stage) advances the host fields at once; the device buffers follow when that batch is launched, and a
+ * launch reads one buffer of a slot and writes the OTHER.  Between the two the host fields are AHEAD of the device.  What each call
+ * keeps (tests/test_gpu_stream_state.py pins these on every synthesis kernel family):
+ *   lw_pwr_clone         copies both buffers of the slot after a device synchronisation, and the host fields as they are.  Batches of
+ *                        the stream that were launched need not be collected; a batch that is planned and NOT yet launched makes the
+ *                        twin wrong: its host fields name a buffer that batch has still to write.  Launch first, then clone.  Takes a
+ *                        slot like lw_pwr_new (below), so it can move the pool.
+ *   lw_pwr_copy_to_host  the same condition: it synchronises the device and reads the buffer the host fields name.  Does not move the
+ *                        pool, but reads its address: not next to a lw_pwr_new / lw_decoder_reserve_streams on another thread.
+ *   lw_pwr_reset         host fields only.  Batches planned before it, launched or not, decode as planned (their records carry slot and
+ *                        buffer); the next batch planned for the stream starts from no previous window.  Nothing has to be finished.
+ *   lw_pwr_free          host only: the slot goes on top of the decoder's free list and the next lw_pwr_new / lw_pwr_clone takes it
+ *                        (most recently freed first).  Batches of the stream still planned or in flight need not be finished, PROVIDED
+ *                        the slot's next stream is launched behind them: one ring launches in the order it staged (lw_ring_launch), so
+ *                        freeing straight after lw_ring_submit and reusing the slot in that ring's next batches is sound.  Two rings (or
+ *                        two HIP streams) of one decoder are NOT ordered against each other: collect the freed stream's last batch
+ *                        before a stream of the other ring can take its slot.  The handle itself is gone at once: it must not appear
+ *                        in a later lw_packet.
+ *   lw_pwr_new, lw_decoder_reserve_streams   the pool MOVES when it grows (64 slots at first, doubled by lw_pwr_new, exactly n by
+ *                        lw_decoder_reserve_streams): device synchronisation, allocation, copy of every slot's two buffers, free.
+ *                        Everything launched before the call is finished by the synchronisation and every live state arrives in the
+ *                        new pool; batches planned and not yet launched are unaffected (a launch reads the pool's address when it is
+ *                        issued).  But a launch call reads that address without the decoder's lock: lw_pwr_new, lw_pwr_clone and
+ *                        lw_decoder_reserve_streams must not run while ANOTHER thread is inside lw_batch_synth* / lw_ring_launch /
+ *                        lw_ring_submit of the same decoder -- a ring's stage thread that opens streams next to its launch thread
+ *                        reserves its slots first (lw_decoder_reserve_streams).  lw_sharder_stream_open between lw_sharder_submit and
+ *                        the collect is sound: submit returns once the call's launches are issued (tests/test_host_shard.py).
+ * None of these calls is synchronised against lw_batch_entropy / lw_ring_stage of a batch that names the same handle. */
 lw_pwr *lw_pwr_new(lw_decoder *d);         /* PreviousWindowRight::new */
 int lw_pwr_is_empty(const lw_pwr *p);      /* ::is_empty */
 lw_pwr *lw_pwr_clone(const lw_pwr *p);     /* #[derive(Clone)] (device copy) */

@@ -4,7 +4,9 @@
 // against the same packets through a one-shard sharder run call by call: statuses, sample counts and block offsets of every
 // packet must agree (the offsets after mapping the shard-by-shard layout), and a stream's packets must stay on one shard.
 // Test harness (tests/test_host_shard.py).
-//   usage: shard_host case.bin shards streams per_call calls [device_entropy]
+//   usage: shard_host case.bin shards streams per_call calls [device_entropy [mode]]
+//   mode 1: a failed launch on one shard; mode 2: ten more streams opened per call while the call is in flight, so that a shard's
+//   state pool moves (at its 65th and its 129th stream) between lw_sharder_submit and the collect of that call
 //   case.bin: u32 n_cases(ignored) | u32 len ident | u32 len setup | u32 n_packets | (u32 len, bytes)*
 #include "../../include/lewton_amd.h"
 
@@ -50,7 +52,8 @@ int main(int argc, char **argv)
 		return 2;
 	const size_t G = (size_t)atoi(argv[2]), S = (size_t)atoi(argv[3]), per = (size_t)atoi(argv[4]), calls = (size_t)atoi(argv[5]);
 	const bool dev_entropy = argc > 6 && atoi(argv[6]) != 0;
-	const bool fail_mode = argc > 7 && atoi(argv[7]) != 0;
+	const bool fail_mode = argc > 7 && atoi(argv[7]) == 1;
+	const size_t grow = argc > 7 && atoi(argv[7]) == 2 ? 10 : 0; // streams opened per call, between the submit and its collect
 	uint32_t nc, npk;
 	std::vector<uint8_t> idp, stp;
 	if (!rd(f, nc) || !rdv(f, idp) || !rdv(f, stp) || !rd(f, npk))
@@ -67,7 +70,7 @@ int main(int argc, char **argv)
 	lw_ident_get_info(id, &info);
 	lw_setup *setup = lw_read_header_setup(stp.data(), stp.size(), info.audio_channels, info.blocksize_0, info.blocksize_1, &err);
 	CHECK(setup, "setup header: %d", err);
-	const size_t n_call = S * per, ch = info.audio_channels, n1 = (size_t)1 << info.blocksize_1;
+	const size_t n_call = (S + grow * calls) * per, ch = info.audio_channels, n1 = (size_t)1 << info.blocksize_1;
 	std::vector<int> devs(G, 0), one(1, 0);
 	{ // with the measurement hook every logical shard gets its own CUs: [32 j / G, 32 (j + 1) / G) of each of the 8 XCDs.  FIRST in
 	  // this process: once a ring of an unshared tenant has made the device's copier stream, CU shares are refused (lewton_amd.h)
@@ -166,6 +169,57 @@ int main(int argc, char **argv)
 		lw_setup_free(setup);
 		lw_ident_free(id);
 		printf("sharder failure ok: shard %zu of %zu restarted, older calls reported, %zu calls\n", dead_shard, G, calls);
+		return 0;
+	}
+	if (grow) {
+		// ---- lw_batch.cpp reads the decoder's pool pointer for a launch without the decoder's mutex; lw_pwr_new replaces it under
+		// the mutex when the pool is full.  lw_sharder_submit returns once the call's launches are queued, so a stream opened after it
+		// moves the pool behind them.  A opens its streams between a submit and that call's collect, B between the calls.
+		size_t alike = 0;
+		for (size_t c = 0; c < calls; c++) {
+			const size_t live = A.st.size(), n = live * per;
+			for (Side *side : {&A, &B}) {
+				for (size_t s = 0; s < live; s++)
+					for (size_t k = 0; k < per; k++) {
+						const auto &p = packet_of(c, s, k);
+						pk[s * per + k] = lw_shard_packet{side->st[s], p.data(), p.size()};
+					}
+				size_t &elems = side == &A ? elemsA[c] : elemsB[c];
+				std::vector<lw_packet_result> &res = side == &A ? resA[c] : resB[c];
+				int rc = lw_sharder_submit(side->sh, pk.data(), n, 2, &elems);
+				CHECK(rc == LW_OK, "submit of call %zu: %d", c, rc);
+				if (side == &A)
+					for (size_t j = 0; j < grow; j++) {
+						A.st.push_back(lw_sharder_stream_open(A.sh, 1000 + 7 * A.st.size()));
+						CHECK(A.st.back(), "stream_open with call %zu in flight", c);
+					}
+				rc = lw_sharder_collect(side->sh, side == &A ? outA.data() : outB.data(), cap, res.data(), n);
+				CHECK(rc == LW_OK, "collect of call %zu: %d", c, rc);
+				if (side == &B)
+					for (size_t j = 0; j < grow; j++) {
+						B.st.push_back(lw_sharder_stream_open(B.sh, 1000 + 7 * B.st.size()));
+						CHECK(B.st.back(), "stream_open after call %zu", c);
+					}
+			}
+			CHECK(elemsA[c] == elemsB[c], "call %zu: %zu elements against %zu", c, elemsA[c], elemsB[c]);
+			for (size_t i = 0; i < n; i++) {
+				const lw_packet_result &a = resA[c][i], &b = resB[c][i];
+				CHECK(a.status == b.status && a.n_samples == b.n_samples, "call %zu packet %zu: status %d / %u samples against %d / %u", c, i,
+				      a.status, a.n_samples, b.status, b.n_samples);
+				alike++;
+			}
+		}
+		const size_t streams = A.st.size();
+		CHECK(streams == S + grow * calls && streams / G > 128, "%zu streams on %zu shards: no shard's pool moved twice", streams, G);
+		for (auto *s : A.st)
+			lw_sharder_stream_close(s);
+		for (auto *s : B.st)
+			lw_sharder_stream_close(s);
+		lw_sharder_destroy(A.sh);
+		lw_sharder_destroy(B.sh);
+		lw_setup_free(setup);
+		lw_ident_free(id);
+		printf("sharder growth ok: %zu shards, %zu streams after %zu calls, %zu packets alike\n", G, streams, calls, alike);
 		return 0;
 	}
 	// ---- B: call by call

@@ -71,3 +71,16 @@ def test_a_failed_launch_restarts_one_shard_and_older_calls_say_so(harness, tmp_
     out = subprocess.run([harness, case, "3", "9", "4", "6", "0", "1"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     assert "sharder failure ok" in out.stdout, out.stdout
+
+
+def test_streams_opened_while_a_call_is_in_flight_move_the_pool_behind_its_launches(harness, tmp_path):
+    """lw_batch.cpp reads the decoder's state-pool pointer for a launch without the decoder's mutex, lw_pwr_new replaces it under the
+    mutex when the pool is full (64 slots, then doubled).  lw_sharder_submit returns once its launches are queued, so ten streams
+    opened between every submit and its collect -- the shard's pool moves at its 65th and its 129th stream -- race with nothing
+    (ThreadSanitizer), and the calls decode like those of a sharder whose streams are opened between the calls."""
+    case = str(tmp_path / "case.bin")
+    _case(case, SETUPS["stereo"](), "LLSSLSL", 90, seed=43)
+    env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1")
+    out = subprocess.run([harness, case, "1", "40", "2", "11", "0", "2"], env=env, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+    assert "sharder growth ok: 1 shards, 150 streams after 11 calls" in out.stdout, out.stdout
